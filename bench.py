@@ -14,8 +14,13 @@ i.e. readFile + callSiteMLError + the output loop (call.cpp:11-20, :213-289,
 sid.cpp:102-105) through the streaming engine (include/sid.h sid_engine_*,
 host-text source, 128 MiB chunks, host_hold_bytes: each chunk's records are
 copied back while later chunks upload, so PCIe runs both ways at once).
-Beside it, in the same line:
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K
+steps and prints the line: value, ms_per_step, the step's PCIe figures and the
+ranks' placement.  `--dump-outputs DIR` also writes what the last timed step
+left for its caller (dump_outputs below).  With `--full`, beside it, in the
+same line (each a run of its own, after the timed steps):
 
+  spot_check    each rank's first chunk of records against the oracle CLI
   device_path   the same run over the text already resident in HBM with the
                 records left in HBM (device_sink 1): the kernels alone, per
                 stage, with the roofline of the dominant stage
@@ -98,8 +103,14 @@ def parse_args(argv=None):
     p.add_argument("--device-steps", type=int, default=0, help="device_path steps (0 = max(steps, 10))")
     p.add_argument("--slots", type=int, default=0, help="PCIe path: device text buffers per GPU (0 = the engine's 3)")
     p.add_argument("--pcie-chunk-mib", type=int, default=0, help="PCIe path chunk size (0 = the engine's 128 MiB)")
-    p.add_argument("--no-extras", action="store_true", help="skip kernel_local, cli and cpu_baseline")
-    p.add_argument("--no-cpu", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="beside the timed value leg: spot_check, device_path and roofline, kernel_local, cli, "
+                        "cpu_baseline (a plain run sets up, warms up, times the steps and prints the line)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps: what the last step left for its caller (the CSV records in the "
+                        "host arena, the Lynch paths' estimate) as DIR/<name>.npy (a seeded sample of the records)")
+    p.add_argument("--no-extras", action="store_true", help="--full: skip kernel_local, cli and cpu_baseline")
+    p.add_argument("--no-cpu", action="store_true", help="--full: skip cpu_baseline")
     p.add_argument("--device-only", action="store_true",
                    help="profiling: only the device_path leg (its line's value is then the device path's)")
     p.add_argument("--allow-shared-gpu", action="store_true",
@@ -110,6 +121,8 @@ def parse_args(argv=None):
                         "DIR/rank<r>.csv and its estimate to DIR/rank<r>.json (parity tests)")
     p.add_argument("--no-node-cli", action="store_true", help="N > 1: skip the whole-node CLI leg")
     a = p.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps takes a count of at least 1, --warmup one of at least 0")
     if a.config is None:
         a.config = {"likelihood_ratio": "C3", "bayes": "C3B"}.get(a.method, "C2")
     return a
@@ -460,13 +473,15 @@ def bench_weak(R, a, cfg):
     elapsed, st, st2, est, eng = pcie_leg(R, a, cfg, host, ln, n, lynch)
     sites_all = R.sum_over_ranks(st.sites)
     placement = R.gather(R.placement(host))
-    if lynch and R.dist is None:   # (one untimed step more: the profile table for the spot check)
+    if a.dump_outputs:
+        dump_outputs(R, a, eng, st, est if lynch else None)
+    if a.full and lynch and R.dist is None:   # (one untimed step more: the profile table for the spot check)
         R.run_step(eng, lynch, capture=True)
     # the first chunk's records from the host arena, for every rank's spot
     # check against the oracle (-m local: the records of a prefix of the text
     # do not depend on the rest; the Lynch paths: given the global profile
     # table, neither do they)
-    spot = eng.records_bytes(1)
+    spot = eng.records_bytes(1) if a.full else None
     if a.dump_records:
         os.makedirs(a.dump_records, exist_ok=True)
         with open(os.path.join(a.dump_records, f"rank{R.rank}.csv"), "wb") as f:
@@ -482,11 +497,11 @@ def bench_weak(R, a, cfg):
     pcie = pcie_stats(a, ln, st, st2, elapsed, lynch)
     eng.close()
     del host
-    spot = spot_check_ranks(R, a, cfg, text, ln, spot, R.last_table if lynch else None)
-
-    dp = device_path(R, a, cfg, text, ln, lynch)
-    node_cli, node_cpu = None, None
-    if R.world > 1 and not a.no_extras and not a.no_node_cli:
+    dp, node_cli, node_cpu = None, None, None
+    if a.full:
+        spot = spot_check_ranks(R, a, cfg, text, ln, spot, R.last_table if lynch else None)
+        dp = device_path(R, a, cfg, text, ln, lynch)
+    if a.full and R.world > 1 and not a.no_extras and not a.no_node_cli:
         holder = [text]
         text = None   # the rank's text is freed before the CLI takes the GPUs (the N = 1 extras do not run)
         node_cli, node_cpu = bench_cli_node(R, cfg, holder, ln, n)
@@ -517,10 +532,9 @@ def bench_weak(R, a, cfg):
                    "rccl_world": R.world if R.dist is not None and R.backend == "nccl" else None,
                    "numa": placement},
         "pcie": pcie,
-        "spot_check": spot,
-        "roofline": dp.pop("roofline"),
-        "device_path": dp,
     }
+    if a.full:
+        out.update({"spot_check": spot, "roofline": dp.pop("roofline"), "device_path": dp})
     if lynch:
         out["estimate"] = {"pi": est.heterozygosity, "eps": est.error_rate, "iterations": est.iterations,
                            "n_unique": est.n_unique}
@@ -528,7 +542,7 @@ def bench_weak(R, a, cfg):
         out["cli"] = node_cli
     if node_cpu is not None and not a.no_cpu:
         out["cpu_baseline"] = node_cpu
-    if R.world == 1 and not a.no_extras:
+    if a.full and R.world == 1 and not a.no_extras:
         out["kernel_local"] = bench_kernel_local(torch, R.dev, cfg, n)
         out["cli"] = bench_cli(cfg, text, ln, n)
         if not a.no_cpu:
@@ -671,6 +685,66 @@ def pcie_stats(a, ln, st, st2, elapsed, lynch):
     return pcie
 
 
+DUMP_SAMPLE_RECORDS = 100_000   # --dump-outputs: records sampled over all ranks (~43 B each: 17 MB as float32)
+DUMP_SAMPLE_SEED = 0x51D
+
+
+def records_arrays(chunks, budget):
+    """--dump-outputs: the records of a run (chunks: each chunk's CSV bytes as
+    a uint8 array, in file order) as float arrays.
+      chunk_summary        float64 [chunks, 3]: every chunk's record count,
+                           byte count and byte sum (the whole output)
+      record_sample        float64 [k, 4]: a fixed, seeded sample of about
+                           budget records (the same share of every chunk, in
+                           file order): the record's index in the output, its
+                           pos, hom_conf and het_conf as printed
+      record_sample_bytes  float32: the sampled records' bytes, end to end
+    The sample depends only on the chunks' record counts, so two builds that
+    print the same records give the same arrays."""
+    import numpy as np
+    per_chunk = max(1, budget // max(1, len(chunks)))
+    summary = np.zeros((len(chunks), 3), np.float64)
+    rows, lines, base = [], [], 0
+    for j, buf in enumerate(chunks):
+        ends = np.flatnonzero(buf == 10) + 1   # one record a line
+        m = len(ends)
+        summary[j] = (m, len(buf), buf.sum(dtype=np.uint64))
+        rng = np.random.default_rng([DUMP_SAMPLE_SEED, j])
+        for i in np.sort(rng.choice(m, min(m, per_chunk), replace=False)):
+            line = buf[ends[i - 1] if i else 0:ends[i]]
+            f = line.tobytes().rstrip(b"\n").split(b",")
+            try:
+                rows.append((base + i, float(f[1]), float(f[4]), float(f[5])))
+            except (IndexError, ValueError):
+                rows.append((base + i, math.nan, math.nan, math.nan))
+            lines.append(line)
+        base += m
+    sample = np.array(rows, np.float64).reshape(-1, 4)
+    raw = np.concatenate(lines).astype(np.float32) if lines else np.zeros(0, np.float32)
+    return {"chunk_summary": summary, "record_sample": sample, "record_sample_bytes": raw[:12 << 20]}
+
+
+def dump_outputs(R, a, eng, st, est):
+    """--dump-outputs DIR: what the last timed step left for its caller -- the
+    CSV records in the engine's host arena (records_arrays) and, for the Lynch
+    paths, the estimate (float64 [pi, eps, iterations, n_unique]) -- as
+    DIR/<name>.npy (N > 1: DIR/rank<r>_<name>.npy, the sample shared out
+    over the ranks)."""
+    import ctypes
+    import numpy as np
+    chunks = []
+    for j in range(st.chunks):
+        p, m = eng.records(j)
+        chunks.append(np.frombuffer((ctypes.c_ubyte * m).from_address(p), np.uint8) if m else np.zeros(0, np.uint8))
+    arrays = records_arrays(chunks, DUMP_SAMPLE_RECORDS // R.world)
+    if est is not None:
+        arrays["estimate"] = np.array([est.heterozygosity, est.error_rate, est.iterations, est.n_unique], np.float64)
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    prefix = f"rank{R.rank}_" if R.world > 1 else ""
+    for name, arr in arrays.items():
+        np.save(os.path.join(a.dump_outputs, prefix + name + ".npy"), arr)
+
+
 def bench_strong(R, a, cfg):
     """C4 / C5 on the metric's footing (in-memory pileup text
     -> CSV): each rank takes 1/8 of the config's sites (C4: 375M sites, 30.4 GB
@@ -705,14 +779,17 @@ def bench_strong(R, a, cfg):
     elapsed, st, st2, est, eng = pcie_leg(R, a, cfg, host, ln, n, lynch)
     sites_all = R.sum_over_ranks(st.sites)
     placement = R.gather(R.placement(host))
-    spot = eng.records_bytes(1)
+    if a.dump_outputs:
+        dump_outputs(R, a, eng, st, est if lynch else None)
+    spot = eng.records_bytes(1) if a.full else None
     pcie = pcie_stats(a, ln, st, st2, elapsed, lynch)
     eng.close()
     del host
-    spot = spot_check_ranks(R, a, cfg, text, ln, spot, None)
-    if not a.chunk_mib:
-        a.chunk_mib = STRONG_RESIDENT_CHUNK_MIB
-    dp = device_path(R, a, cfg, text, ln, lynch)
+    if a.full:
+        spot = spot_check_ranks(R, a, cfg, text, ln, spot, None)
+        if not a.chunk_mib:
+            a.chunk_mib = STRONG_RESIDENT_CHUNK_MIB
+        dp = device_path(R, a, cfg, text, ln, lynch)
     out = {
         "metric": METRIC,
         "value": sites_all * a.steps / elapsed,
@@ -736,14 +813,13 @@ def bench_strong(R, a, cfg):
                    "parallelism": f"site-range shards x{R.world}", "ranks": R.world,
                    "oversubscribed": R.oversub, "numa": placement},
         "pcie": pcie,
-        "spot_check": spot,
-        "roofline": dp.pop("roofline"),
-        "device_path": dp,
         "generator": {"ms": gen_ms, "inside_step": False,
                       "note": "the shard's text generated into HBM (then copied to pinned host memory), before "
                               "the timed region"},
     }
-    if R.world == 1 and not a.no_extras and not a.no_cpu:
+    if a.full:
+        out.update({"spot_check": spot, "roofline": dp.pop("roofline"), "device_path": dp})
+    if a.full and R.world == 1 and not a.no_extras and not a.no_cpu:
         out["cpu_baseline"] = bench_cpu(cfg, text, ln, n, R.cpus0,
                                         sample_sites=50_000_000 if cfg["depth"] < 100 else 10_000_000)
     return out, []

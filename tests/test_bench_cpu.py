@@ -85,3 +85,41 @@ def test_bench_cpu(bench, oracle, text_c3, config):
             assert rs["port_over_reference"]["single_core"] > 0
     else:
         assert res["cores"] == 1 and "global" in res["sample"]
+
+
+def test_records_arrays(bench):
+    """--dump-outputs' arrays over a stored CSV cut into three uneven chunks:
+    the summary counts every record and byte, the sample is the same from call
+    to call, each sampled row is the record at its index as printed, and a
+    changed digit outside the sample still changes the summary."""
+    import gzip
+    with gzip.open(os.path.join(ROOT, "tests", "golden", "c1_10k.local.csv.gz")) as f:
+        rows = f.read().split(b"\n")[1:-1]
+    cuts = [0, 17, 4001, len(rows)]
+    chunks = [np.frombuffer(b"".join(r + b"\n" for r in rows[lo:hi]), np.uint8) for lo, hi in zip(cuts, cuts[1:])]
+    got = bench.records_arrays(chunks, 300)
+    again = bench.records_arrays(chunks, 300)
+    assert sorted(got) == ["chunk_summary", "record_sample", "record_sample_bytes"]
+    for k in got:
+        assert got[k].dtype in (np.float32, np.float64) and np.array_equal(got[k], again[k])
+    s = got["chunk_summary"]
+    assert s[:, 0].tolist() == [17, 3984, len(rows) - 4001]
+    assert s[:, 1].sum() == sum(len(c) for c in chunks)
+    assert s[:, 2].tolist() == [float(c.sum(dtype=np.uint64)) for c in chunks]
+    sample = got["record_sample"]
+    assert len(sample) == 17 + 100 + 100 and np.all(np.diff(sample[:, 0]) > 0)
+    want = b""
+    for i, pos, hom, het in sample:
+        f = rows[int(i)].split(b",")
+        assert (pos, hom, het) == (float(f[1]), float(f[4]), float(f[5]))
+        want += rows[int(i)] + b"\n"
+    assert got["record_sample_bytes"].astype(np.uint8).tobytes() == want
+    k = next(i for i in range(len(rows)) if i not in set(sample[:, 0].astype(int)))
+    j = sum(k >= c for c in cuts[1:])
+    changed = bytearray(chunks[j].tobytes())
+    at = sum(len(r) + 1 for r in rows[cuts[j]:k]) + len(rows[k]) - len(b",p_value") - 1
+    assert chr(changed[at]).isdigit()
+    changed[at] = ord("0") + (changed[at] - ord("0") + 1) % 10
+    other = bench.records_arrays(chunks[:j] + [np.frombuffer(bytes(changed), np.uint8)] + chunks[j + 1:], 300)
+    assert not np.array_equal(other["chunk_summary"], s)
+    assert np.array_equal(other["record_sample"], sample)

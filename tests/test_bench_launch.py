@@ -12,7 +12,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
-SMALL = ["--sites", "200000", "--steps", "1", "--warmup", "0", "--device-steps", "1", "--no-extras"]
+SMALL = ["--full", "--sites", "200000", "--steps", "1", "--warmup", "0", "--device-steps", "1", "--no-extras"]
 
 
 def run_bench(args, timeout):
@@ -75,6 +75,48 @@ def assert_self_checked(d, ranks):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("config", ["C2", "C3"])
+def test_plain_run_times_the_steps_and_dumps_its_outputs(config, tmp_path):
+    """A plain run (no --full): the headline line alone -- the steps asked
+    for, ms_per_step and value from the same clock -- without the legs that
+    take runs of their own; --dump-outputs writes the last timed step's
+    records as float arrays (bench.py records_arrays), here beside the whole
+    CSV of the same run (--dump-records): the summary counts its records and
+    bytes, and the sampled records are the CSV's lines at their indices."""
+    import numpy as np
+    n = 300_000
+    out, rec = tmp_path / "out", tmp_path / "rec"
+    r = run_bench(["--gpus", "1", "--config", config, "--sites", str(n), "--steps", "3", "--warmup", "1",
+                   "--dump-outputs", str(out), "--dump-records", str(rec)], 300)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith('{"metric"')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "sites/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(n / (d["ms_per_step"] * 1e-3), rel=1e-9)
+    for k in ("spot_check", "device_path", "roofline", "kernel_local", "cli", "cpu_baseline"):
+        assert k not in d
+    names = ["chunk_summary", "record_sample", "record_sample_bytes"] + (["estimate"] if config == "C3" else [])
+    assert sorted(p.name for p in out.iterdir()) == sorted(x + ".npy" for x in names)
+    got = {x: np.load(out / (x + ".npy")) for x in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    csv = (rec / "rank0.csv").read_bytes()
+    rows = csv.split(b"\n")[:-1]
+    assert got["chunk_summary"][:, 0].sum() == len(rows) > 0
+    assert got["chunk_summary"][:, 1].sum() == len(csv) == d["config"]["csv_bytes_rank0"]
+    assert got["chunk_summary"][:, 2].sum() == float(np.frombuffer(csv, np.uint8).sum(dtype=np.uint64))
+    sample = got["record_sample"]
+    per_chunk = 100_000 // len(got["chunk_summary"])   # (the same share of every chunk)
+    assert len(sample) == sum(min(int(m), per_chunk) for m in got["chunk_summary"][:, 0])
+    assert np.all(np.diff(sample[:, 0]) > 0)
+    assert got["record_sample_bytes"].astype(np.uint8).tobytes() == b"".join(rows[int(i)] + b"\n" for i in sample[:, 0])
+    if config == "C3":
+        j = json.loads((rec / "rank0.json").read_text())
+        assert got["estimate"].tolist() == [j["pi"], j["eps"], j["iterations"], j["n_unique"]]
+
+
+@pytest.mark.gpu
 @pytest.mark.timeout(900)
 def test_two_rank_lynch_exchange_equals_one_process(sid, oracle, gpu, tmp_path):
     """C3's one collective (bench.py Rank.lynch_step_exchange): two ranks, each
@@ -89,7 +131,7 @@ def test_two_rank_lynch_exchange_equals_one_process(sid, oracle, gpu, tmp_path):
     n = 2_000_000
     dump = tmp_path / "dump"
     r = run_bench(["--gpus", "2", "--allow-shared-gpu", "--config", "C3", "--sites", str(n), "--steps", "1",
-                   "--warmup", "0", "--device-steps", "1", "--no-extras", "--dump-records", str(dump)], 600)
+                   "--warmup", "0", "--device-steps", "1", "--full", "--no-extras", "--dump-records", str(dump)], 600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     d = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith('{"metric"')][0])
     assert d["config"]["ranks"] == 2 and d["config"]["sites_total"] == 2 * n
@@ -132,7 +174,7 @@ def test_shared_gpu_rehearsal_runs_the_node_cli(config):
     if visible_gpus() != 1:
         pytest.skip("the rehearsal case: one visible GPU")
     args = ["--gpus", "2", "--allow-shared-gpu", "--config", config, "--sites", "300000", "--steps", "1",
-            "--warmup", "0", "--device-steps", "1"]
+            "--warmup", "0", "--device-steps", "1", "--full"]
     r = run_bench(args, 500)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     d = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith('{"metric"')][0])
@@ -169,7 +211,7 @@ def test_strong_config_value_leg():
     """C5 (bench.py bench_strong) at a small total: the rank's eighth as
     pinned host text through the value leg's engine, device_path beside it."""
     r = run_bench(["--config", "C5", "--sites", "1600000", "--steps", "2", "--warmup", "1", "--device-steps", "2",
-                   "--no-extras"], 500)
+                   "--full", "--no-extras"], 500)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     d = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith('{"metric"')][0])
     assert d["config"]["sites_per_gpu"] == 200_000 and d["config"]["sites_all_ranks"] == 200_000

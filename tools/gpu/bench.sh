@@ -7,7 +7,7 @@ CFGS=()
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do CFGS+=("$1"); shift; done
 [ "$1" = "--" ] && shift
 for c in "${CFGS[@]:-C2}"; do
-    timeout -k 10 600 python3 -u bench.py --config $c "$@" > $O/bench_${c,,}_$TAG.json 2> $O/bench_${c,,}_$TAG.err \
+    timeout -k 10 600 python3 -u bench.py --full --config $c "$@" > $O/bench_${c,,}_$TAG.json 2> $O/bench_${c,,}_$TAG.err \
         || { echo "bench $c failed"; tail $O/bench_${c,,}_$TAG.err; exit 1; }
     summary $O/bench_${c,,}_$TAG.json
 done

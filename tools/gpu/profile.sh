@@ -20,7 +20,7 @@ pmc() {   # group counters...
 for pass in ${PASSES:-trace dtrace insts fetch write}; do
     case $pass in
     trace) ( cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $P/trace -o trace -- \
-               python3 $OLDPWD/bench.py --steps 20 --warmup 5 --no-cpu "$@" > $P/trace.json 2> $P/trace.log ) \
+               python3 $OLDPWD/bench.py --full --steps 20 --warmup 5 --no-cpu "$@" > $P/trace.json 2> $P/trace.log ) \
                || { echo "trace failed"; tail -3 $P/trace.log; exit 1; } ;;
     dtrace) ( cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $P/dtrace -o trace -- \
                python3 $OLDPWD/bench.py --device-only --steps 10 "$@" > $P/dtrace.json 2> $P/dtrace.log ) \
