@@ -26,6 +26,14 @@
  *     gt[1] base, bit 7 = het label, bit 6 = site dropped (its profile was
  *     filtered, coverage < 4, and the reference prints no record for it:
  *     call.cpp:131-140).
+ *   - Selection by label (sid_opts.select: SID_SELECT_ALL, _HET, _HOM): every
+ *     formatter bound to a context -- the engine, sid_dtext_format and the
+ *     chunk formatters behind them -- emits only the records whose label is
+ *     the context's selection, byte for byte and in the order of the
+ *     unselected output.  The calls and the Lynch estimate see every site;
+ *     the per-site arrays (code / confs) are not changed by it.  Host
+ *     formatting (sid_format_csv) takes no context: sid_select_mark marks the
+ *     codes first.
  *   - Counts layout: profile_t (pileup.hpp:7) = 4 x uint16 {A,C,G,T} per site,
  *     array of structures, 8 bytes per site.
  */
@@ -73,6 +81,8 @@ const char* sid_version(void);
 #define SID_CODE_DROPPED 0x40
 
 enum { SID_METHOD_LOCAL = 0, SID_METHOD_LIKELIHOOD_RATIO = 1, SID_METHOD_BAYES = 2, SID_METHOD_QUALITY = 3 };
+/* which records a formatter emits, by their label field (--only) */
+enum { SID_SELECT_ALL = 0, SID_SELECT_HET = 1, SID_SELECT_HOM = 2 };
 
 /* GlobalOptions, sid.cpp:11-17 */
 typedef struct {
@@ -81,8 +91,16 @@ typedef struct {
     double snp_prior;            /* -r   (default -1 = no prior)                   */
     double significance_level;   /* -p   (default 0.05)                            */
     double site_error_threshold; /* -E   (default 0.1)                             */
+    int select;                  /* --only (default SID_SELECT_ALL): the records
+                                    emitted, by label; sid_create and
+                                    sid_engine_create return SID_EINVAL for any
+                                    other value                                    */
 } sid_opts;
 void sid_opts_default(sid_opts* o);
+/* Sets SID_CODE_DROPPED on the n host codes whose label is not `select`, so
+ * that sid_format_csv skips them (SID_SELECT_ALL: nothing changes).
+ * SID_EINVAL for another value of select or a NULL code with n != 0. */
+int sid_select_mark(uint8_t* code /* host */, size_t n, int select);
 
 /* ------------------------------------------------------------- contexts -- */
 typedef struct sid_ctx sid_ctx;
@@ -319,7 +337,8 @@ typedef struct {
     uint64_t sites;              /* non-empty lines parsed                           */
     uint64_t chunks;
     uint64_t bytes_in;           /* input text bytes                                 */
-    uint64_t bytes_out;          /* CSV bytes (header excluded)                      */
+    uint64_t bytes_out;          /* CSV bytes written (header excluded; with a
+                                    selection: the selected records')               */
     uint64_t chunks_held;        /* formatted in the first pass                      */
     uint64_t chunks_retained;    /* text kept in HBM for the second pass             */
     uint64_t chunks_reloaded;    /* text read from the source a second time          */

@@ -48,7 +48,7 @@ class SidError(RuntimeError):
 class Opts(C.Structure):
     """sid_opts = GlobalOptions (sid.cpp:11-17)."""
     _fields_ = [("method", C.c_int), ("estimate_prior", C.c_int), ("snp_prior", C.c_double),
-                ("significance_level", C.c_double), ("site_error_threshold", C.c_double)]
+                ("significance_level", C.c_double), ("site_error_threshold", C.c_double), ("select", C.c_int)]
 
 
 class Estimate(C.Structure):
@@ -97,6 +97,7 @@ SIGNATURES = [
     ("sid_last_hip_error", _I, []),
     ("sid_version", C.c_char_p, []),
     ("sid_opts_default", None, [C.POINTER(Opts)]),
+    ("sid_select_mark", _I, [_P, _SZ, _I]),
     ("sid_device_count", _I, [C.POINTER(C.c_int)]),
     ("sid_create", _I, [_I, C.POINTER(Opts), C.POINTER(_P)]),
     ("sid_destroy", _I, [_P]),
@@ -188,8 +189,11 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 
 
+SELECT = {"all": 0, "het": 1, "hom": 2}   # SID_SELECT_*: the records emitted, by label (--only)
+
+
 def make_opts(method="local", estimate_prior=False, snp_prior=-1.0, significance_level=0.05,
-              site_error_threshold=0.1) -> Opts:
+              site_error_threshold=0.1, select="all") -> Opts:
     o = Opts()
     lib().sid_opts_default(C.byref(o))
     o.method = METHODS[method] if isinstance(method, str) else int(method)
@@ -197,6 +201,9 @@ def make_opts(method="local", estimate_prior=False, snp_prior=-1.0, significance
     o.snp_prior = float(snp_prior)
     o.significance_level = float(significance_level)
     o.site_error_threshold = float(site_error_threshold)
+    if isinstance(select, str) and select not in SELECT:
+        raise SidError(1, f"select: expected one of {sorted(SELECT)}, got {select!r}")
+    o.select = SELECT[select] if isinstance(select, str) else int(select)
     return o
 
 
@@ -261,6 +268,17 @@ def format_csv(sites: Sites, code: np.ndarray, hom: np.ndarray, het: np.ndarray,
     check(L.sid_format_csv(sites.handle, begin, n, _ptr(code), _ptr(hom), _ptr(het), conf_type.encode(),
                            buf, need.value, C.byref(ln)), "format")
     return buf.raw[: ln.value]
+
+
+def select_mark(code: np.ndarray, select="all") -> np.ndarray:
+    """sid_select_mark on a copy of the codes: the sites whose label is not
+    `select` get SID_CODE_DROPPED, so format_csv skips them."""
+    out = np.array(code, np.uint8, copy=True)
+    if isinstance(select, str) and select not in SELECT:
+        raise SidError(1, f"select: expected one of {sorted(SELECT)}, got {select!r}")
+    check(lib().sid_select_mark(_ptr(out), out.size, SELECT[select] if isinstance(select, str) else int(select)),
+          "sid_select_mark")
+    return out
 
 
 def format_double(v: float) -> str:

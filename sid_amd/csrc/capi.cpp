@@ -59,6 +59,7 @@ extern "C" void sid_opts_default(sid_opts* o)
     o->snp_prior = -1;
     o->significance_level = 0.05;
     o->site_error_threshold = 0.1;
+    o->select = SID_SELECT_ALL;
 }
 
 // GSL 2.7.1 specfunc/gamma.c lngamma_lanczos (x >= 0.5, away from 1 and 2,
@@ -116,7 +117,7 @@ static hipError_t sid_build_table(sid_ctx* c)
 {
     if (c->K.general) return hipSuccess;
     hipError_t e = sid_launch_local_table_build(&c->K, c->d_lnt, c->ws.table, c->ws.table2, nullptr);
-    if (e == hipSuccess) e = sid_launch_local_str_build(&c->K, c->ws.table, c->ws.table2, &c->ws, nullptr);
+    if (e == hipSuccess) e = sid_launch_local_str_build(&c->K, c->ws.table, c->ws.table2, &c->ws, c->opts.select, nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     return e;
 }
@@ -125,6 +126,7 @@ extern "C" int sid_create(int device, const sid_opts* opts, sid_ctx** out)
 {
     if (!out) return SID_EINVAL;
     *out = nullptr;
+    if (opts && (opts->select < SID_SELECT_ALL || opts->select > SID_SELECT_HOM)) return SID_EINVAL;
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return sid_set_hip_error(e);
     sid_ctx* c = new sid_ctx();
@@ -148,6 +150,10 @@ extern "C" int sid_create(int device, const sid_opts* opts, sid_ctx** out)
     if (e == hipSuccess) e = hipMalloc(&c->ws.len1, tab);
     if (e == hipSuccess) e = hipMalloc(&c->ws.str2, (size_t)SID_TAB2_N * SID_STR_BYTES);
     if (e == hipSuccess) e = hipMalloc(&c->ws.len2, SID_TAB2_N);
+    if (c->opts.select != SID_SELECT_ALL) {   // the filtered twins of len1 / len2 (sid_local_ws)
+        if (e == hipSuccess) e = hipMalloc(&c->ws.len1f, tab);
+        if (e == hipSuccess) e = hipMalloc(&c->ws.len2f, SID_TAB2_N);
+    }
     if (e == hipSuccess) e = hipMalloc(&c->ws.miss, (size_t)c->ws.cap * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc(&c->ws.ctr, 2 * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemset(c->ws.ctr, 0, 2 * sizeof(uint32_t));
@@ -169,7 +175,8 @@ extern "C" int sid_destroy(sid_ctx* c)
     if (c->d_cdf) (void)hipFree(c->d_cdf);
     if (c->ws.table) (void)hipFree(c->ws.table);
     if (c->ws.table2) (void)hipFree(c->ws.table2);
-    for (void* p : {(void*)c->ws.str1, (void*)c->ws.len1, (void*)c->ws.str2, (void*)c->ws.len2})
+    for (void* p : {(void*)c->ws.str1, (void*)c->ws.len1, (void*)c->ws.str2, (void*)c->ws.len2, (void*)c->ws.len1f,
+                    (void*)c->ws.len2f})
         if (p) (void)hipFree(p);
     if (c->ws.miss) (void)hipFree(c->ws.miss);
     if (c->ws.ctr) (void)hipFree(c->ws.ctr);

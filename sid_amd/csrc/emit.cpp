@@ -103,3 +103,17 @@ extern "C" int sid_format_csv(const sid_sites* s, size_t begin, size_t end, cons
     *len = (size_t)(p - buf);
     return SID_OK;
 }
+
+// --only on the host path: the codes whose label is not selected get the
+// "no record" bit, which sid_format_csv skips (the selection of a context's
+// device formatters, for records formatted on the host)
+extern "C" int sid_select_mark(uint8_t* code, size_t n, int select)
+{
+    if (select != SID_SELECT_ALL && select != SID_SELECT_HET && select != SID_SELECT_HOM) return SID_EINVAL;
+    if (n && !code) return SID_EINVAL;
+    if (select == SID_SELECT_ALL) return SID_OK;
+    const uint8_t want = select == SID_SELECT_HET ? SID_CODE_HET : 0;
+    for (size_t i = 0; i < n; ++i)
+        if ((code[i] & SID_CODE_HET) != want) code[i] |= SID_CODE_DROPPED;
+    return SID_OK;
+}

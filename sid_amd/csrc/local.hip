@@ -260,6 +260,20 @@ __global__ __launch_bounds__(256) void sid_local_str_build(const double* __restr
     len[i] = (uint8_t)n;
 }
 
+// The filtered twin of a tail-length table for a selection by label
+// (sid_opts.select): a class of another label gets length 0 (a real tail is
+// never empty), an untabulated one keeps 0xFF.
+__global__ __launch_bounds__(256) void sid_local_len_filter(const char* __restrict__ str,
+                                                           const uint8_t* __restrict__ len, uint32_t N, uint32_t want_het,
+                                                           uint8_t* __restrict__ lenf)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const uint8_t L = len[i];
+    const uint32_t het = (uint8_t)str[(size_t)i * SID_STR_BYTES + 1] & 1u;
+    lenf[i] = L == 0xFF || het == want_het ? L : (uint8_t)0;
+}
+
 // ------------------------------------------------------------- launcher --
 // Called by the C ABI (capi.cpp).  counts must be at least 8-byte aligned
 // (profile_t is 8 bytes).  Non-general option sets: table kernel (x4 when the
@@ -277,10 +291,15 @@ extern "C" hipError_t sid_launch_local_table_build(const sid_local_k* K, const d
 }
 
 extern "C" hipError_t sid_launch_local_str_build(const sid_local_k* K, const double* d_table, const double* d_table2,
-                                                 const sid_local_ws* ws, hipStream_t stream)
+                                                 const sid_local_ws* ws, int select, hipStream_t stream)
 {
     sid_local_str_build<<<SID_TAB_N / 256, 256, 0, stream>>>(d_table, SID_TAB_N, K->sig, ws->str1, ws->len1);
     sid_local_str_build<<<SID_TAB2_N / 256, 256, 0, stream>>>(d_table2, SID_TAB2_N, K->sig, ws->str2, ws->len2);
+    if (ws->len1f && ws->len2f) {   // a selection by label (select: SID_SELECT_HET or _HOM)
+        const uint32_t want = select == SID_SELECT_HET;
+        sid_local_len_filter<<<SID_TAB_N / 256, 256, 0, stream>>>(ws->str1, ws->len1, SID_TAB_N, want, ws->len1f);
+        sid_local_len_filter<<<SID_TAB2_N / 256, 256, 0, stream>>>(ws->str2, ws->len2, SID_TAB2_N, want, ws->len2f);
+    }
     return hipGetLastError();
 }
 

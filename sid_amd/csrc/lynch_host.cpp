@@ -1133,7 +1133,7 @@ extern "C" int sid_lynch_prepare_given(sid_ctx* c, int verbose, const sid_estima
     if (!L->d_strbad) HIPCHECK(hipMalloc(&L->d_strbad, 4));
     HIPCHECK(hipMemsetAsync(L->d_strbad, 0, 4, 0));
     HIPCHECK(sid_launch_lynch_str_build(L->d_pcode, L->d_cc, (uint32_t)U, mode == 1 ? "probability" : "p_value",
-                                        L->d_dense_cidx, L->d_lstr, L->d_dlen, L->d_strbad, 0));
+                                        L->d_dense_cidx, L->d_lstr, L->d_dlen, L->d_strbad, c->opts.select, 0));
     uint32_t strbad = 0;
     HIPCHECK(hipMemcpyAsync(&strbad, L->d_strbad, 4, hipMemcpyDeviceToHost, 0));
     HIPCHECK(hipStreamSynchronize(0));

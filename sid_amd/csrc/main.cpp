@@ -10,7 +10,15 @@
 //
 // Extra long options (no short letter, so they cannot collide with the
 // reference's flags): --devices N, --threads N, --stats, --host-parse,
-// --chunk-bytes N, --hold-bytes N, --retain-bytes N, --host-hold N.
+// --chunk-bytes N, --hold-bytes N, --retain-bytes N, --host-hold N,
+// --only het|hom|all.
+//
+// --only het (or hom) writes the header and only the records with that label
+// -- the reference pipeline's `zgrep ,het,` step, done before the records are
+// formatted (sid_opts.select); everything else, stderr included, is as
+// without it.  Any other value: "sid: --only: expected het, hom or all" on
+// stderr, exit status 1, nothing on stdout.  Not listed by -h, whose text
+// stays the reference's.
 //
 // --host-parse keeps the round-1 path instead: the whole input parsed on the
 // host (sid_parse_text), counts to the devices, records formatted on the host
@@ -223,6 +231,7 @@ int main(int argc, char** argv)
                                          {"hold-bytes", required_argument, nullptr, 6},
                                          {"retain-bytes", required_argument, nullptr, 7},
                                          {"host-hold", required_argument, nullptr, 8},
+                                         {"only", required_argument, nullptr, 9},
                                          {nullptr, 0, nullptr, 0}};
     int flag;
     while ((flag = getopt_long(argc, argv, "E:Rhm:p:r:", LONG, nullptr)) != -1) {
@@ -248,6 +257,16 @@ int main(int argc, char** argv)
         case 6: opt.hold_bytes = std::strtoull(optarg, nullptr, 10); break;
         case 7: opt.retain_bytes = std::strtoull(optarg, nullptr, 10); break;
         case 8: opt.host_hold = std::strtoull(optarg, nullptr, 10); break;
+        case 9:
+            if (std::strcmp(optarg, "het") == 0) opt.o.select = SID_SELECT_HET;
+            else if (std::strcmp(optarg, "hom") == 0) opt.o.select = SID_SELECT_HOM;
+            else if (std::strcmp(optarg, "all") == 0) opt.o.select = SID_SELECT_ALL;
+            else {
+                std::fflush(stdout);
+                std::fputs("sid: --only: expected het, hom or all\n", stderr);
+                std::exit(EXIT_FAILURE);
+            }
+            break;
         default: std::exit(EXIT_FAILURE);
         }
     }
@@ -570,6 +589,7 @@ int main(int argc, char** argv)
             }
             HCHECK(hipStreamSynchronize(s.stream), "D2H");
         });
+        CHECK(sid_select_mark(h_code, n, opt.o.select), "select");   // --only: the other labels' sites get no record
         const size_t BLOCK = 1u << 18;
         const size_t nblocks = (n + BLOCK - 1) / BLOCK;
         std::vector<std::vector<char>> bufs(nblocks);

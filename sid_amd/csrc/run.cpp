@@ -870,6 +870,7 @@ extern "C" int sid_engine_create(const sid_opts* opts, const sid_engine_cfg* cfg
 {
     if (!out) return SID_EINVAL;
     *out = nullptr;
+    if (opts && (opts->select < SID_SELECT_ALL || opts->select > SID_SELECT_HOM)) return SID_EINVAL;
     int nvis = 0;
     if (hipGetDeviceCount(&nvis) != hipSuccess || nvis <= 0) return SID_EHIP;
     sid_engine* e = new sid_engine();
@@ -912,6 +913,7 @@ extern "C" int sid_engine_create(const sid_opts* opts, const sid_engine_cfg* cfg
             }
         });
         int rc = sid_create(d->device, &e->opts, &d->ctx);
+        d->ws.select = e->opts.select;   // (the formatters that take no context: sid_chunk_fmt_len / _put)
         qs.join();
         if (rc == SID_OK && x != hipSuccess) rc = sid_set_hip_error(x);
         rcs[i] = rc;

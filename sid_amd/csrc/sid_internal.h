@@ -34,6 +34,11 @@ struct sid_local_ws {
     uint8_t* len1 = nullptr;
     char* str2 = nullptr;
     uint8_t* len2 = nullptr;
+    // with a selection (sid_opts.select): the twins of len1 / len2 in which a
+    // class of another label has length 0 (a real tail is never empty), read
+    // by the selecting parse; null without a selection
+    uint8_t* len1f = nullptr;
+    uint8_t* len2f = nullptr;
 };
 #define SID_STR_BYTES 32   // entry: [0] tail length, [1] het, [8..32) the tail, zero-padded
 #define SID_STR_TEXT 8
@@ -50,7 +55,7 @@ extern "C" hipError_t sid_launch_local(const uint16_t* counts, size_t n, uint8_t
 extern "C" hipError_t sid_launch_local_table_build(const sid_local_k* K, const double* d_lnt,
                                                    double* d_table, double* d_table2, hipStream_t stream);
 extern "C" hipError_t sid_launch_local_str_build(const sid_local_k* K, const double* d_table, const double* d_table2,
-                                                 const sid_local_ws* ws, hipStream_t stream);
+                                                 const sid_local_ws* ws, int select, hipStream_t stream);
 extern "C" hipError_t sid_launch_synth(uint64_t seed, uint64_t first, size_t n,
                                        const uint64_t* d_cdf, uint32_t kmax, uint16_t* counts,
                                        hipStream_t stream);
@@ -66,7 +71,8 @@ void sid_lynch_dev_destroy(sid_lynch_dev* L);
 // (ckeys / cidx / cmask / special_idx); none = the profile was filtered (no
 // record).  Per class SID_LSTR_BYTES of record tail: [0] its length, from
 // [8] "label,gt,conf1,conf2,conf_type\n"; dlen[d] = the tail length of
-// dense code d's class (0: none).
+// dense code d's class (0: none).  A class whose label the context's
+// selection (sid_opts.select) leaves out has length 0: no record either.
 #define SID_LSTR_BYTES 64
 struct sid_lynch_fmt {
     const uint32_t* dense_cidx;
@@ -82,7 +88,7 @@ int sid_lynch_fmt_view(const sid_ctx* c, sid_lynch_fmt* v);
 // textpath.hip: the tails of the U classes and the dense codes' lengths
 hipError_t sid_launch_lynch_str_build(const uint8_t* pcode, const double* cc, uint32_t U, const char* conf_type,
                                       const uint32_t* dense_cidx, char* lstr, uint8_t* dlen, uint32_t* bad,
-                                      hipStream_t st);
+                                      int select, hipStream_t st);
 
 #define SID_STAGE_N 8                   // reader threads / pinned input buffers
 #define SID_STAGE_BYTES (16u << 20)     // bytes per input buffer
@@ -171,6 +177,8 @@ struct sid_chunk_ws {
     uint64_t slots = 0;           // of slot_cap per tile, `slots` of them (sid_chunk_tile_local)
     bool tile_quad = false;       // the tile parse's shape (the compaction; the -m local writer: wave entries or not)
     uint64_t tile_ntp = 0;
+    int select = 0;               // the owner's sid_opts.select, for the formatters that take no context
+                                  // (sid_chunk_fmt_len / _put); set once by the owner
 };
 int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites);
 void sid_chunk_release(sid_chunk_ws* W);

@@ -1322,6 +1322,16 @@ __device__ __forceinline__ Head site_head(Reader& R, const Off* startp, const ui
     return site_head_hw(R, startp, hdr ? *(const ulonglong2*)hdr : make_ulonglong2(0, 0));
 }
 
+// The selection by label (sid_opts.select, --only): a site has no record when
+// its code has bit 6 set (a filtered profile) or its label is not the
+// selected one -- ((c ^ x) & m) != 0 with x in bits 0-7 and m in bits 8-15 of
+// the word sel_word makes (no selection: x = 0, m = 0x40, the bit 6 test alone)
+static uint32_t sel_word(int select)
+{
+    return select == SID_SELECT_HET ? 0xC080u : select == SID_SELECT_HOM ? 0xC000u : 0x4000u;
+}
+__device__ __forceinline__ bool code_out(uint32_t c, uint32_t xm) { return ((c ^ xm) & (xm >> 8) & 0xFFu) != 0; }
+
 // record length of a site (call.hpp:29-38): 0 for a filtered profile (no
 // record, call.cpp:131-140), -1 for a confidence outside the formatter's range
 __device__ __forceinline__ int record_len(const Head& h, uint8_t c, const sid_g6& gh, const sid_g6& gt, int tlen)
@@ -1379,7 +1389,8 @@ __global__ __launch_bounds__(TB) void sid_fmt_len_kernel(const char* __restrict_
                                                          uint64_t s1, const uint8_t* __restrict__ code,
                                                          const double* __restrict__ hom,
                                                          const double* __restrict__ het, CType ct,
-                                                         uint32_t* __restrict__ bsum, int* __restrict__ bad)
+                                                         uint32_t* __restrict__ bsum, int* __restrict__ bad,
+                                                         uint32_t xm)
 {
     __shared__ double p10[SID_P10_N];
     load_p10(p10);
@@ -1387,7 +1398,7 @@ __global__ __launch_bounds__(TB) void sid_fmt_len_kernel(const char* __restrict_
     int l = 0;
     if (i < s1) {
         const uint8_t c = code[i];
-        if (!(c & 0x40)) {
+        if (!code_out(c, xm)) {
             Reader R{text, len};
             const Head h = site_head(R, starts + i, hdr ? hdr + 2 * i : nullptr);
             l = record_len(h, c, sid_g6_prep(hom[i], p10), sid_g6_prep(het[i], p10), ct.len);
@@ -1411,7 +1422,7 @@ __global__ __launch_bounds__(TB) void sid_fmt_write_kernel(const char* __restric
                                                            const double* __restrict__ hom,
                                                            const double* __restrict__ het, CType ct,
                                                            const uint64_t* __restrict__ boff, uint64_t out0,
-                                                           char* __restrict__ out)
+                                                           char* __restrict__ out, uint32_t xm)
 {
     __shared__ __attribute__((aligned(16))) char buf[FMT_LDS + 32];
     __shared__ double p10[SID_P10_N];
@@ -1424,7 +1435,7 @@ __global__ __launch_bounds__(TB) void sid_fmt_write_kernel(const char* __restric
     sid_g6 gh{}, gt{};
     if (i < s1) {
         c = code[i];
-        if (!(c & 0x40)) {
+        if (!code_out(c, xm)) {
             h = site_head(R, starts + i, hdr ? hdr + 2 * i : nullptr);
             gh = sid_g6_prep(hom[i], p10);
             gt = sid_g6_prep(het[i], p10);
@@ -1541,7 +1552,8 @@ __global__ __launch_bounds__(FTB) void sid_fmt_blen_kernel(const char* __restric
                                                           const uint8_t* __restrict__ code,
                                                           const double* __restrict__ hom,
                                                           const double* __restrict__ het, CType ct,
-                                                          uint32_t* __restrict__ bsum, unsigned long long* lb)
+                                                          uint32_t* __restrict__ bsum, unsigned long long* lb,
+                                                          uint32_t xm)
 {
     __shared__ double p10[SID_P10_N];
     load_p10(p10);
@@ -1549,7 +1561,7 @@ __global__ __launch_bounds__(FTB) void sid_fmt_blen_kernel(const char* __restric
     int l = 0;
     if (i < n) {
         const uint8_t c = code[i];
-        if (!(c & 0x40)) {
+        if (!code_out(c, xm)) {
             Reader R{text, len};
             const Head h = site_head(R, starts + i, hdr + 2 * i);
             l = record_len(h, c, sid_g6_prep(hom[i], p10), sid_g6_prep(het[i], p10), ct.len);
@@ -1570,7 +1582,7 @@ __global__ __launch_bounds__(FTB) void sid_fmt_put_kernel(const char* __restrict
                                                          const double* __restrict__ hom,
                                                          const double* __restrict__ het, CType ct,
                                                          const uint64_t* __restrict__ boff, const uint64_t* state,
-                                                         unsigned long long* lb, char* __restrict__ out)
+                                                         unsigned long long* lb, char* __restrict__ out, uint32_t xm)
 {
     __shared__ __attribute__((aligned(16))) char buf[FMT_LDS2 + 32];
     __shared__ double p10[SID_P10_N];
@@ -1583,7 +1595,7 @@ __global__ __launch_bounds__(FTB) void sid_fmt_put_kernel(const char* __restrict
     sid_g6 gh{}, gt{};
     if (i < n) {
         c = code[i];
-        if (!(c & 0x40)) {
+        if (!code_out(c, xm)) {
             h = site_head(R, starts + i, hdr + 2 * i);
             gh = sid_g6_prep(hom[i], p10);
             gt = sid_g6_prep(het[i], p10);
@@ -1659,7 +1671,12 @@ __device__ __forceinline__ uint32_t local_word(uint32_t k, uint32_t f, uint32_t 
 // instead of 20 B, each way).  No compact word is SID_CLS_MISS: k < 0xFFFFF.
 constexpr uint32_t SID_CLS_COMPACT = 1u << 27;
 constexpr uint32_t SID_CLS_DPOS = 128;   // offsets 0 .. 127
-static_assert(SID_TAB_N + SID_TAB2_N < 0xFFFFFu, "a compact word never equals SID_CLS_MISS");
+// SID_CLS_SKIP, the second reserved value: a tabulated site whose label the
+// selection (sid_opts.select) leaves out -- no record, and nothing else of the
+// slot is read.  Stored only by the selecting parse (SEL), for the selecting
+// writers, which test for it before cls_compact.
+constexpr uint32_t SID_CLS_SKIP = 0xFFFFFFFEu;
+static_assert(SID_TAB_N + SID_TAB2_N < 0xFFFFEu, "a compact word never equals SID_CLS_MISS or SID_CLS_SKIP");
 __device__ __forceinline__ bool cls_compact(uint32_t w) { return (w & SID_CLS_COMPACT) && w != SID_CLS_MISS; }
 
 // The site's record length (0: a fix-up site, listed in LL.miss; a record
@@ -1671,41 +1688,50 @@ __device__ __forceinline__ bool cls_compact(uint32_t w) { return (w & SID_CLS_CO
 // quad_head: 11.19 with it, 11.03 without; for the lane shape, 2 KiB of the
 // ~30x profiles: C2 parse 1.79 -> 1.92 ms.)
 // the class word and tail length alone (-1 and SID_CLS_MISS: a fix-up site)
+// SEL (a selection by label: LL's tables are the filtered twins, in which a
+// class of another label has length 0): -2 and SID_CLS_SKIP for such a class
+template <bool SEL = false>
 __device__ __forceinline__ int local_site_word(uint64_t c, const uint8_t* L1, const LocalLen& LL, uint32_t* w)
 {
     uint32_t f, s, nf, ns, cov;
     sid_major(c, f, s, nf, ns, cov);
     const uint32_t k = local_entry(nf, ns, cov - nf - ns);
     const uint32_t L = k < SID_TAB_N ? L1[k] : k != UINT32_MAX ? LL.len2[k - SID_TAB_N] : 0xFFu;
+    if (SEL && L == 0) {
+        *w = SID_CLS_SKIP;
+        return -2;
+    }
     *w = L == 0xFFu ? SID_CLS_MISS : local_word(k, f, s);
     return L == 0xFFu ? -1 : (int)L;
 }
-template <bool LIST = true>   // LIST: a fix-up site listed in LL.miss (else the caller fixes it up)
+template <bool LIST = true, bool SEL = false>   // LIST: a fix-up site listed in LL.miss (else the caller fixes it up)
 __device__ __forceinline__ int local_site_tail(uint64_t c, uint64_t i, const uint8_t* L1, const LocalLen& LL)
 {
     uint32_t w;
-    const int L = local_site_word(c, L1, LL, &w);
-    const bool miss = L < 0;
+    const int L = local_site_word<SEL>(c, L1, LL, &w);
+    const bool miss = SEL ? L == -1 : L < 0;
     LL.cls[i] = w;   // (read back by the writer soon: through the caches)
     if (miss) {
         if (LIST) LL.miss[atomicAdd(LL.nmiss, 1ull)] = (uint32_t)i;   // its bytes: the fix-up's
         return -1;
     }
-    return (int)L;
+    return (int)L;   // (SEL: -2 for a class the selection leaves out)
 }
+template <bool SEL = false>
 __device__ __forceinline__ int local_site_len(const Head& h, uint64_t c, uint64_t i, const uint8_t* L1,
                                               const LocalLen& LL)
 {
-    const int L = local_site_tail(c, i, L1, LL);
+    const int L = local_site_tail<true, SEL>(c, i, L1, LL);
     return L < 0 ? 0 : local_rec_len(h, (uint32_t)L);
 }
 
 // (out of line: its tokeniser would set the parse's register count)
+template <bool SEL = false>
 __device__ __noinline__ int local_site_len_text(const char* text, uint64_t len, uint64_t s0, uint64_t c, uint64_t i,
                                                 LocalLen LL)
 {
     Reader R{text, len};
-    return local_site_len(site_head(R, &s0, nullptr), c, i, LL.len1, LL);
+    return local_site_len<SEL>(site_head(R, &s0, nullptr), c, i, LL.len1, LL);
 }
 
 // The parse with the -m local call's record lengths fused in (the length
@@ -1716,6 +1742,8 @@ __device__ __noinline__ int local_site_len_text(const char* text, uint64_t len, 
 // general routine (sid_local_len_list_kernel).  The tail-length table is read
 // through the caches (an LDS copy would cost the parse a block per CU).
 // (the two-pass fallback's parse since the tile parse: 7 waves a SIMD)
+// SEL: a selection by label (LL's tables the filtered twins; local_site_word)
+template <bool SEL>
 __global__ __launch_bounds__(TB) void sid_parse_len_kernel(const char* __restrict__ text, uint64_t len,
                                                            const sid_off_t* __restrict__ starts,
                                                            const uint64_t* __restrict__ range,
@@ -1751,9 +1779,9 @@ __global__ __launch_bounds__(TB) void sid_parse_len_kernel(const char* __restric
                     Head hd;
                     hd.clen = (uint32_t)(h[0] >> 32) & 0xFFFu;
                     hd.pos = (int32_t)(uint32_t)h[0];
-                    l = local_site_len(hd, c, i - lo, LL.len1, LL);
+                    l = local_site_len<SEL>(hd, c, i - lo, LL.len1, LL);
                 } else {   // position not a plain 1-9 digit run: the formatter's tokeniser
-                    l = local_site_len_text(text, len, s0, c, i - lo, LL);
+                    l = local_site_len_text<SEL>(text, len, s0, c, i - lo, LL);
                 }
                 if (l == 0) counts[i] = c;   // a fix-up site: the fix-up reads its counts (the writer, the class word)
             } else {
@@ -1766,6 +1794,7 @@ __global__ __launch_bounds__(TB) void sid_parse_len_kernel(const char* __restric
 }
 
 // the record lengths of listed sites (the lines the general routine parsed)
+template <bool SEL>
 __global__ __launch_bounds__(TB) void sid_local_len_list_kernel(const char* __restrict__ text, uint64_t len,
                                                                const sid_off_t* __restrict__ starts,
                                                                const uint64_t* __restrict__ hdr,
@@ -1777,7 +1806,7 @@ __global__ __launch_bounds__(TB) void sid_local_len_list_kernel(const char* __re
     for (uint64_t j = (uint64_t)blockIdx.x * TB + threadIdx.x; j < m; j += (uint64_t)gridDim.x * TB) {
         const uint32_t i = list[j];
         Reader R{text, len};
-        const int l = local_site_len(site_head(R, starts + i, hdr + 2 * i), counts[i], i, LL.len1, LL);
+        const int l = local_site_len<SEL>(site_head(R, starts + i, hdr + 2 * i), counts[i], i, LL.len1, LL);
         if (l) atomicAdd(LL.bsum + i / FTB, (uint32_t)l);
     }
 }
@@ -1869,7 +1898,7 @@ struct LaneSlot {
     uint32_t pl = 0;           // the position's digits
     bool elig = false;         // the words are the wave's to store
 };
-template <bool LOCAL, class Ld>
+template <bool LOCAL, bool SEL, class Ld>
 __device__ __forceinline__ int tile_line(const char* __restrict__ text, const char* tl, Ld ld, uint64_t g0, uint32_t r0,
                                          uint64_t g, uint32_t len_t, uint64_t c1, const uint8_t* cls,
                                          const uint32_t* rbl, const TileOut& O, const LocalLen& LL, LaneSlot& ws)
@@ -1897,7 +1926,11 @@ __device__ __forceinline__ int tile_line(const char* __restrict__ text, const ch
         hd.pos = (int32_t)(uint32_t)h[0];
         if (LOCAL && hv && clen <= 8) {
             uint32_t w;
-            const int L = local_site_word(c, LL.len1, LL, &w);
+            const int L = local_site_word<SEL>(c, LL.len1, LL, &w);
+            if (SEL && L == -2) {   // a class the selection leaves out: the skip word, no bytes, no header pair
+                LL.cls[g] = w;
+                return 0;
+            }
             if (L >= 0) {   // (a fix-up site: stored here, below)
                 ws.h0 = h[0];
                 ws.h1 = h[1];
@@ -1912,9 +1945,9 @@ __device__ __forceinline__ int tile_line(const char* __restrict__ text, const ch
         if (!LOCAL) {
             ST_MID(O.counts + g, c);
         } else if (hv) {
-            l = local_site_len(hd, c, g, LL.len1, LL);
+            l = local_site_len<SEL>(hd, c, g, LL.len1, LL);
         } else {   // position not a plain 1-9 digit run: the formatter's tokeniser
-            l = local_site_len_text(text, c1, s0, c, g, LL);
+            l = local_site_len_text<SEL>(text, c1, s0, c, g, LL);
         }
         if (LOCAL && l == 0) O.counts[g] = c;   // a fix-up site: the fix-up reads its counts
     } else {
@@ -2036,16 +2069,17 @@ __device__ __forceinline__ void quad_bases(const char* tl, Ld ld, uint64_t g0, u
 // -m local's call of a counted quad-shape line, a lane per line as the
 // header: the class word, the record's length (returned; 0 for a fix-up site
 // or a line not counted here)
+template <bool SEL>
 __device__ __forceinline__ int quad_tail(const char* __restrict__ text, uint64_t s0, uint32_t mt, uint64_t c, uint64_t g,
                                          uint64_t c1, const TileOut& O, const LocalLen& LL)
 {
     if (!(mt >> 31)) return 0;
     int l;
     if ((mt >> 10) & 1u) {
-        const int L = local_site_tail(c, g, LL.len1, LL);
+        const int L = local_site_tail<true, SEL>(c, g, LL.len1, LL);
         l = L < 0 ? 0 : (int)((mt >> 11) & 0x1FFFu) + L;
     } else {   // position not a plain 1-9 digit run: the formatter's tokeniser
-        l = local_site_len_text(text, c1, s0, c, g, LL);
+        l = local_site_len_text<SEL>(text, c1, s0, c, g, LL);
     }
     if (l == 0) O.counts[g] = c;   // a fix-up site: the fix-up reads its counts
     return l;
@@ -2069,7 +2103,10 @@ __device__ uint32_t put_stamp[TP_STAMP_N][4];
 #define TP_STAMP_AT(v)
 #define PUT_STAMP_AT(v)
 #endif
-template <bool QUAD, bool LOCAL>
+// SEL (LOCAL only): a selection by label -- LL's tail-length tables are the
+// filtered twins, a class of another label stores SID_CLS_SKIP and adds no
+// bytes (local_site_word); the instantiations without it are unchanged.
+template <bool QUAD, bool LOCAL, bool SEL = false>
 __global__ __launch_bounds__(TB) void sid_tile_parse_kernel(const char* __restrict__ text, uint64_t tile_base,
                                                             uint64_t c0, uint64_t c1, TileOut O, LocalLen LL)
 {
@@ -2298,7 +2335,7 @@ __global__ __launch_bounds__(TB) void sid_tile_parse_kernel(const char* __restri
                 __syncthreads();
                 __builtin_amdgcn_s_setprio(2);
                 int l = 0;
-                if (tid < cnt) l = quad_tail(text, g0 + ls[tid], qmeta[tid], qcnt[tid], g_tile + tid, c1, O, LL);
+                if (tid < cnt) l = quad_tail<SEL>(text, g0 + ls[tid], qmeta[tid], qcnt[tid], g_tile + tid, c1, O, LL);
                 bsum_add(tid & ~63u, tid, l);
             }
         } else {
@@ -2306,7 +2343,8 @@ __global__ __launch_bounds__(TB) void sid_tile_parse_kernel(const char* __restri
                 const uint32_t j = j0 + tid;
                 int l = 0;
                 LaneSlot ws;
-                if (j < cnt) l = tile_line<LOCAL>(text, tl, ld, g0, ls[j], g_tile + j, len_t, c1, cls, rbl, O, LL, ws);
+                if (j < cnt)
+                    l = tile_line<LOCAL, SEL>(text, tl, ld, g0, ls[j], g_tile + j, len_t, c1, cls, rbl, O, LL, ws);
                 if constexpr (LOCAL) {
                     tile_wave_store(ws, g_tile + j, O.twv + t * O.nwv + ((j0 + (tid & ~63u)) >> 6), O, LL);
                     bsum_add(j0 + (tid & ~63u), j, l);
@@ -2340,6 +2378,7 @@ struct LocalFix {
     uint8_t* code;
     double* hom;
     double* het;
+    uint32_t xm;   // the selection by label (sel_word): a fix-up site of another label has no record
 };
 __device__ __forceinline__ void fix_site(uint64_t i, const Head& hd, uint64_t c, const LocalFix& F,
                                          unsigned long long* lb)
@@ -2349,6 +2388,7 @@ __device__ __forceinline__ void fix_site(uint64_t i, const Head& hd, uint64_t c,
     F.code[i] = (uint8_t)code;
     F.hom[i] = h;
     F.het[i] = t;
+    if (code_out(code, F.xm)) return;   // (the writers test the code again)
     int l = record_len(hd, (uint8_t)code, sid_g6_prep(h), sid_g6_prep(t), F.ct.len);
     if (l < 0) {
         atomicExch(lb + 2, 1ull);
@@ -2365,7 +2405,7 @@ __device__ __forceinline__ void fix_site(uint64_t i, const Head& hd, uint64_t c,
 // record length, a fix-up where no class table covers it, and the fix-ups
 // the tile parse listed (LL.miss) -- the work of two more launches a chunk
 // (a record-length kernel over the leftovers, then the fix-up kernel)
-template <bool LOCAL>
+template <bool LOCAL, bool SEL = false>
 __global__ __launch_bounds__(TB) void sid_tile_serial_kernel(const char* __restrict__ text, uint64_t len,
                                                              const uint32_t* __restrict__ fb,
                                                              const uint32_t* __restrict__ fbo,
@@ -2426,9 +2466,9 @@ __global__ __launch_bounds__(TB) void sid_tile_serial_kernel(const char* __restr
         if constexpr (LOCAL) {
             Reader R{text, len};
             const Head hd = slot_head(R, make_ulonglong2(0, s0));
-            const int L = local_site_tail<false>(c, g, F.LL.len1, F.LL);
+            const int L = local_site_tail<false, SEL>(c, g, F.LL.len1, F.LL);
             if (L >= 0) atomicAdd(F.LL.bsum + g / FTB, (uint32_t)local_rec_len(hd, (uint32_t)L));
-            else fix_site(g, hd, c, F, lb);
+            else if (L == -1) fix_site(g, hd, c, F, lb);
         }
     }
     if constexpr (LOCAL) {   // the tile parse's fix-up sites
@@ -2516,7 +2556,7 @@ __global__ __launch_bounds__(FTB) void sid_local_len_kernel(const char* __restri
             const uint32_t L = k < SID_TAB_N ? L1[k] : k != UINT32_MAX ? len2[k - SID_TAB_N] : 0xFFu;
             if (L == 0xFFu) {
                 miss[atomicAdd(nmiss, 1ull)] = (uint32_t)i;   // its bytes: the fix-up's
-            } else {
+            } else if (L) {   // (0: the filtered tables of a selection, a class of another label)
                 Reader R{text, len};
                 l = local_rec_len(site_head_hw(R, starts + i, hw), L);
             }
@@ -2537,7 +2577,7 @@ __global__ __launch_bounds__(TB) void sid_local_fixlen_kernel(const char* __rest
                                                              const double* __restrict__ lnt, CType ct,
                                                              uint8_t* __restrict__ code, double* __restrict__ hom,
                                                              double* __restrict__ het, uint32_t* bsum,
-                                                             unsigned long long* lb)
+                                                             unsigned long long* lb, uint32_t xm)
 {
     const uint64_t m = *nmiss;
     for (uint64_t j = (uint64_t)blockIdx.x * TB + threadIdx.x; j < m; j += (uint64_t)gridDim.x * TB) {
@@ -2547,6 +2587,7 @@ __global__ __launch_bounds__(TB) void sid_local_fixlen_kernel(const char* __rest
         code[i] = (uint8_t)c;
         hom[i] = h;
         het[i] = t;
+        if (code_out(c, xm)) continue;   // a label the selection leaves out: no record (the writer tests the code too)
         Reader R{text, len};
         const Head hd = SLOT ? slot_head(R, *(const ulonglong2*)(hdr + 2 * (uint64_t)i))
                              : site_head(R, starts + i, hdr + 2 * i);
@@ -2705,6 +2746,10 @@ __device__ void record_tail_bytes(Reader& R, const Head& h, uint8_t c, uint4 ea,
         if ((uint32_t)j < L) put(n + j, (w[j >> 2] >> (8 * (j & 3))) & 0xFFu);
 }
 
+// (TAG: the selecting kernels call copies of their own, TAG 1 -- these
+// functions have internal linkage, so the compiler shapes each to the whole
+// set of its callers, and the kernels without a selection keep theirs, TAG 0)
+template <int TAG = 0>
 __device__ __noinline__ void record_put_tail(const char* text, uint64_t len, Head h, uint8_t c, uint4 ea, uint4 eb,
                                              char* out)
 {
@@ -2712,6 +2757,7 @@ __device__ __noinline__ void record_put_tail(const char* text, uint64_t len, Hea
     record_tail_bytes(R, h, c, ea, eb, [&](uint32_t k, uint32_t ch) { out[k] = (char)ch; });
 }
 
+template <int TAG = 0>
 __device__ __noinline__ void record_or_tail(const char* text, uint64_t len, Head h, uint8_t c, uint4 ea, uint4 eb,
                                             unsigned long long* B, uint32_t q)
 {
@@ -2721,12 +2767,14 @@ __device__ __noinline__ void record_or_tail(const char* text, uint64_t len, Head
 
 // the fix-up's sites (rare), out of line so that their %g code does not set
 // the writer's register count: the record length, and the record
+template <int TAG = 0>
 __device__ __noinline__ int miss_len(Head h, uint8_t c, double hm, double ht, CType ct)
 {
     const int l = record_len(h, c, sid_g6_prep(hm), sid_g6_prep(ht), ct.len);
     return l < 0 ? 0 : l;
 }
 
+template <int TAG = 0>
 __device__ __noinline__ void miss_or(const char* text, uint64_t len, Head h, uint8_t c, double hm, double ht,
                                      CType ct, unsigned long long* B, uint32_t q)
 {
@@ -2734,6 +2782,7 @@ __device__ __noinline__ void miss_or(const char* text, uint64_t len, Head h, uin
     record_or(R, h, c, sid_g6_prep(hm), sid_g6_prep(ht), ct, B, q);
 }
 
+template <int TAG = 0>
 __device__ __noinline__ void miss_put(const char* text, uint64_t len, Head h, uint8_t c, double hm, double ht,
                                       CType ct, char* out)
 {
@@ -2747,8 +2796,13 @@ __device__ __noinline__ void miss_put(const char* text, uint64_t len, Head h, ui
 // tile's count, chrom and position by slot_head
 // WV: the slots' compact words and wave entries (the lane-shape tile parse,
 // tile_wave_store); else every slot's header pair
-template <bool CLS, bool WV = false>
-__global__ __launch_bounds__(FTB, SID_PUT_WAVES) void sid_local_put_kernel(const char* __restrict__ text, uint64_t len,
+// SEL (sid_local_put_sel_kernel): a selection by label (xm: sel_word) -- a
+// SID_CLS_SKIP word, a class of another label or a fix-up site of another
+// label has no record (as the length kernels counted)
+// (the body shared by the two kernels below: the one without a selection keeps
+// its parameters and its code)
+template <bool CLS, bool WV, bool SEL>
+__device__ __forceinline__ void local_put_body(const char* __restrict__ text, uint64_t len,
                                                            const sid_off_t* __restrict__ starts,
                                                            const uint64_t* __restrict__ hdr, uint64_t n,
                                                            const uint32_t* __restrict__ tcnt, uint32_t cap,
@@ -2761,7 +2815,7 @@ __global__ __launch_bounds__(FTB, SID_PUT_WAVES) void sid_local_put_kernel(const
                                                            const double* __restrict__ hom,
                                                            const double* __restrict__ het, CType ct,
                                                            const uint64_t* __restrict__ boff, const uint64_t* state,
-                                                           unsigned long long* lb, char* __restrict__ out)
+                                                           unsigned long long* lb, char* __restrict__ out, uint32_t xm)
 {
     constexpr int NQ = (FMT_LDS2 + 64) / 16;   // records, slack
     PUT_STAMP_AT(ps0);
@@ -2799,9 +2853,11 @@ __global__ __launch_bounds__(FTB, SID_PUT_WAVES) void sid_local_put_kernel(const
         const uint32_t j = (uint32_t)i - __umul24(t, cap);
         if (WV) te = twv[__umul24(t, nwv) + (j >> 6)];
         site = j < tcnt[t];
+        if (SEL && CLS) site = site && w0 != SID_CLS_SKIP;
         cw = WV && cls_compact(w0);
         if (WV && site && !cw) hw0 = *(const ulonglong2*)(hdr + 2 * i);
     }
+    if (SEL && CLS && !tcnt && site) site = cwords[i] != SID_CLS_SKIP;
     if (site) {
         uint32_t k;
         if (CLS) {
@@ -2840,9 +2896,10 @@ __global__ __launch_bounds__(FTB, SID_PUT_WAVES) void sid_local_put_kernel(const
             const bool het_l = (ea.x >> 8) & 1u;
             c = (uint8_t)(f | ((het_l ? s : f) << 2) | (het_l ? 0x80u : 0u));
             l = (int)h.clen + pl + 9 + (int)(ea.x & 0xFFu);   // (local_rec_len)
+            if (SEL && code_out(c, xm)) l = 0;
         } else {   // the fix-up's site
             c = code[i];
-            l = miss_len(h, c, hom[i], het[i], ct);
+            l = SEL && code_out(c, xm) ? 0 : miss_len<SEL>(h, c, hom[i], het[i], ct);
         }
     }
     PUT_STAMP_AT(ps1);
@@ -2853,8 +2910,8 @@ __global__ __launch_bounds__(FTB, SID_PUT_WAVES) void sid_local_put_kernel(const
     PUT_STAMP_AT(ps2);
     char* const dst = out + boff[blockIdx.x];
     if (tot > FMT_LDS2) {   // long records (long chromosome names): straight to global, byte by byte
-        if (l && tab) record_put_tail(text, len, h, c, ea, eb, dst + my);
-        else if (l) miss_put(text, len, h, c, hom[i], het[i], ct, dst + my);
+        if (l && tab) record_put_tail<SEL>(text, len, h, c, ea, eb, dst + my);
+        else if (l) miss_put<SEL>(text, len, h, c, hom[i], het[i], ct, dst + my);
         return;
     }
     if (l && tab && (h.c8 || h.clen == 0) && h.pos >= 0) {
@@ -2878,9 +2935,9 @@ __global__ __launch_bounds__(FTB, SID_PUT_WAVES) void sid_local_put_kernel(const
                                 ((uint64_t)eb.w << 32) | eb.z};
         lds_or_run<3>(B, q2 + 7, tv);
     } else if (l && tab) {
-        record_or_tail(text, len, h, c, ea, eb, B, my);
+        record_or_tail<SEL>(text, len, h, c, ea, eb, B, my);
     } else if (l) {
-        miss_or(text, len, h, c, hom[i], het[i], ct, B, my);
+        miss_or<SEL>(text, len, h, c, hom[i], het[i], ct, B, my);
     }
     __syncthreads();
     PUT_STAMP_AT(ps3);
@@ -2894,6 +2951,127 @@ __global__ __launch_bounds__(FTB, SID_PUT_WAVES) void sid_local_put_kernel(const
         put_stamp[blockIdx.x][3] = (uint32_t)(ps4 - ps3);
     }
 #endif
+}
+
+template <bool CLS, bool WV = false>
+__global__ __launch_bounds__(FTB, SID_PUT_WAVES) void sid_local_put_kernel(const char* __restrict__ text, uint64_t len,
+                                                           const sid_off_t* __restrict__ starts,
+                                                           const uint64_t* __restrict__ hdr, uint64_t n,
+                                                           const uint32_t* __restrict__ tcnt, uint32_t cap,
+                                                           SlotDiv cdiv, const ulonglong2* __restrict__ twv,
+                                                           uint32_t nwv, const uint64_t* __restrict__ counts,
+                                                           const uint32_t* __restrict__ cwords,
+                                                           const char* __restrict__ str1,
+                                                           const char* __restrict__ str2,
+                                                           const uint8_t* __restrict__ code,
+                                                           const double* __restrict__ hom,
+                                                           const double* __restrict__ het, CType ct,
+                                                           const uint64_t* __restrict__ boff, const uint64_t* state,
+                                                           unsigned long long* lb, char* __restrict__ out)
+{
+    local_put_body<CLS, WV, false>(text, len, starts, hdr, n, tcnt, cap, cdiv, twv, nwv, counts, cwords, str1, str2, code, hom, het, ct, boff,
+                                   state, lb, out, 0u);
+}
+
+template <bool CLS, bool WV = false>
+__global__ __launch_bounds__(FTB, SID_PUT_WAVES) void sid_local_put_sel_kernel(const char* __restrict__ text, uint64_t len,
+                                                           const sid_off_t* __restrict__ starts,
+                                                           const uint64_t* __restrict__ hdr, uint64_t n,
+                                                           const uint32_t* __restrict__ tcnt, uint32_t cap,
+                                                           SlotDiv cdiv, const ulonglong2* __restrict__ twv,
+                                                           uint32_t nwv, const uint64_t* __restrict__ counts,
+                                                           const uint32_t* __restrict__ cwords,
+                                                           const char* __restrict__ str1,
+                                                           const char* __restrict__ str2,
+                                                           const uint8_t* __restrict__ code,
+                                                           const double* __restrict__ hom,
+                                                           const double* __restrict__ het, CType ct,
+                                                           const uint64_t* __restrict__ boff, const uint64_t* state,
+                                                           unsigned long long* lb, char* __restrict__ out, uint32_t xm)
+{
+    local_put_body<CLS, WV, true>(text, len, starts, hdr, n, tcnt, cap, cdiv, twv, nwv, counts, cwords, str1, str2, code, hom, het, ct, boff,
+                                   state, lb, out, xm);
+}
+
+// The sparse -m local writer over the tile parse's slots, for a selection
+// that keeps few records (--only het).  A block walks SPB 512-slot groups; a
+// group without record bytes (its block sum) costs one load.  In the others
+// every slot loads its class word (4 B, coalesced) and its tile's count; only
+// the slots that hold a site whose word is not SID_CLS_SKIP go on to the wave
+// entry or header pair, the class entry and the record, stored byte by byte
+// at the group's offset + its prefix (no LDS assembly: the records are too
+// few to fill 16-B stores).  The record of a slot is the one
+// sid_local_put_sel_kernel<true, WV> writes.
+constexpr int SPB = 8;   // groups per block of the sparse writers
+template <bool WV>
+__global__ __launch_bounds__(FTB) void sid_local_put_sparse_kernel(const char* __restrict__ text, uint64_t len,
+                                                                  const uint64_t* __restrict__ hdr, uint64_t n,
+                                                                  const uint32_t* __restrict__ tcnt, uint32_t cap,
+                                                                  SlotDiv cdiv, const ulonglong2* __restrict__ twv,
+                                                                  uint32_t nwv, const uint32_t* __restrict__ cwords,
+                                                                  const char* __restrict__ str1,
+                                                                  const char* __restrict__ str2,
+                                                                  const uint8_t* __restrict__ code,
+                                                                  const double* __restrict__ hom,
+                                                                  const double* __restrict__ het, CType ct,
+                                                                  const uint32_t* __restrict__ bsum,
+                                                                  const uint64_t* __restrict__ boff,
+                                                                  const uint64_t* state, unsigned long long* lb,
+                                                                  char* __restrict__ out, uint32_t xm)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) lb[4] = state[4];
+    const uint64_t nb = (n + FTB - 1) / FTB;
+    for (int it = 0; it < SPB; ++it) {
+        const uint64_t b = (uint64_t)blockIdx.x * SPB + it;
+        if (b >= nb) break;
+        if (bsum[b] == 0) continue;   // (block-uniform: one address)
+        const uint64_t i = b * FTB + threadIdx.x;
+        int l = 0;
+        Head h{0, 0, 0, 0};
+        uint4 ea = make_uint4(0, 0, 0, 0), eb = ea;
+        bool tab = false;
+        uint8_t c = 0;
+        if (i < n) {
+            const uint32_t w = cwords[i];
+            const uint32_t t = slot_tile((uint32_t)i, cdiv);
+            const uint32_t j = (uint32_t)i - __umul24(t, cap);
+            if (j < tcnt[t] && w != SID_CLS_SKIP) {
+                if (WV && cls_compact(w)) {   // (the entry: tile_wave_store)
+                    const ulonglong2 te = twv[__umul24(t, nwv) + (j >> 6)];
+                    const uint32_t dp = (w >> 20) & (SID_CLS_DPOS - 1);
+                    h.clen = (uint32_t)(te.y >> 32) & 0xFFFu;
+                    h.pos = (int32_t)((uint32_t)te.y + dp);
+                    h.c8 = te.x;
+                    h.cb = 0;
+                } else {
+                    Reader R{text, len};
+                    h = slot_head(R, *(const ulonglong2*)(hdr + 2 * i));
+                }
+                if (w != SID_CLS_MISS) {
+                    const uint32_t k = w & 0xFFFFFu;
+                    const uint4* e = (const uint4*)(k < SID_TAB_N ? str1 + (size_t)k * SID_STR_BYTES
+                                                                  : str2 + (size_t)(k - SID_TAB_N) * SID_STR_BYTES);
+                    ea = e[0];
+                    eb = e[1];
+                    tab = (ea.x & 0xFFu) != 0xFFu;
+                }
+                if (tab) {
+                    const uint32_t f = (w >> 28) & 3u, s2 = w >> 30;
+                    const bool het_l = (ea.x >> 8) & 1u;
+                    c = (uint8_t)(f | ((het_l ? s2 : f) << 2) | (het_l ? 0x80u : 0u));
+                    l = code_out(c, xm) ? 0 : local_rec_len(h, ea.x & 0xFFu);
+                } else {   // the fix-up's site
+                    c = code[i];
+                    l = code_out(c, xm) ? 0 : miss_len<1>(h, c, hom[i], het[i], ct);
+                }
+            }
+        }
+        uint32_t tot;
+        const uint32_t my = block_exscan<FTB>((uint32_t)l, &tot);
+        char* const dst = out + boff[b] + my;
+        if (l && tab) record_put_tail<1>(text, len, h, c, ea, eb, dst);
+        else if (l) miss_put<1>(text, len, h, c, hom[i], het[i], ct, dst);
+    }
 }
 
 // ---- likelihood_ratio / bayes, fused with the class lookup: a site's
@@ -2924,6 +3102,9 @@ __device__ __forceinline__ int lynch_rec_len(const Head& h, uint32_t tail)
     return (int)h.clen + 1 + sid_i32_len(h.pos) + 1 + (int)tail;
 }
 
+// SPARSE (a selection that keeps few records): the header pair loaded only by
+// the sites that have a record, not beside every site's class lookup
+template <bool SPARSE>
 __global__ __launch_bounds__(FTB) void sid_lynch_len_kernel(const char* __restrict__ text, uint64_t len,
                                                            const sid_off_t* __restrict__ starts,
                                                            const uint64_t* __restrict__ hdr, uint64_t n,
@@ -2943,7 +3124,8 @@ __global__ __launch_bounds__(FTB) void sid_lynch_len_kernel(const char* __restri
         int l = 0;
         if (i < n && !V.empty) {
             const uint64_t w = counts[i];
-            const ulonglong2 hw = *(const ulonglong2*)(hdr + 2 * i);   // in flight beside the class lookup
+            ulonglong2 hw = make_ulonglong2(0, 0);
+            if (!SPARSE) hw = *(const ulonglong2*)(hdr + 2 * i);   // in flight beside the class lookup
             const uint32_t d = sid_dense_code(w);
             uint32_t L = 0;
             if (d != SID_DENSE_NONE) {
@@ -2953,6 +3135,7 @@ __global__ __launch_bounds__(FTB) void sid_lynch_len_kernel(const char* __restri
                 L = idx == 0xFFFFFFFFu ? 0u : (uint8_t)V.lstr[(size_t)idx * SID_LSTR_BYTES];
             }
             if (L) {
+                if (SPARSE) hw = *(const ulonglong2*)(hdr + 2 * i);
                 Reader R{text, len};
                 l = lynch_rec_len(site_head_hw(R, starts + i, hw), L);
             }
@@ -2992,6 +3175,7 @@ __device__ void lynch_record_bytes(Reader& R, const Head& h, const uint4 (&e)[4]
         if ((uint32_t)j < L) put(n + j, (w[j >> 2] >> (8 * (j & 3))) & 0xFFu);
 }
 
+template <int TAG = 0>   // (as record_put_tail's)
 __device__ __noinline__ void lynch_put_global(const char* text, uint64_t len, Head h, uint4 e0, uint4 e1, uint4 e2,
                                               uint4 e3, char* out)
 {
@@ -3000,6 +3184,7 @@ __device__ __noinline__ void lynch_put_global(const char* text, uint64_t len, He
     lynch_record_bytes(R, h, e, [&](uint32_t k, uint32_t ch) { out[k] = (char)ch; });
 }
 
+template <int TAG = 0>
 __device__ __noinline__ void lynch_put_or(const char* text, uint64_t len, Head h, uint4 e0, uint4 e1, uint4 e2,
                                           uint4 e3, unsigned long long* B, uint32_t q)
 {
@@ -3008,6 +3193,8 @@ __device__ __noinline__ void lynch_put_or(const char* text, uint64_t len, Head h
     lynch_record_bytes(R, h, e, [&](uint32_t k, uint32_t ch) { lds_or_byte(B, q + k, ch); });
 }
 
+// SEL: a selection by label -- a class of length 0 has no record (as the length kernel counted)
+template <bool SEL>
 __global__ __launch_bounds__(FTB, SID_PUT_WAVES) void sid_lynch_put_kernel(const char* __restrict__ text, uint64_t len,
                                                                           const sid_off_t* __restrict__ starts,
                                                                           const uint64_t* __restrict__ hdr, uint64_t n,
@@ -3036,9 +3223,11 @@ __global__ __launch_bounds__(FTB, SID_PUT_WAVES) void sid_lynch_put_kernel(const
             e1 = e[1];
             e2 = e[2];
             e3 = e[3];
-            Reader R{text, len};
-            h = site_head_hw(R, starts + i, hw);
-            l = lynch_rec_len(h, e0.x & 0xFFu);
+            if (!SEL || (e0.x & 0xFFu)) {
+                Reader R{text, len};
+                h = site_head_hw(R, starts + i, hw);
+                l = lynch_rec_len(h, e0.x & 0xFFu);
+            }
         }
     }
     __builtin_amdgcn_s_setprio(0);
@@ -3047,7 +3236,7 @@ __global__ __launch_bounds__(FTB, SID_PUT_WAVES) void sid_lynch_put_kernel(const
     const uint32_t my = block_exscan_once<FTB>((uint32_t)l, &tot);   // (its barrier also orders the zeroing)
     char* const dst = out + boff[blockIdx.x];
     if (tot > FMT_LDS2) {   // long records (long chromosome names): straight to global, byte by byte
-        if (l) lynch_put_global(text, len, h, e0, e1, e2, e3, dst + my);
+        if (l) lynch_put_global<SEL>(text, len, h, e0, e1, e2, e3, dst + my);
         return;
     }
     if (l && (h.c8 || h.clen == 0) && h.pos >= 0) {
@@ -3064,16 +3253,75 @@ __global__ __launch_bounds__(FTB, SID_PUT_WAVES) void sid_lynch_put_kernel(const
                                 ((uint64_t)e3.w << 32) | e3.z};
         lds_or_run<7>(B, q1 + (uint32_t)pl + 2, tv);
     } else if (l) {
-        lynch_put_or(text, len, h, e0, e1, e2, e3, B, my);
+        lynch_put_or<SEL>(text, len, h, e0, e1, e2, e3, B, my);
     }
     __syncthreads();
     block_store<true>((const char*)buf4, tot, dst);
 }
 
+// The sparse writer of a selection that keeps few records (--only het: about
+// a site in a thousand).  A block walks SPB 512-site groups; a group without
+// record bytes (its block sum) costs one load.  In the others every site
+// loads its counts (8 B) and resolves its class's tail length from the LDS
+// copy of the dense length table, as the length kernel does; only a selected
+// site goes on to its header pair and its class's tail, and stores its record
+// byte by byte at the group's offset + its prefix (no LDS assembly: the
+// records are too few to fill 16-B stores).
+__global__ __launch_bounds__(FTB) void sid_lynch_put_sparse_kernel(const char* __restrict__ text, uint64_t len,
+                                                                  const sid_off_t* __restrict__ starts,
+                                                                  const uint64_t* __restrict__ hdr, uint64_t n,
+                                                                  const uint64_t* __restrict__ counts, sid_lynch_fmt V,
+                                                                  const uint32_t* __restrict__ bsum,
+                                                                  const uint64_t* __restrict__ boff,
+                                                                  const uint64_t* state, unsigned long long* lb,
+                                                                  char* __restrict__ out)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t DL[SID_DENSE_N];
+    ((uint4*)DL)[2 * threadIdx.x] = ((const uint4*)V.dlen)[2 * threadIdx.x];
+    ((uint4*)DL)[2 * threadIdx.x + 1] = ((const uint4*)V.dlen)[2 * threadIdx.x + 1];
+    if (blockIdx.x == 0 && threadIdx.x == 0) lb[4] = state[4];
+    __syncthreads();
+    const uint64_t nb = (n + FTB - 1) / FTB;
+    for (int it = 0; it < SPB; ++it) {
+        const uint64_t b = (uint64_t)blockIdx.x * SPB + it;
+        if (b >= nb) break;
+        if (bsum[b] == 0) continue;   // (block-uniform: one address)
+        const uint64_t i = b * FTB + threadIdx.x;
+        int l = 0;
+        Head h{0, 0, 0, 0};
+        uint4 e0 = make_uint4(0, 0, 0, 0), e1 = e0, e2 = e0, e3 = e0;
+        if (i < n) {
+            const uint64_t w = counts[i];
+            const uint32_t d = sid_dense_code(w);
+            uint32_t idx = 0xFFFFFFFFu;
+            if (d != SID_DENSE_NONE) {
+                if (DL[d]) idx = V.dense_cidx[d];
+            } else {
+                idx = lynch_class(w, V);
+            }
+            if (idx != 0xFFFFFFFFu) {
+                const uint4* e = (const uint4*)(V.lstr + (size_t)idx * SID_LSTR_BYTES);
+                e0 = e[0];
+                if (e0.x & 0xFFu) {
+                    e1 = e[1];
+                    e2 = e[2];
+                    e3 = e[3];
+                    Reader R{text, len};
+                    h = site_head_hw(R, starts + i, *(const ulonglong2*)(hdr + 2 * i));
+                    l = lynch_rec_len(h, e0.x & 0xFFu);
+                }
+            }
+        }
+        uint32_t tot;
+        const uint32_t my = block_exscan<FTB>((uint32_t)l, &tot);
+        if (l) lynch_put_global<1>(text, len, h, e0, e1, e2, e3, out + boff[b] + my);
+    }
+}
+
 // tails of the U classes (one thread each), then the dense codes' lengths
 __global__ __launch_bounds__(256) void sid_lynch_str_kernel(const uint8_t* __restrict__ pcode,
                                                            const double* __restrict__ cc, uint32_t U, CType ct,
-                                                           char* __restrict__ lstr, uint32_t* bad)
+                                                           char* __restrict__ lstr, uint32_t* bad, uint32_t xm)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= U) return;
@@ -3101,7 +3349,9 @@ __global__ __launch_bounds__(256) void sid_lynch_str_kernel(const uint8_t* __res
     if (n > SID_LSTR_BYTES - 8) atomicExch(bad, 1u);   // (45 at most: never)
     char* e = lstr + (size_t)i * SID_LSTR_BYTES;
     for (int k = 0; k < SID_LSTR_BYTES; ++k) e[k] = 0;
-    e[0] = (char)n;
+    // (a class whose label the selection leaves out: length 0, no record --
+    // a real tail is never empty; the text stays, for nobody)
+    e[0] = code_out(c, xm) ? (char)0 : (char)n;
     for (int k = 0; k < n && k < SID_LSTR_BYTES - 8; ++k) e[8 + k] = t[k];
 }
 
@@ -3547,7 +3797,8 @@ extern "C" int sid_dtext_parse_fd(sid_ctx* ctx, int fd, uint64_t offset, uint64_
     return SID_OK;
 }
 
-// CSV records of sites [begin, end) (code bit 6: skipped) into pinned staging
+// CSV records of sites [begin, end) (code bit 6, or a label the context's
+// selection leaves out: skipped) into pinned staging
 // buffers piece by piece; write() receives them in order.
 extern "C" int sid_dtext_format(sid_ctx* ctx, const sid_dtext* T, size_t begin, size_t end, const uint8_t* d_code,
                                 const double* d_hom, const double* d_het, const char* conf_type,
@@ -3623,7 +3874,7 @@ extern "C" int sid_dtext_format(sid_ctx* ctx, const sid_dtext* T, size_t begin, 
         hip(hipMemsetAsync(d_bad, 0, 4, st));
         hip(hipMemsetAsync(d_base, 0, 8, st));
         sid_fmt_len_kernel<<<(unsigned)nb, TB, 0, st>>>(T->d_text, T->len, T->d_starts, T->d_hdr, begin, end, d_code, d_hom,
-                                                        d_het, ct, d_bsum, d_bad);
+                                                        d_het, ct, d_bsum, d_bad, sel_word(ctx->opts.select));
         launch_scan(d_bsum, nb, d_boff, d_base, nullptr,
                     (uint64_t*)((char*)d_bsum + ((std::max<size_t>(nb, 1) * 4 + 7) & ~(size_t)7)), st);
         hip(hipGetLastError());
@@ -3660,7 +3911,8 @@ extern "C" int sid_dtext_format(sid_ctx* ctx, const sid_dtext* T, size_t begin, 
         flush(k);   // buffer k is about to be reused
         if (rc != SID_OK) break;
         sid_fmt_write_kernel<<<(unsigned)(b1 - b0), TB, 0, st>>>(T->d_text, T->len, T->d_starts, T->d_hdr, s0, s1, d_code, d_hom,
-                                                                 d_het, ct, d_boff + b0, boff[b0], d_out[k]);
+                                                                 d_het, ct, d_boff + b0, boff[b0], d_out[k],
+                                                                 sel_word(ctx->opts.select));
         if (!hip(hipGetLastError())) break;
         hip(hipEventRecord(written, st));
         hip(hipStreamWaitEvent(cs, written, 0));
@@ -3883,7 +4135,9 @@ void sid_chunk_release(sid_chunk_ws* W)
                     (void*)W->bsum, (void*)W->boff, (void*)W->tcnt, (void*)W->toff, (void*)W->state,
                     (void*)W->hdr, (void*)W->fb, (void*)W->masks, (void*)W->lb, (void*)W->cls, (void*)W->twv})
         if (p) (void)hipFree(p);
+    const int select = W->select;   // (the owner's option, not the buffers')
     *W = sid_chunk_ws{};
+    W->select = select;
 }
 
 // blocks of the strided index kernels (count kernel, index stage per 50M
@@ -3913,6 +4167,9 @@ int sid_chunk_index(sid_chunk_ws* W, const char* base, uint64_t c0, uint64_t c1,
 
 // line offsets from the index's masks + the two-pass parse of the n sites;
 // state[4] = min(offset * 8 + kind) over the malformed lines (all ones: none)
+// -m local with a selection by label: the context's filtered tail-length tables
+static bool local_sel(const sid_ctx* ctx) { return ctx->opts.select != SID_SELECT_ALL && ctx->ws.len1f; }
+
 int sid_chunk_parse(sid_chunk_ws* W, const char* base, uint64_t c0, uint64_t c1, uint64_t n, int qmode,
                     hipStream_t st, const sid_ctx* lctx)
 {
@@ -3939,13 +4196,17 @@ int sid_chunk_parse(sid_chunk_ws* W, const char* base, uint64_t c0, uint64_t c1,
         // sid_chunk_local_len then has only the fix-up and the scan left
         // (lb: [0] the miss count, [1] bytes, [2] range flag; zeroed above)
         uint32_t* late = W->fb + W->site_cap;
-        const LocalLen LL{lctx->ws.len1, lctx->ws.len2, W->bsum, W->fb + 2 * W->site_cap, W->lb, W->cls};
+        const bool sel = local_sel(lctx);   // (a selection by label: the filtered tail lengths)
+        const LocalLen LL{sel ? lctx->ws.len1f : lctx->ws.len1, sel ? lctx->ws.len2f : lctx->ws.len2, W->bsum,
+                          W->fb + 2 * W->site_cap, W->lb, W->cls};
         const unsigned pg = (unsigned)std::min<uint64_t>((n + TB - 1) / TB, 16384);
-        sid_parse_len_kernel<<<line_walk_grid(n, c1 - c0, pg), TB, 0, st>>>(base, c1, W->starts, W->state + 1,
-                                                                            W->counts, W->hdr, W->fb, fbn, LL);
+        auto plen = sel ? sid_parse_len_kernel<true> : sid_parse_len_kernel<false>;
+        plen<<<line_walk_grid(n, c1 - c0, pg), TB, 0, st>>>(base, c1, W->starts, W->state + 1, W->counts, W->hdr,
+                                                            W->fb, fbn, LL);
         sid_parse_serial_kernel<<<256, TB, 0, st>>>(base, c1, W->starts, W->state + 1, W->counts, W->hdr, W->fb,
                                                     fbn, (unsigned long long*)(W->state + 4), 0, late, fbn + 1);
-        sid_local_len_list_kernel<<<64, TB, 0, st>>>(base, c1, W->starts, W->hdr, W->counts, late, fbn + 1, LL);
+        auto llist = sel ? sid_local_len_list_kernel<true> : sid_local_len_list_kernel<false>;
+        llist<<<64, TB, 0, st>>>(base, c1, W->starts, W->hdr, W->counts, late, fbn + 1, LL);
         W->lens_ready = true;
         W->cls_ready = true;
     } else {
@@ -3990,7 +4251,7 @@ int sid_chunk_fmt_len(sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n
     WCHECK(hipMemsetAsync(W->lb, 0, 8 * 8, st));
     const uint64_t nb = (n + FTB - 1) / FTB;
     if (nb) sid_fmt_blen_kernel<<<(unsigned)nb, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->code, W->hom,
-                                                              W->het, ct, W->bsum, W->lb);
+                                                              W->het, ct, W->bsum, W->lb, sel_word(W->select));
     WCHECK(hipGetLastError());
     return fmt_scan(W, nb, st);
 }
@@ -4004,14 +4265,15 @@ int sid_chunk_fmt_put(sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n
     if (nb == 0) return hipMemcpyAsync(W->lb + 4, W->state + 4, 8, hipMemcpyDeviceToDevice, st) == hipSuccess
                             ? SID_OK : SID_EHIP;
     sid_fmt_put_kernel<<<(unsigned)nb, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->code, W->hom, W->het, ct,
-                                                    W->boff, W->state, W->lb, out);
+                                                    W->boff, W->state, W->lb, out, sel_word(W->select));
     WCHECK(hipGetLastError());
     return SID_OK;
 }
 
 bool sid_chunk_local_ok(const sid_ctx* ctx)
 {
-    return ctx->opts.method == SID_METHOD_LOCAL && !ctx->K.general && ctx->ws.str1;
+    return ctx->opts.method == SID_METHOD_LOCAL && !ctx->K.general && ctx->ws.str1 &&
+           (ctx->opts.select == SID_SELECT_ALL || ctx->ws.len1f);
 }
 
 // the string tables hold -m local's record tails, conf_type "p_value" included
@@ -4035,10 +4297,13 @@ int sid_chunk_local_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     if (nb) {
         const unsigned grid = (unsigned)((nb + LPB - 1) / LPB);
         if (!W->lens_ready)   // (else the parse computed them: sid_parse_len_kernel)
-            sid_local_len_kernel<<<grid, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->counts, ctx->ws.len1,
-                                                       ctx->ws.len2, W->bsum, miss, W->lb);
+            sid_local_len_kernel<<<grid, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->counts,
+                                                       local_sel(ctx) ? ctx->ws.len1f : ctx->ws.len1,
+                                                       local_sel(ctx) ? ctx->ws.len2f : ctx->ws.len2, W->bsum, miss,
+                                                       W->lb);
         sid_local_fixlen_kernel<false><<<64, TB, 0, st>>>(base, c1, W->starts, W->hdr, W->counts, miss, W->lb, ctx->K,
-                                                   ctx->d_lnt, ct, W->code, W->hom, W->het, W->bsum, W->lb);
+                                                   ctx->d_lnt, ct, W->code, W->hom, W->het, W->bsum, W->lb,
+                                                   sel_word(ctx->opts.select));
     }
     W->lens_ready = false;
     WCHECK(hipGetLastError());
@@ -4051,16 +4316,36 @@ int sid_chunk_local_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     CType ct;
     if (local_ctype(ctx, conf_type, &ct)) return SID_EINVAL;
     const uint64_t nb = (n + FTB - 1) / FTB;
+    const bool sel = local_sel(ctx);
     if (W->slot_cap) {   // the tile parse's slots
         const uint64_t nbs = (W->slots + FTB - 1) / FTB;
         if (nbs == 0) return hipMemcpyAsync(W->lb + 4, W->state + 4, 8, hipMemcpyDeviceToDevice, st) == hipSuccess
                                  ? SID_OK : SID_EHIP;
         if (W->slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (slot_tile's exact range: a 4 GiB chunk has fewer)
         const SlotDiv cdiv = slot_div(W->slot_cap);
-        auto put = W->tile_quad ? sid_local_put_kernel<true, false> : sid_local_put_kernel<true, true>;
-        put<<<(unsigned)nbs, FTB, 0, st>>>(base, c1, nullptr, W->hdr, W->slots, W->tcnt, W->slot_cap, cdiv, W->twv,
-                                           tile_nwv(W->slot_cap), W->counts, W->cls, ctx->ws.str1, ctx->ws.str2,
-                                           W->code, W->hom, W->het, ct, W->boff, W->state, W->lb, out);
+        const uint32_t xm = sel_word(ctx->opts.select);
+        if (ctx->opts.select == SID_SELECT_HET) {
+            // about a site in a thousand: the sparse writer (hom keeps nearly
+            // all: the LDS assembly below, with the skip word honoured)
+            auto sput = W->tile_quad ? sid_local_put_sparse_kernel<false> : sid_local_put_sparse_kernel<true>;
+            sput<<<(unsigned)((nbs + SPB - 1) / SPB), FTB, 0, st>>>(base, c1, W->hdr, W->slots, W->tcnt, W->slot_cap,
+                                                                    cdiv, W->twv, tile_nwv(W->slot_cap), W->cls,
+                                                                    ctx->ws.str1, ctx->ws.str2, W->code, W->hom, W->het,
+                                                                    ct, W->bsum, W->boff, W->state, W->lb, out, xm);
+            WCHECK(hipGetLastError());
+            return SID_OK;
+        }
+        if (sel) {
+            auto put = W->tile_quad ? sid_local_put_sel_kernel<true, false> : sid_local_put_sel_kernel<true, true>;
+            put<<<(unsigned)nbs, FTB, 0, st>>>(base, c1, nullptr, W->hdr, W->slots, W->tcnt, W->slot_cap, cdiv, W->twv,
+                                               tile_nwv(W->slot_cap), W->counts, W->cls, ctx->ws.str1, ctx->ws.str2,
+                                               W->code, W->hom, W->het, ct, W->boff, W->state, W->lb, out, xm);
+        } else {
+            auto put = W->tile_quad ? sid_local_put_kernel<true, false> : sid_local_put_kernel<true, true>;
+            put<<<(unsigned)nbs, FTB, 0, st>>>(base, c1, nullptr, W->hdr, W->slots, W->tcnt, W->slot_cap, cdiv, W->twv,
+                                               tile_nwv(W->slot_cap), W->counts, W->cls, ctx->ws.str1, ctx->ws.str2,
+                                               W->code, W->hom, W->het, ct, W->boff, W->state, W->lb, out);
+        }
         WCHECK(hipGetLastError());
 #ifdef SID_TP_STAMP
         {
@@ -4080,16 +4365,18 @@ int sid_chunk_local_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     }
     if (nb == 0) return hipMemcpyAsync(W->lb + 4, W->state + 4, 8, hipMemcpyDeviceToDevice, st) == hipSuccess
                             ? SID_OK : SID_EHIP;
-    if (W->cls_ready)
-        sid_local_put_kernel<true><<<(unsigned)nb, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, nullptr, 0, SlotDiv{0, 0},
-                                                                nullptr, 0, W->counts, W->cls,
-                                                                ctx->ws.str1, ctx->ws.str2, W->code, W->hom, W->het,
-                                                                ct, W->boff, W->state, W->lb, out);
-    else
-        sid_local_put_kernel<false><<<(unsigned)nb, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, nullptr, 0,
-                                                                 SlotDiv{0, 0}, nullptr, 0, W->counts, nullptr,
-                                                                 ctx->ws.str1, ctx->ws.str2, W->code, W->hom, W->het,
-                                                                 ct, W->boff, W->state, W->lb, out);
+    const uint32_t* cw = W->cls_ready ? W->cls : nullptr;
+    if (sel) {
+        auto put = W->cls_ready ? sid_local_put_sel_kernel<true> : sid_local_put_sel_kernel<false>;
+        put<<<(unsigned)nb, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, nullptr, 0, SlotDiv{0, 0}, nullptr, 0,
+                                          W->counts, cw, ctx->ws.str1, ctx->ws.str2, W->code, W->hom, W->het, ct,
+                                          W->boff, W->state, W->lb, out, sel_word(ctx->opts.select));
+    } else {
+        auto put = W->cls_ready ? sid_local_put_kernel<true> : sid_local_put_kernel<false>;
+        put<<<(unsigned)nb, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, nullptr, 0, SlotDiv{0, 0}, nullptr, 0,
+                                          W->counts, cw, ctx->ws.str1, ctx->ws.str2, W->code, W->hom, W->het, ct,
+                                          W->boff, W->state, W->lb, out);
+    }
     WCHECK(hipGetLastError());
     return SID_OK;
 }
@@ -4100,15 +4387,15 @@ static uint64_t tile_count(uint64_t c0, uint64_t c1, bool quad)
     return c1 > c0 ? (c1 - t0 + tp_tile(quad) - 1) / tp_tile(quad) : 0;
 }
 
-template <bool LOCAL>
+template <bool LOCAL, bool SEL = false>
 static void launch_tile_parse(bool quad, const char* base, uint64_t c0, uint64_t c1, uint64_t ntp, const TileOut& O,
                               const LocalLen& LL, hipStream_t st)
 {
     const uint64_t tb = c0 & ~(uint64_t)15;
     if (quad)
-        sid_tile_parse_kernel<true, LOCAL><<<(unsigned)ntp, TB, 0, st>>>(base, tb, c0, c1, O, LL);
+        sid_tile_parse_kernel<true, LOCAL, SEL><<<(unsigned)ntp, TB, 0, st>>>(base, tb, c0, c1, O, LL);
     else
-        sid_tile_parse_kernel<false, LOCAL><<<(unsigned)ntp, TB, 0, st>>>(base, tb, c0, c1, O, LL);
+        sid_tile_parse_kernel<false, LOCAL, SEL><<<(unsigned)ntp, TB, 0, st>>>(base, tb, c0, c1, O, LL);
 #ifdef SID_TP_STAMP
     {
         const uint64_t m = std::min<uint64_t>(ntp, TP_STAMP_N);
@@ -4169,13 +4456,16 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
         return fmt_scan(W, nb, st);
     }
     uint32_t* miss = W->fb + 2 * W->site_cap;
-    const LocalLen LL{ctx->ws.len1, ctx->ws.len2, W->bsum, miss, W->lb, W->cls};
+    const bool sel = local_sel(ctx);   // (a selection by label: the filtered tail lengths, the skip word)
+    const LocalLen LL{sel ? ctx->ws.len1f : ctx->ws.len1, sel ? ctx->ws.len2f : ctx->ws.len2, W->bsum, miss, W->lb,
+                      W->cls};
     const TileOut O{cap, W->tcnt, W->hdr, W->counts, W->fb, W->starts, W->lb, W->state, W->twv, tile_nwv(cap)};
-    launch_tile_parse<true>(quad, base, c0, c1, ntp, O, LL, st);
-    const LocalFix F{LL, ctx->K, ctx->d_lnt, ct, W->code, W->hom, W->het};
-    sid_tile_serial_kernel<true><<<TILE_SERIAL_GRID, TB, 0, st>>>(base, c1, W->fb, W->starts, W->lb, W->tcnt, ntp,
-                                                     cap, W->counts, W->hdr,
-                                                     (unsigned long long*)(W->state + 4), F);
+    if (sel) launch_tile_parse<true, true>(quad, base, c0, c1, ntp, O, LL, st);
+    else launch_tile_parse<true>(quad, base, c0, c1, ntp, O, LL, st);
+    const LocalFix F{LL, ctx->K, ctx->d_lnt, ct, W->code, W->hom, W->het, sel_word(ctx->opts.select)};
+    auto serial = sel ? sid_tile_serial_kernel<true, true> : sid_tile_serial_kernel<true>;
+    serial<<<TILE_SERIAL_GRID, TB, 0, st>>>(base, c1, W->fb, W->starts, W->lb, W->tcnt, ntp, cap, W->counts, W->hdr,
+                                            (unsigned long long*)(W->state + 4), F);
     WCHECK(hipGetLastError());
     W->cls_ready = true;
     return fmt_scan(W, nb, st);
@@ -4237,8 +4527,8 @@ int sid_chunk_lynch_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     if (nb && V.empty) {   // no class: every site dropped (and no length table)
         WCHECK(hipMemsetAsync(W->bsum, 0, nb * 4, st));
     } else if (nb) {
-        sid_lynch_len_kernel<<<(unsigned)((nb + LPB - 1) / LPB), FTB, 0, st>>>(base, c1, W->starts, W->hdr, n,
-                                                                                W->counts, V, W->bsum);
+        (ctx->opts.select == SID_SELECT_HET ? sid_lynch_len_kernel<true> : sid_lynch_len_kernel<false>)
+            <<<(unsigned)((nb + LPB - 1) / LPB), FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->counts, V, W->bsum);
     }
     WCHECK(hipGetLastError());
     return fmt_scan(W, nb, st);
@@ -4252,19 +4542,26 @@ int sid_chunk_lynch_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     const uint64_t nb = (n + FTB - 1) / FTB;
     if (nb == 0) return hipMemcpyAsync(W->lb + 4, W->state + 4, 8, hipMemcpyDeviceToDevice, st) == hipSuccess
                             ? SID_OK : SID_EHIP;
-    sid_lynch_put_kernel<<<(unsigned)nb, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->counts, V, W->boff,
-                                                      W->state, W->lb, out);
+    // --only het keeps about a site in a thousand: the sparse writer; hom
+    // keeps nearly all, and goes through the LDS assembly with the others'
+    // length 0 honoured
+    if (ctx->opts.select == SID_SELECT_HET && !V.empty)
+        sid_lynch_put_sparse_kernel<<<(unsigned)((nb + SPB - 1) / SPB), FTB, 0, st>>>(
+            base, c1, W->starts, W->hdr, n, W->counts, V, W->bsum, W->boff, W->state, W->lb, out);
+    else
+        (ctx->opts.select != SID_SELECT_ALL ? sid_lynch_put_kernel<true> : sid_lynch_put_kernel<false>)
+            <<<(unsigned)nb, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->counts, V, W->boff, W->state, W->lb, out);
     WCHECK(hipGetLastError());
     return SID_OK;
 }
 
 hipError_t sid_launch_lynch_str_build(const uint8_t* pcode, const double* cc, uint32_t U, const char* conf_type,
                                       const uint32_t* dense_cidx, char* lstr, uint8_t* dlen, uint32_t* bad,
-                                      hipStream_t st)
+                                      int select, hipStream_t st)
 {
     CType ct;
     if (chunk_ctype(conf_type, &ct)) return hipErrorInvalidValue;
-    if (U) sid_lynch_str_kernel<<<(U + 255) / 256, 256, 0, st>>>(pcode, cc, U, ct, lstr, bad);
+    if (U) sid_lynch_str_kernel<<<(U + 255) / 256, 256, 0, st>>>(pcode, cc, U, ct, lstr, bad, sel_word(select));
     sid_lynch_dlen_kernel<<<SID_DENSE_N / 256, 256, 0, st>>>(dense_cidx, lstr, dlen);
     return hipGetLastError();
 }
