@@ -34,6 +34,16 @@
  *     the per-site arrays (code / confs) are not changed by it.  Host
  *     formatting (sid_format_csv) takes no context: sid_select_mark marks the
  *     codes first.
+ *   - Selection by region (sid_opts.regions, a sid_regions; NULL = every
+ *     site): the same formatters emit only the records whose site lies inside
+ *     the set -- its chrom field equals a set chrom byte for byte and start <
+ *     pos <= end (BED: 0-based, half-open), pos being the integer the record
+ *     prints -- byte for byte and in the order of the unselected output.  With
+ *     a selection by label as well, a record is emitted when both hold.  The
+ *     calls, the -R prior, the Lynch estimate and Benjamini-Hochberg see every
+ *     site; the caller's per-site arrays are not changed.  sid_create and
+ *     sid_engine_create copy what they need: the object may be freed right
+ *     after.  Host formatting: sid_regions_mark marks the codes first.
  *   - Counts layout: profile_t (pileup.hpp:7) = 4 x uint16 {A,C,G,T} per site,
  *     array of structures, 8 bytes per site.
  */
@@ -95,12 +105,50 @@ typedef struct {
                                     emitted, by label; sid_create and
                                     sid_engine_create return SID_EINVAL for any
                                     other value                                    */
+    const struct sid_regions* regions; /* --regions (default NULL = every site): the
+                                    records emitted, by (chrom, pos); see
+                                    sid_regions_* below                            */
 } sid_opts;
 void sid_opts_default(sid_opts* o);
 /* Sets SID_CODE_DROPPED on the n host codes whose label is not `select`, so
  * that sid_format_csv skips them (SID_SELECT_ALL: nothing changes).
  * SID_EINVAL for another value of select or a NULL code with n != 0. */
 int sid_select_mark(uint8_t* code /* host */, size_t n, int select);
+
+/* ---------------------------------------------------------- region sets --
+ * A set of (chrom, start, end) intervals in BED convention (0-based,
+ * half-open), merged per chrom into sorted, disjoint intervals; a site is
+ * inside when its chrom equals a set chrom byte for byte and start < pos <=
+ * end.  A set without a non-empty interval is valid and holds nothing.
+ *
+ * sid_regions_from_bed: BED text.  Lines end in '\n' (a final line without
+ *   one counts); empty lines and lines starting with '#', "track" or
+ *   "browser" are skipped; fields are separated by runs of space or tab.
+ *   Three or more fields: chrom start end (the rest ignored), start and end
+ *   decimal with 0 <= start <= end, an end above 2^31-1 clamped, start == end
+ *   an empty interval.  One field: the whole chromosome, 0 .. 2^31-1.
+ *   Anything else (two fields, a sign, a non-digit, start > end): SID_EINVAL
+ *   and the 1-based line number in *err_line.
+ * sid_regions_from_intervals: n intervals from arrays (SID_EINVAL for a NULL
+ *   or empty chrom, one holding a space, tab or newline, start < 0 or start >
+ *   end).
+ * sid_regions_intervals / _chroms: the intervals after the merge, and the
+ *   chroms that own at least one.
+ * sid_regions_contains: 1 / 0, on the host.
+ * sid_regions_mark: sets SID_CODE_DROPPED on the host codes code[begin, end)
+ *   of the sites outside (regions == NULL: nothing changes), so that
+ *   sid_format_csv skips them -- the analogue of sid_select_mark. */
+typedef struct sid_regions sid_regions;
+struct sid_sites;
+int sid_regions_from_bed(const char* text, size_t len, sid_regions** out, uint64_t* err_line);
+int sid_regions_from_intervals(const char* const* chrom, const int32_t* start, const int32_t* end, size_t n,
+                               sid_regions** out);
+size_t sid_regions_intervals(const sid_regions* r);
+size_t sid_regions_chroms(const sid_regions* r);
+int sid_regions_contains(const sid_regions* r, const char* chrom, size_t chrom_len, int32_t pos);
+void sid_regions_free(sid_regions* r);
+int sid_regions_mark(const sid_regions* r, const struct sid_sites* s, size_t begin, size_t end,
+                     uint8_t* code /* host */);
 
 /* ------------------------------------------------------------- contexts -- */
 typedef struct sid_ctx sid_ctx;
@@ -338,7 +386,8 @@ typedef struct {
     uint64_t chunks;
     uint64_t bytes_in;           /* input text bytes                                 */
     uint64_t bytes_out;          /* CSV bytes written (header excluded; with a
-                                    selection: the selected records')               */
+                                    selection by label or region: the selected
+                                    records')                                       */
     uint64_t chunks_held;        /* formatted in the first pass                      */
     uint64_t chunks_retained;    /* text kept in HBM for the second pass             */
     uint64_t chunks_reloaded;    /* text read from the source a second time          */

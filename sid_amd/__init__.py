@@ -48,7 +48,8 @@ class SidError(RuntimeError):
 class Opts(C.Structure):
     """sid_opts = GlobalOptions (sid.cpp:11-17)."""
     _fields_ = [("method", C.c_int), ("estimate_prior", C.c_int), ("snp_prior", C.c_double),
-                ("significance_level", C.c_double), ("site_error_threshold", C.c_double), ("select", C.c_int)]
+                ("significance_level", C.c_double), ("site_error_threshold", C.c_double), ("select", C.c_int),
+                ("regions", C.c_void_p)]
 
 
 class Estimate(C.Structure):
@@ -98,6 +99,13 @@ SIGNATURES = [
     ("sid_version", C.c_char_p, []),
     ("sid_opts_default", None, [C.POINTER(Opts)]),
     ("sid_select_mark", _I, [_P, _SZ, _I]),
+    ("sid_regions_from_bed", _I, [C.c_char_p, _SZ, C.POINTER(_P), C.POINTER(C.c_uint64)]),
+    ("sid_regions_from_intervals", _I, [C.POINTER(C.c_char_p), _P, _P, _SZ, C.POINTER(_P)]),
+    ("sid_regions_intervals", _SZ, [_P]),
+    ("sid_regions_chroms", _SZ, [_P]),
+    ("sid_regions_contains", _I, [_P, C.c_char_p, _SZ, C.c_int32]),
+    ("sid_regions_free", None, [_P]),
+    ("sid_regions_mark", _I, [_P, _P, _SZ, _SZ, _P]),
     ("sid_device_count", _I, [C.POINTER(C.c_int)]),
     ("sid_create", _I, [_I, C.POINTER(Opts), C.POINTER(_P)]),
     ("sid_destroy", _I, [_P]),
@@ -192,8 +200,72 @@ def _ptr(a: np.ndarray):
 SELECT = {"all": 0, "het": 1, "hom": 2}   # SID_SELECT_*: the records emitted, by label (--only)
 
 
+class Regions:
+    """A region set (sid_regions, --regions): BED intervals, 0-based and
+    half-open, merged per chrom; a site is inside when start < pos <= end.
+    Built from BED bytes, a path to a BED file, or a list of (chrom, start,
+    end).  A malformed BED line raises SidError naming its 1-based line.
+    Context and Engine copy what they need when they are created, so the object
+    may be closed right after."""
+
+    def __init__(self, source):
+        self.h = None
+        L = lib()
+        h = C.c_void_p()
+        if isinstance(source, (str, os.PathLike)):
+            with open(source, "rb") as f:
+                source = f.read()
+        if isinstance(source, (bytes, bytearray, memoryview)):
+            text = bytes(source)
+            line = C.c_uint64(0)
+            st = L.sid_regions_from_bed(text, len(text), C.byref(h), C.byref(line))
+            if st != SID_OK:
+                raise SidError(st, f"sid_regions_from_bed: line {line.value}: malformed region")
+        else:
+            iv = list(source)
+            names = (C.c_char_p * max(len(iv), 1))(*[c if isinstance(c, bytes) else str(c).encode() for c, _, _ in iv])
+            for _, s, e in iv:
+                if not (-2**31 <= int(s) < 2**31 and -2**31 <= int(e) < 2**31):
+                    raise SidError(1, f"regions: interval ({s}, {e}) outside int32")
+            start = np.array([s for _, s, _ in iv], np.int32)
+            end = np.array([e for _, _, e in iv], np.int32)
+            check(L.sid_regions_from_intervals(names, _ptr(start), _ptr(end), len(iv), C.byref(h)),
+                  "sid_regions_from_intervals")
+        self.h = h
+
+    def _handle(self):
+        if not self.h:
+            raise SidError(1, "regions: the object is closed")
+        return self.h
+
+    def contains(self, chrom, pos: int) -> bool:
+        c = chrom if isinstance(chrom, bytes) else str(chrom).encode()
+        if not -2**31 <= int(pos) < 2**31:
+            return False
+        return bool(lib().sid_regions_contains(self._handle(), c, len(c), int(pos)))
+
+    def __len__(self):
+        """The intervals after the merge."""
+        return int(lib().sid_regions_intervals(self._handle()))
+
+    @property
+    def chroms(self) -> int:
+        return int(lib().sid_regions_chroms(self._handle()))
+
+    def close(self):
+        if getattr(self, "h", None) and _LIB is not None:
+            _LIB.sid_regions_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def make_opts(method="local", estimate_prior=False, snp_prior=-1.0, significance_level=0.05,
-              site_error_threshold=0.1, select="all") -> Opts:
+              site_error_threshold=0.1, select="all", regions=None) -> Opts:
     o = Opts()
     lib().sid_opts_default(C.byref(o))
     o.method = METHODS[method] if isinstance(method, str) else int(method)
@@ -204,6 +276,11 @@ def make_opts(method="local", estimate_prior=False, snp_prior=-1.0, significance
     if isinstance(select, str) and select not in SELECT:
         raise SidError(1, f"select: expected one of {sorted(SELECT)}, got {select!r}")
     o.select = SELECT[select] if isinstance(select, str) else int(select)
+    if regions is not None and not isinstance(regions, Regions):
+        raise SidError(1, f"regions: expected a Regions object or None, got {type(regions).__name__}")
+    # (the pointer alone: sid_create / sid_engine_create copy the set, and the
+    # caller keeps the Regions object until then)
+    o.regions = regions._handle() if regions is not None else None
     return o
 
 
@@ -278,6 +355,19 @@ def select_mark(code: np.ndarray, select="all") -> np.ndarray:
         raise SidError(1, f"select: expected one of {sorted(SELECT)}, got {select!r}")
     check(lib().sid_select_mark(_ptr(out), out.size, SELECT[select] if isinstance(select, str) else int(select)),
           "sid_select_mark")
+    return out
+
+
+def regions_mark(sites: Sites, code: np.ndarray, regions) -> np.ndarray:
+    """sid_regions_mark on a copy of the codes: the sites outside `regions`
+    get SID_CODE_DROPPED, so format_csv skips them (None: every site stays)."""
+    out = np.array(code, np.uint8, copy=True)
+    if regions is not None and not isinstance(regions, Regions):
+        raise SidError(1, f"regions: expected a Regions object or None, got {type(regions).__name__}")
+    if out.size != len(sites):
+        raise SidError(1, "regions_mark: one code per site")
+    check(lib().sid_regions_mark(regions._handle() if regions is not None else None, sites.handle, 0, out.size,
+                                 _ptr(out)), "sid_regions_mark")
     return out
 
 
@@ -374,6 +464,7 @@ class Context:
         self.device = device
         h = C.c_void_p()
         check(lib().sid_create(device, C.byref(self.opts), C.byref(h)), "sid_create")
+        self.opts.regions = None   # (the context holds its own copy of the set)
         self.h = h
 
     @classmethod
@@ -483,6 +574,7 @@ class Engine:
         self.cfg = cfg
         h = C.c_void_p()
         check(lib().sid_engine_create(C.byref(self.opts), C.byref(cfg), C.byref(h)), "sid_engine_create")
+        self.opts.regions = None   # (every pipeline's context holds its own copy of the set)
         self.h = h
         self._keep = None
 

@@ -13,6 +13,7 @@
 #include <thread>
 #include <vector>
 
+#include "regions.h"
 #include "sid_internal.h"
 #include "synth.h"
 
@@ -60,6 +61,7 @@ extern "C" void sid_opts_default(sid_opts* o)
     o->significance_level = 0.05;
     o->site_error_threshold = 0.1;
     o->select = SID_SELECT_ALL;
+    o->regions = nullptr;
 }
 
 // GSL 2.7.1 specfunc/gamma.c lngamma_lanczos (x >= 0.5, away from 1 and 2,
@@ -158,6 +160,21 @@ extern "C" int sid_create(int device, const sid_opts* opts, sid_ctx** out)
     if (e == hipSuccess) e = hipMalloc(&c->ws.ctr, 2 * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemset(c->ws.ctr, 0, 2 * sizeof(uint32_t));
     if (e == hipSuccess) e = sid_build_table(c);
+    // the region set: the context's own flat copy on the device (the caller's
+    // object may be freed after this call)
+    if (const sid_regions* rg = c->opts.regions) {
+        std::vector<char> flat;
+        sid_regions_layout L;
+        sid_regions_flatten(rg, flat, &L);
+        if (e == hipSuccess) e = hipMalloc(&c->d_regions, L.bytes);
+        if (e == hipSuccess) e = hipMemcpy(c->d_regions, flat.data(), L.bytes, hipMemcpyHostToDevice);
+        const char* b = c->d_regions;
+        c->regtab = sid_regtab{(const uint64_t*)(b + L.c8),   (const uint32_t*)(b + L.clen), (const uint32_t*)(b + L.noff),
+                               (const uint32_t*)(b + L.ibeg), (const int32_t*)(b + L.start), (const int32_t*)(b + L.end),
+                               b + L.names, L.nc, L.ni};
+        c->has_regions = true;
+        c->opts.regions = nullptr;
+    }
     if (e != hipSuccess) {
         int rc = sid_set_hip_error(e);
         sid_destroy(c);
@@ -180,6 +197,7 @@ extern "C" int sid_destroy(sid_ctx* c)
         if (p) (void)hipFree(p);
     if (c->ws.miss) (void)hipFree(c->ws.miss);
     if (c->ws.ctr) (void)hipFree(c->ws.ctr);
+    if (c->d_regions) (void)hipFree(c->d_regions);
     if (c->lynch) sid_lynch_dev_destroy(c->lynch);
     for (int b = 0; b < 2; ++b) {
         if (c->fmt_d[b]) (void)hipFree(c->fmt_d[b]);

@@ -11,7 +11,17 @@
 // Extra long options (no short letter, so they cannot collide with the
 // reference's flags): --devices N, --threads N, --stats, --host-parse,
 // --chunk-bytes N, --hold-bytes N, --retain-bytes N, --host-hold N,
-// --only het|hom|all.
+// --only het|hom|all, --regions FILE.
+//
+// --regions FILE (a BED file: chrom start end, 0-based half-open, or a chrom
+// alone for all of it; sid_regions_from_bed) writes the header and only the
+// records whose (chrom, pos) lies in the file's intervals -- the reference
+// pipeline's filter-exon-sites.sh step, or one chromosome of parallel-run-
+// sid.sh -- selected before the records are formatted (sid_opts.regions);
+// everything else, stderr included, is as without it, and with --only both
+// must hold.  The file is read when the option is parsed: "sid: --regions:
+// could not open FILE" or "sid: --regions: FILE:LINE: malformed region" on
+// stderr, exit status 1, nothing on stdout.  Given twice, the last wins.
 //
 // --only het (or hom) writes the header and only the records with that label
 // -- the reference pipeline's `zgrep ,het,` step, done before the records are
@@ -137,10 +147,18 @@ bool tool_attached()
     return false;
 }
 
+sid_regions* g_regions = nullptr;   // the --regions set: freed on the way out (finish, or exit's handler)
+void free_regions()
+{
+    sid_regions_free(g_regions);
+    g_regions = nullptr;
+}
+
 [[noreturn]] void finish(int code)
 {
     std::fflush(stdout);
     std::fflush(stderr);
+    free_regions();
     if (tool_attached()) std::exit(code);
     ::_exit(code);
 }
@@ -223,6 +241,8 @@ int main(int argc, char** argv)
     setenv("HSA_ENABLE_SDMA", "1", 0);
     Options opt;
     sid_opts_default(&opt.o);
+    sid_regions* regions = nullptr;   // --regions (kept for the run: --host-parse marks with it)
+    std::atexit(free_regions);   // (the ways out that do not go through finish)
     static const struct option LONG[] = {{"devices", required_argument, nullptr, 1},
                                          {"threads", required_argument, nullptr, 2},
                                          {"stats", no_argument, nullptr, 3},
@@ -232,6 +252,7 @@ int main(int argc, char** argv)
                                          {"retain-bytes", required_argument, nullptr, 7},
                                          {"host-hold", required_argument, nullptr, 8},
                                          {"only", required_argument, nullptr, 9},
+                                         {"regions", required_argument, nullptr, 10},
                                          {nullptr, 0, nullptr, 0}};
     int flag;
     while ((flag = getopt_long(argc, argv, "E:Rhm:p:r:", LONG, nullptr)) != -1) {
@@ -267,6 +288,36 @@ int main(int argc, char** argv)
                 std::exit(EXIT_FAILURE);
             }
             break;
+        case 10: {
+            std::string bed;
+            FILE* f = std::fopen(optarg, "rb");
+            if (!f) {
+                std::fflush(stdout);
+                std::fprintf(stderr, "sid: --regions: could not open %s\n", optarg);
+                std::exit(EXIT_FAILURE);
+            }
+            char buf[1 << 16];
+            for (size_t k; (k = std::fread(buf, 1, sizeof buf, f)) > 0;) bed.append(buf, k);
+            const bool unread = std::ferror(f) != 0;   // (a directory opens, and cannot be read)
+            std::fclose(f);
+            if (unread) {
+                std::fflush(stdout);
+                std::fprintf(stderr, "sid: --regions: could not open %s\n", optarg);
+                std::exit(EXIT_FAILURE);
+            }
+            sid_regions* rg = nullptr;
+            uint64_t bad = 0;
+            if (sid_regions_from_bed(bed.data(), bed.size(), &rg, &bad) != SID_OK) {
+                std::fflush(stdout);
+                std::fprintf(stderr, "sid: --regions: %s:%llu: malformed region\n", optarg, (unsigned long long)bad);
+                std::exit(EXIT_FAILURE);
+            }
+            sid_regions_free(regions);   // (given twice: the last wins)
+            regions = rg;
+            g_regions = rg;
+            opt.o.regions = rg;
+            break;
+        }
         default: std::exit(EXIT_FAILURE);
         }
     }
@@ -590,6 +641,7 @@ int main(int argc, char** argv)
             HCHECK(hipStreamSynchronize(s.stream), "D2H");
         });
         CHECK(sid_select_mark(h_code, n, opt.o.select), "select");   // --only: the other labels' sites get no record
+        CHECK(sid_regions_mark(regions, sites, 0, n, h_code), "regions");   // --regions: nor the sites outside
         const size_t BLOCK = 1u << 18;
         const size_t nblocks = (n + BLOCK - 1) / BLOCK;
         std::vector<std::vector<char>> bufs(nblocks);

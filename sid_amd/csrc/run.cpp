@@ -914,6 +914,7 @@ extern "C" int sid_engine_create(const sid_opts* opts, const sid_engine_cfg* cfg
         });
         int rc = sid_create(d->device, &e->opts, &d->ctx);
         d->ws.select = e->opts.select;   // (the formatters that take no context: sid_chunk_fmt_len / _put)
+        if (rc == SID_OK && d->ctx->has_regions) d->ws.regions = &d->ctx->regtab;   // (likewise: the context's copy)
         qs.join();
         if (rc == SID_OK && x != hipSuccess) rc = sid_set_hip_error(x);
         rcs[i] = rc;
@@ -927,6 +928,7 @@ extern "C" int sid_engine_create(const sid_opts* opts, const sid_engine_cfg* cfg
         for (auto& t : th) t.join();
     }
     (void)hipSetDevice(e->devs[0]->device);
+    e->opts.regions = nullptr;   // (every context holds its own copy: the caller may free the object now)
     for (int rc : rcs)
         if (rc != SID_OK) {
             sid_engine_destroy(e);

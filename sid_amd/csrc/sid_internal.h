@@ -43,6 +43,22 @@ struct sid_local_ws {
 #define SID_STR_BYTES 32   // entry: [0] tail length, [1] het, [8..32) the tail, zero-padded
 #define SID_STR_TEXT 8
 
+// A region set as the device kernels search it (sid_opts.regions; regions.h
+// has the layout): the chroms sorted by (c8, clen, bytes) -- the form a
+// formatter's Head{clen, c8, cb} carries -- each with its range [ibeg[k],
+// ibeg[k + 1]) of the sorted, disjoint intervals (start[j] < pos <= end[j]).
+// One device buffer per context, built by sid_create.
+struct sid_regtab {
+    const uint64_t* c8 = nullptr;
+    const uint32_t* clen = nullptr;
+    const uint32_t* noff = nullptr;   // the name's offset in `names` (read for names over 8 bytes)
+    const uint32_t* ibeg = nullptr;
+    const int32_t* start = nullptr;
+    const int32_t* end = nullptr;
+    const char* names = nullptr;
+    uint32_t nc = 0, ni = 0;
+};
+
 struct sid_timing_ev {
     hipEvent_t start, mid, end;
 };
@@ -104,6 +120,10 @@ struct sid_ctx {
     uint32_t cdf_k = 0;
     double cdf_mean = -1.0;
     sid_local_ws ws;
+    // the region set (sid_opts.regions, copied: opts.regions is null afterwards)
+    bool has_regions = false;
+    char* d_regions = nullptr;   // the table's device buffer
+    sid_regtab regtab;
     // measurement (sid_timing_enable / sid_timing_read)
     int timing = 0;
     std::vector<sid_timing_ev> ev_pool, ev_pending;
@@ -179,6 +199,7 @@ struct sid_chunk_ws {
     uint64_t tile_ntp = 0;
     int select = 0;               // the owner's sid_opts.select, for the formatters that take no context
                                   // (sid_chunk_fmt_len / _put); set once by the owner
+    const sid_regtab* regions = nullptr;   // likewise the owner's region set (its context's regtab), or null
 };
 int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites);
 void sid_chunk_release(sid_chunk_ws* W);

@@ -2799,9 +2799,12 @@ __device__ __noinline__ void miss_put(const char* text, uint64_t len, Head h, ui
 // SEL (sid_local_put_sel_kernel): a selection by label (xm: sel_word) -- a
 // SID_CLS_SKIP word, a class of another label or a fix-up site of another
 // label has no record (as the length kernels counted)
-// (the body shared by the two kernels below: the one without a selection keeps
+// (the body shared by the kernels below: the one without a selection keeps
 // its parameters and its code)
-template <bool CLS, bool WV, bool SEL>
+// SEL 2 (sid_local_put_reg_kernel): a selection by region -- the same tests,
+// on the words and codes sid_region_mark_kernel marked, with out-of-line
+// helpers of its own (TAG 2)
+template <bool CLS, bool WV, int SEL>
 __device__ __forceinline__ void local_put_body(const char* __restrict__ text, uint64_t len,
                                                            const sid_off_t* __restrict__ starts,
                                                            const uint64_t* __restrict__ hdr, uint64_t n,
@@ -2969,7 +2972,7 @@ __global__ __launch_bounds__(FTB, SID_PUT_WAVES) void sid_local_put_kernel(const
                                                            const uint64_t* __restrict__ boff, const uint64_t* state,
                                                            unsigned long long* lb, char* __restrict__ out)
 {
-    local_put_body<CLS, WV, false>(text, len, starts, hdr, n, tcnt, cap, cdiv, twv, nwv, counts, cwords, str1, str2, code, hom, het, ct, boff,
+    local_put_body<CLS, WV, 0>(text, len, starts, hdr, n, tcnt, cap, cdiv, twv, nwv, counts, cwords, str1, str2, code, hom, het, ct, boff,
                                    state, lb, out, 0u);
 }
 
@@ -2989,8 +2992,36 @@ __global__ __launch_bounds__(FTB, SID_PUT_WAVES) void sid_local_put_sel_kernel(c
                                                            const uint64_t* __restrict__ boff, const uint64_t* state,
                                                            unsigned long long* lb, char* __restrict__ out, uint32_t xm)
 {
-    local_put_body<CLS, WV, true>(text, len, starts, hdr, n, tcnt, cap, cdiv, twv, nwv, counts, cwords, str1, str2, code, hom, het, ct, boff,
+    local_put_body<CLS, WV, 1>(text, len, starts, hdr, n, tcnt, cap, cdiv, twv, nwv, counts, cwords, str1, str2, code, hom, het, ct, boff,
                                    state, lb, out, xm);
+}
+
+// With a region set: the groups whose record bytes (their block sums) reach
+// `lo`; the sparse writer below takes the others (both read the sum, one
+// block-uniform load, and skip the other's groups).
+template <bool CLS, bool WV = false>
+__global__ __launch_bounds__(FTB, SID_PUT_WAVES) void sid_local_put_reg_kernel(const char* __restrict__ text, uint64_t len,
+                                                           const sid_off_t* __restrict__ starts,
+                                                           const uint64_t* __restrict__ hdr, uint64_t n,
+                                                           const uint32_t* __restrict__ tcnt, uint32_t cap,
+                                                           SlotDiv cdiv, const ulonglong2* __restrict__ twv,
+                                                           uint32_t nwv, const uint64_t* __restrict__ counts,
+                                                           const uint32_t* __restrict__ cwords,
+                                                           const char* __restrict__ str1,
+                                                           const char* __restrict__ str2,
+                                                           const uint8_t* __restrict__ code,
+                                                           const double* __restrict__ hom,
+                                                           const double* __restrict__ het, CType ct,
+                                                           const uint32_t* __restrict__ bsum, uint32_t lo,
+                                                           const uint64_t* __restrict__ boff, const uint64_t* state,
+                                                           unsigned long long* lb, char* __restrict__ out, uint32_t xm)
+{
+    if (bsum[blockIdx.x] < lo) {   // (block-uniform)
+        if (blockIdx.x == 0 && threadIdx.x == 0) lb[4] = state[4];
+        return;
+    }
+    local_put_body<CLS, WV, 2>(text, len, starts, hdr, n, tcnt, cap, cdiv, twv, nwv, counts, cwords, str1, str2, code, hom, het, ct, boff,
+                               state, lb, out, xm);
 }
 
 // The sparse -m local writer over the tile parse's slots, for a selection
@@ -3071,6 +3102,81 @@ __global__ __launch_bounds__(FTB) void sid_local_put_sparse_kernel(const char* _
         char* const dst = out + boff[b] + my;
         if (l && tab) record_put_tail<1>(text, len, h, c, ea, eb, dst);
         else if (l) miss_put<1>(text, len, h, c, hom[i], het[i], ct, dst);
+    }
+}
+
+// The same writer under a region set, a copy of its own (the kernel above keeps
+// its code): only the groups sid_local_put_reg_kernel leaves, those with fewer
+// than `hi` record bytes, and out-of-line helpers of its own (TAG 2).
+template <bool WV>
+__global__ __launch_bounds__(FTB) void sid_local_put_reg_sparse_kernel(const char* __restrict__ text, uint64_t len,
+                                                                  const uint64_t* __restrict__ hdr, uint64_t n,
+                                                                  const uint32_t* __restrict__ tcnt, uint32_t cap,
+                                                                  SlotDiv cdiv, const ulonglong2* __restrict__ twv,
+                                                                  uint32_t nwv, const uint32_t* __restrict__ cwords,
+                                                                  const char* __restrict__ str1,
+                                                                  const char* __restrict__ str2,
+                                                                  const uint8_t* __restrict__ code,
+                                                                  const double* __restrict__ hom,
+                                                                  const double* __restrict__ het, CType ct,
+                                                                  const uint32_t* __restrict__ bsum,
+                                                                  const uint64_t* __restrict__ boff,
+                                                                  const uint64_t* state, unsigned long long* lb,
+                                                                  char* __restrict__ out, uint32_t xm, uint32_t hi)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) lb[4] = state[4];
+    const uint64_t nb = (n + FTB - 1) / FTB;
+    for (int it = 0; it < SPB; ++it) {
+        const uint64_t b = (uint64_t)blockIdx.x * SPB + it;
+        if (b >= nb) break;
+        const uint32_t bs = bsum[b];   // (block-uniform: one address)
+        if (bs == 0 || bs >= hi) continue;
+        const uint64_t i = b * FTB + threadIdx.x;
+        int l = 0;
+        Head h{0, 0, 0, 0};
+        uint4 ea = make_uint4(0, 0, 0, 0), eb = ea;
+        bool tab = false;
+        uint8_t c = 0;
+        if (i < n) {
+            const uint32_t w = cwords[i];
+            const uint32_t t = slot_tile((uint32_t)i, cdiv);
+            const uint32_t j = (uint32_t)i - __umul24(t, cap);
+            if (j < tcnt[t] && w != SID_CLS_SKIP) {
+                if (WV && cls_compact(w)) {   // (the entry: tile_wave_store)
+                    const ulonglong2 te = twv[__umul24(t, nwv) + (j >> 6)];
+                    const uint32_t dp = (w >> 20) & (SID_CLS_DPOS - 1);
+                    h.clen = (uint32_t)(te.y >> 32) & 0xFFFu;
+                    h.pos = (int32_t)((uint32_t)te.y + dp);
+                    h.c8 = te.x;
+                    h.cb = 0;
+                } else {
+                    Reader R{text, len};
+                    h = slot_head(R, *(const ulonglong2*)(hdr + 2 * i));
+                }
+                if (w != SID_CLS_MISS) {
+                    const uint32_t k = w & 0xFFFFFu;
+                    const uint4* e = (const uint4*)(k < SID_TAB_N ? str1 + (size_t)k * SID_STR_BYTES
+                                                                  : str2 + (size_t)(k - SID_TAB_N) * SID_STR_BYTES);
+                    ea = e[0];
+                    eb = e[1];
+                    tab = (ea.x & 0xFFu) != 0xFFu;
+                }
+                if (tab) {
+                    const uint32_t f = (w >> 28) & 3u, s2 = w >> 30;
+                    const bool het_l = (ea.x >> 8) & 1u;
+                    c = (uint8_t)(f | ((het_l ? s2 : f) << 2) | (het_l ? 0x80u : 0u));
+                    l = code_out(c, xm) ? 0 : local_rec_len(h, ea.x & 0xFFu);
+                } else {   // the fix-up's site
+                    c = code[i];
+                    l = code_out(c, xm) ? 0 : miss_len<2>(h, c, hom[i], het[i], ct);
+                }
+            }
+        }
+        uint32_t tot;
+        const uint32_t my = block_exscan<FTB>((uint32_t)l, &tot);
+        char* const dst = out + boff[b] + my;
+        if (l && tab) record_put_tail<2>(text, len, h, c, ea, eb, dst);
+        else if (l) miss_put<2>(text, len, h, c, hom[i], het[i], ct, dst);
     }
 }
 
@@ -3317,6 +3423,297 @@ __global__ __launch_bounds__(FTB) void sid_lynch_put_sparse_kernel(const char* _
         if (l) lynch_put_global<1>(text, len, h, e0, e1, e2, e3, out + boff[b] + my);
     }
 }
+
+// ---------------------------------------------------------------- regions --
+// The selection by region (sid_opts.regions; sid_regtab): a site is inside
+// when the set holds its chrom, byte for byte, and an interval with start <
+// pos <= end.  One kernel per formatter family marks the sites outside with
+// the marker that family's length kernel and writer already honour:
+//   -m local (class words)      SID_CLS_SKIP in the slot's / site's word
+//   likelihood_ratio / bayes    the site's counts zeroed (coverage 0: the
+//                               class lookup gives it no record)
+//   code / confs formatters     SID_CODE_DROPPED in the formatter's codes
+// It runs after the call (the Lynch paths: after pass 1's histogram, on pass
+// 2's parse) and before the scan of the block sums.  Where the record lengths
+// come after it (Lynch, code / confs) marking is all; where they came out of
+// the parse (-m local) the block recomputes its 512-slot group's sum from the
+// sites it kept -- one block owns one group, so a plain reduction -- and only
+// when it dropped one (a whole-chromosome set costs the test alone).
+//
+// The search uses the input's order: a wave's first site (its leader) looks
+// its chrom up in the sorted chrom table and its position in the chrom's
+// intervals (binary searches, ~log2 of the table dependent loads); a lane of
+// the same chrom at or past the leader's position walks a few intervals on
+// from the leader's, else searches its chrom's range; a lane of another
+// chrom searches in full.  Any order is correct, only slower.
+// (Measured per 50M-site C2 step with 4167 intervals: every lane walking on
+// from the leader's interval by loads of its own, after the leader's
+// 12-load binary search, 0.87 ms; the leader's search by the whole wave and
+// its interval and the next broadcast, so that nearly every lane decides
+// without a load)
+__device__ __forceinline__ uint64_t reg_c8(Reader& R, const Head& h)
+{
+    if (h.c8 || h.clen == 0) return h.clen >= 8 ? h.c8 : h.c8 & ((1ull << (8 * h.clen)) - 1ull);
+    uint64_t v = 0;
+    const uint32_t m = min(h.clen, 8u);
+    for (uint32_t k = 0; k < m; ++k) v |= (uint64_t)R.at(h.cb + k) << (8 * k);
+    return v;
+}
+
+// bytes [8, clen) of the site's chrom against those of the set's chrom k (of the same length)
+__device__ __noinline__ bool reg_name_eq(const char* text, uint64_t len, uint64_t cb, uint32_t clen, const char* nm)
+{
+    Reader R{text, len};
+    for (uint32_t j = 8; j < clen; ++j)
+        if (R.at(cb + j) != (uint32_t)(uint8_t)nm[j]) return false;
+    return true;
+}
+
+// the set's chrom equal to the site's: its index, or -1
+__device__ __forceinline__ int32_t reg_chrom(Reader& R, const Head& h, uint64_t c8, const sid_regtab& T)
+{
+    uint32_t lo = 0, hi = T.nc;
+    while (lo < hi) {   // the first chrom with (c8, clen) >= the site's
+        const uint32_t mid = (lo + hi) >> 1;
+        const uint64_t m8 = T.c8[mid];
+        if (m8 < c8 || (m8 == c8 && T.clen[mid] < h.clen)) lo = mid + 1;
+        else hi = mid;
+    }
+    for (; lo < T.nc && T.c8[lo] == c8 && T.clen[lo] == h.clen; ++lo)
+        if (h.clen <= 8 || reg_name_eq(R.text, R.limit, h.cb, h.clen, T.names + T.noff[lo])) return (int32_t)lo;
+    return -1;
+}
+
+// the first interval of [lo, hi) with end >= pos (the only one that can hold pos)
+__device__ __forceinline__ uint32_t reg_lower(const int32_t* __restrict__ end, uint32_t lo, uint32_t hi, int32_t pos)
+{
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (end[mid] < pos) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The same bound for a wave-uniform (lo, hi, pos), by all 64 lanes together:
+// each round every lane probes the last interval of its 64th of the range, so
+// a round divides the range by 64 (two dependent loads for 4096 intervals,
+// three for 250,000, where a lane alone takes 12 and 18).  The last round's
+// lanes hold the intervals themselves: the found one and the next come back
+// in iv = {start, end, next start, next end} without another round trip (none:
+// INT32_MAX, which no position is above).  Every lane of the wave calls it,
+// in uniform control flow.
+__device__ __forceinline__ uint32_t reg_lower_wave(const int32_t* __restrict__ start, const int32_t* __restrict__ end,
+                                                   uint32_t lo, uint32_t hi, int32_t pos, int32_t (&iv)[4])
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t top = hi;
+    iv[0] = iv[1] = iv[2] = iv[3] = INT32_MAX;
+    while (hi - lo > 64) {   // (wave-uniform)
+        const uint32_t n = hi - lo, step = (n + 63) >> 6;
+        const uint32_t last = min(lo + (lane + 1) * step, hi) - 1;   // (lo + lane step < hi for the lanes that count)
+        const bool ge = lo + lane * step < hi && end[last] >= pos;
+        const uint64_t m = __ballot(ge);
+        if (!m) return top;
+        const uint32_t seg = (uint32_t)__ffsll((unsigned long long)m) - 1;
+        hi = min(lo + (seg + 1) * step, hi);
+        lo = lo + seg * step;
+    }
+    const bool v = lo + lane < hi;
+    const int32_t ev = v ? end[lo + lane] : INT32_MAX, sv = v ? start[lo + lane] : INT32_MAX;
+    const uint64_t m = __ballot(v && ev >= pos);
+    if (!m) return top;
+    const uint32_t f = (uint32_t)__ffsll((unsigned long long)m) - 1, idx = lo + f;
+    iv[0] = __shfl(sv, (int)f, 64);
+    iv[1] = __shfl(ev, (int)f, 64);
+    if (idx + 1 < hi) {   // (wave-uniform) the next one is in a lane too (f + 1 < 64: the window holds at most 64)
+        iv[2] = __shfl(sv, (int)f + 1, 64);
+        iv[3] = __shfl(ev, (int)f + 1, 64);
+    } else if (idx + 1 < top) {
+        iv[2] = start[idx + 1];
+        iv[3] = end[idx + 1];
+    }
+    return idx;
+}
+
+__device__ __forceinline__ uint64_t shfl64(uint64_t x, int src)
+{
+    return ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(x >> 32), src, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)x, src, 64);
+}
+
+// every lane of the wave calls it (site: the lane holds one, h its chrom and position)
+__device__ __forceinline__ bool reg_inside(Reader& R, const Head& h, bool site, const sid_regtab& T)
+{
+    const uint64_t act = __ballot(site);
+    if (!act) return false;   // (wave-uniform)
+    const int lead = __ffsll((unsigned long long)act) - 1;
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool is_lead = (int)lane == lead;
+    const uint64_t c8 = site ? reg_c8(R, h) : 0;
+    const uint64_t c8L = shfl64(c8, lead), cbL = shfl64(h.cb, lead);
+    const uint32_t clenL = (uint32_t)__shfl((int)h.clen, lead, 64);
+    const int32_t posL = __shfl(h.pos, lead, 64);
+    // the leader's chrom and its interval range
+    int32_t kL = -1;
+    uint32_t ibL = 0, ieL = 0;
+    if (T.nc <= 64) {   // (wave-uniform) a lane per chrom of the set: one round trip
+        const bool v = lane < T.nc;
+        const uint64_t m8 = v ? T.c8[lane] : 0;
+        const uint32_t ml = v ? T.clen[lane] : 0, b0 = v ? T.ibeg[lane] : 0, b1 = v ? T.ibeg[lane + 1] : 0;
+        bool hit = v && m8 == c8L && ml == clenL;
+        if (hit && clenL > 8) hit = reg_name_eq(R.text, R.limit, cbL, clenL, T.names + T.noff[lane]);
+        const uint64_t hm = __ballot(hit);
+        if (hm) {
+            kL = __ffsll((unsigned long long)hm) - 1;
+            ibL = (uint32_t)__shfl((int)b0, kL, 64);
+            ieL = (uint32_t)__shfl((int)b1, kL, 64);
+        }
+    } else {
+        int32_t k1 = -1;
+        if (is_lead) k1 = reg_chrom(R, h, c8, T);
+        kL = __shfl(k1, lead, 64);
+        if (kL >= 0) ibL = T.ibeg[kL], ieL = T.ibeg[kL + 1];
+    }
+    // the leader's interval (the first of its chrom with end >= its position) and the next one, for every lane
+    int32_t iv[4] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MAX};
+    uint32_t idxL = 0;
+    if (kL >= 0) idxL = reg_lower_wave(T.start, T.end, ibL, ieL, posL, iv);   // (wave-uniform)
+    if (!site) return false;
+    bool same = is_lead || (c8 == c8L && h.clen == clenL);
+    if (same && !is_lead && h.clen > 8)
+        same = kL >= 0 && reg_name_eq(R.text, R.limit, h.cb, h.clen, T.names + T.noff[kL]);
+    const int32_t k = same ? kL : reg_chrom(R, h, c8, T);
+    if (k < 0) return false;
+    if (same && h.pos >= posL) {   // at or past the leader: its interval, the next, or a search on from there
+        if (h.pos <= iv[1]) return iv[0] < h.pos;
+        if (h.pos <= iv[3]) return iv[2] < h.pos;
+        if (idxL + 2 >= ieL) return false;
+        const uint32_t idx = reg_lower(T.end, idxL + 2, ieL, h.pos);
+        return idx < ieL && T.start[idx] < h.pos;
+    }
+    const uint32_t ib = T.ibeg[k], ie = T.ibeg[k + 1];
+    const uint32_t idx = reg_lower(T.end, ib, ie, h.pos);
+    return idx < ie && T.start[idx] < h.pos;
+}
+
+enum { REG_TILE = 0, REG_DENSE = 1, REG_LYNCH = 2, REG_CODE = 3 };
+template <class Off>
+struct RegArgs {
+    const char* text;
+    uint64_t len;
+    const Off* starts;            // (not the tile layout)
+    const uint64_t* hdr;          // header pairs (REG_CODE: or null)
+    uint64_t s0, s1;              // the sites (REG_TILE: slots) [s0, s1), block b from s0 + b FTB
+    const uint32_t* tcnt;         // REG_TILE: the slot layout (local_put_body)
+    uint32_t cap;
+    SlotDiv cdiv;
+    const ulonglong2* twv;
+    uint32_t nwv;
+    uint32_t* cls;                // -m local: the class words (REG_DENSE with OPT: written here from the counts)
+    uint64_t* counts;
+    uint8_t* code;
+    const double* hom;
+    const double* het;
+    CType ct;
+    uint32_t xm;                  // sel_word: the selection by label
+    const uint8_t* len1;          // -m local: the tail lengths the length pass used
+    const uint8_t* len2;
+    uint32_t* bsum;               // -m local: the groups' record bytes
+    sid_regtab T;
+};
+
+// MODE REG_TILE: OPT = the lane shape (compact words and wave entries);
+// REG_DENSE: OPT = no class words yet (the length kernel read the counts:
+// long lines, or pass 2 of -R -m local on the kept parse), this kernel writes
+// them for the writer
+template <int MODE, bool OPT, class Off>
+__global__ __launch_bounds__(FTB) void sid_region_mark_kernel(const RegArgs<Off> A)
+{
+    const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
+    Reader R{A.text, A.len};
+    bool site = i < A.s1;
+    Head h{0, 0, 0, 0};
+    uint32_t w = 0;
+    if (MODE == REG_TILE) {
+        if (site) {
+            w = A.cls[i];
+            const uint32_t t = slot_tile((uint32_t)i, A.cdiv);
+            const uint32_t j = (uint32_t)i - __umul24(t, A.cap);
+            // (the wave's entry loaded beside the word, not after it: one round trip, as the writer's)
+            ulonglong2 te = make_ulonglong2(0, 0);
+            if (OPT) te = A.twv[__umul24(t, A.nwv) + (j >> 6)];
+            site = j < A.tcnt[t] && w != SID_CLS_SKIP;
+            if (site) {
+                if (OPT && cls_compact(w)) {   // (the entry: tile_wave_store)
+                    h.clen = (uint32_t)(te.y >> 32) & 0xFFFu;
+                    h.pos = (int32_t)((uint32_t)te.y + ((w >> 20) & (SID_CLS_DPOS - 1)));
+                    h.c8 = te.x;
+                } else {
+                    h = slot_head(R, *(const ulonglong2*)(A.hdr + 2 * i));
+                }
+            }
+        }
+    } else if (MODE == REG_DENSE) {
+        if (site) {
+            if (OPT) {
+                const LocalLen LL{A.len1, A.len2, nullptr, nullptr, nullptr, nullptr};
+                (void)local_site_word<true>(A.counts[i], A.len1, LL, &w);
+                A.cls[i] = w;
+            } else {
+                w = A.cls[i];
+            }
+            site = w != SID_CLS_SKIP;
+            if (site) h = site_head(R, A.starts + i, A.hdr + 2 * i);
+        }
+    } else {
+        if (MODE == REG_CODE && site) site = !code_out(A.code[i], A.xm);   // (no record anyway)
+        if (site) h = site_head(R, A.starts + i, A.hdr ? A.hdr + 2 * i : nullptr);
+    }
+    const bool in = reg_inside(R, h, site, A.T);
+    const bool drop = site && !in;
+    if (MODE == REG_LYNCH) {
+        if (drop) A.counts[i] = 0;
+        return;
+    }
+    if (MODE == REG_CODE) {
+        if (drop) A.code[i] |= SID_CODE_DROPPED;
+        return;
+    }
+    if (!__syncthreads_or(drop)) return;   // nothing dropped: the group's sum stands
+    // nothing kept (most groups of an exon-like set): a group without bytes, which both writers pass over
+    // on its sum alone -- its words stay unmarked and unread (195 MB of stores a 50M-site step otherwise)
+    if (!__syncthreads_or(site && in)) {
+        if (threadIdx.x == 0) A.bsum[blockIdx.x] = 0;
+        return;
+    }
+    if (drop) A.cls[i] = SID_CLS_SKIP;
+    int l = 0;
+    if (site && in) {
+        if (w == SID_CLS_MISS) {   // the fix-up's site
+            const uint8_t c = A.code[i];
+            l = code_out(c, A.xm) ? 0 : miss_len<2>(h, c, A.hom[i], A.het[i], A.ct);
+        } else {
+            const uint32_t k = w & 0xFFFFFu;
+            const uint32_t L = k < SID_TAB_N ? A.len1[k] : A.len2[k - SID_TAB_N];
+            l = L && L != 0xFFu ? local_rec_len(h, L) : 0;
+        }
+    }
+    const uint32_t tot = block_sum<FTB>((uint32_t)l);
+    if (threadIdx.x == 0) A.bsum[blockIdx.x] = tot;
+}
+
+template <int MODE, bool OPT, class Off>
+static void launch_region_mark(const RegArgs<Off>& A, hipStream_t st)
+{
+    const uint64_t nb = (A.s1 - A.s0 + FTB - 1) / FTB;
+    if (nb) sid_region_mark_kernel<MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(A);
+}
+
+// The writer of a 512-slot group of -m local's tile layout under a region
+// set, by the group's record bytes: from REG_LDS_MIN on the LDS assembly
+// (16-B stores; a full group holds ~22 KB), below it the sparse writer's byte
+// stores (an exon-like set leaves most groups empty or with a few records).
+constexpr uint32_t REG_LDS_MIN = 2048;
 
 // tails of the U classes (one thread each), then the dense codes' lengths
 __global__ __launch_bounds__(256) void sid_lynch_str_kernel(const uint8_t* __restrict__ pcode,
@@ -3870,6 +4267,19 @@ extern "C" int sid_dtext_format(sid_ctx* ctx, const sid_dtext* T, size_t begin, 
     hip(hipMalloc(&d_boff, (nb + 1) * 8));
     hip(hipMalloc(&d_base, 8));
     hip(hipMalloc(&d_bad, 4));
+    // a region set: the sites outside get the "no record" bit in a copy of the
+    // codes (the caller's array stays as it is; indexed by site like it, so `end`
+    // bytes of which [begin, end) are used)
+    uint8_t* d_rcode = nullptr;
+    if (rc == SID_OK && nb && ctx->has_regions && hip(hipMalloc(&d_rcode, end)) &&
+        hip(hipMemcpyAsync(d_rcode + begin, d_code + begin, n, hipMemcpyDeviceToDevice, st))) {
+        RegArgs<uint64_t> A{};
+        A.text = T->d_text, A.len = T->len, A.starts = T->d_starts, A.hdr = T->d_hdr, A.s0 = begin, A.s1 = end;
+        A.code = d_rcode, A.xm = sel_word(ctx->opts.select), A.T = ctx->regtab;
+        launch_region_mark<REG_CODE, false>(A, st);
+        hip(hipGetLastError());
+        d_code = d_rcode;
+    }
     if (rc == SID_OK && nb) {
         hip(hipMemsetAsync(d_bad, 0, 4, st));
         hip(hipMemsetAsync(d_base, 0, 8, st));
@@ -3935,7 +4345,7 @@ extern "C" int sid_dtext_format(sid_ctx* ctx, const sid_dtext* T, size_t begin, 
     for (int b = 0; b < 2; ++b) (void)hipEventDestroy(done[b]);
     (void)hipEventDestroy(written);
     (void)hipStreamDestroy(cs);
-    for (void* p : {(void*)d_bsum, (void*)d_boff, (void*)d_base, (void*)d_bad})
+    for (void* p : {(void*)d_bsum, (void*)d_boff, (void*)d_base, (void*)d_bad, (void*)d_rcode})
         if (p) (void)hipFree(p);
     return rc;
 }
@@ -4135,9 +4545,11 @@ void sid_chunk_release(sid_chunk_ws* W)
                     (void*)W->bsum, (void*)W->boff, (void*)W->tcnt, (void*)W->toff, (void*)W->state,
                     (void*)W->hdr, (void*)W->fb, (void*)W->masks, (void*)W->lb, (void*)W->cls, (void*)W->twv})
         if (p) (void)hipFree(p);
-    const int select = W->select;   // (the owner's option, not the buffers')
+    const int select = W->select;   // (the owner's options, not the buffers')
+    const sid_regtab* regions = W->regions;
     *W = sid_chunk_ws{};
     W->select = select;
+    W->regions = regions;
 }
 
 // blocks of the strided index kernels (count kernel, index stage per 50M
@@ -4250,6 +4662,12 @@ int sid_chunk_fmt_len(sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n
     if (n > W->site_cap) return SID_EINVAL;
     WCHECK(hipMemsetAsync(W->lb, 0, 8 * 8, st));
     const uint64_t nb = (n + FTB - 1) / FTB;
+    if (W->regions) {   // the sites outside the region set: dropped in the workspace's codes
+        RegArgs<sid_off_t> A{};
+        A.text = base, A.len = c1, A.starts = W->starts, A.hdr = W->hdr, A.s1 = n, A.code = W->code;
+        A.xm = sel_word(W->select), A.T = *W->regions;
+        launch_region_mark<REG_CODE, false>(A, st);
+    }
     if (nb) sid_fmt_blen_kernel<<<(unsigned)nb, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->code, W->hom,
                                                               W->het, ct, W->bsum, W->lb, sel_word(W->select));
     WCHECK(hipGetLastError());
@@ -4304,6 +4722,19 @@ int sid_chunk_local_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
         sid_local_fixlen_kernel<false><<<64, TB, 0, st>>>(base, c1, W->starts, W->hdr, W->counts, miss, W->lb, ctx->K,
                                                    ctx->d_lnt, ct, W->code, W->hom, W->het, W->bsum, W->lb,
                                                    sel_word(ctx->opts.select));
+        if (ctx->has_regions) {
+            // the sites outside the region set: the skip word, and their groups' sums again.  Without class
+            // words (the length kernel read the counts) the kernel writes them, for the writer
+            RegArgs<sid_off_t> A{};
+            A.text = base, A.len = c1, A.starts = W->starts, A.hdr = W->hdr, A.s1 = n, A.cls = W->cls;
+            A.counts = W->counts, A.code = W->code, A.hom = W->hom, A.het = W->het, A.ct = ct;
+            A.xm = sel_word(ctx->opts.select);
+            A.len1 = local_sel(ctx) ? ctx->ws.len1f : ctx->ws.len1, A.len2 = local_sel(ctx) ? ctx->ws.len2f : ctx->ws.len2;
+            A.bsum = W->bsum, A.T = ctx->regtab;
+            if (W->cls_ready) launch_region_mark<REG_DENSE, false>(A, st);
+            else launch_region_mark<REG_DENSE, true>(A, st);
+            W->cls_ready = true;
+        }
     }
     W->lens_ready = false;
     WCHECK(hipGetLastError());
@@ -4324,6 +4755,21 @@ int sid_chunk_local_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
         if (W->slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (slot_tile's exact range: a 4 GiB chunk has fewer)
         const SlotDiv cdiv = slot_div(W->slot_cap);
         const uint32_t xm = sel_word(ctx->opts.select);
+        if (ctx->has_regions) {   // per group, by its record bytes (REG_LDS_MIN): the LDS assembly or the byte stores
+            auto put = W->tile_quad ? sid_local_put_reg_kernel<true, false> : sid_local_put_reg_kernel<true, true>;
+            put<<<(unsigned)nbs, FTB, 0, st>>>(base, c1, nullptr, W->hdr, W->slots, W->tcnt, W->slot_cap, cdiv, W->twv,
+                                               tile_nwv(W->slot_cap), W->counts, W->cls, ctx->ws.str1, ctx->ws.str2,
+                                               W->code, W->hom, W->het, ct, W->bsum, REG_LDS_MIN, W->boff, W->state, W->lb,
+                                               out, xm);
+            auto sput = W->tile_quad ? sid_local_put_reg_sparse_kernel<false> : sid_local_put_reg_sparse_kernel<true>;
+            sput<<<(unsigned)((nbs + SPB - 1) / SPB), FTB, 0, st>>>(base, c1, W->hdr, W->slots, W->tcnt, W->slot_cap,
+                                                                    cdiv, W->twv, tile_nwv(W->slot_cap), W->cls,
+                                                                    ctx->ws.str1, ctx->ws.str2, W->code, W->hom, W->het,
+                                                                    ct, W->bsum, W->boff, W->state, W->lb, out, xm,
+                                                                    REG_LDS_MIN);
+            WCHECK(hipGetLastError());
+            return SID_OK;
+        }
         if (ctx->opts.select == SID_SELECT_HET) {
             // about a site in a thousand: the sparse writer (hom keeps nearly
             // all: the LDS assembly below, with the skip word honoured)
@@ -4366,7 +4812,13 @@ int sid_chunk_local_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     if (nb == 0) return hipMemcpyAsync(W->lb + 4, W->state + 4, 8, hipMemcpyDeviceToDevice, st) == hipSuccess
                             ? SID_OK : SID_EHIP;
     const uint32_t* cw = W->cls_ready ? W->cls : nullptr;
-    if (sel) {
+    if (ctx->has_regions) {   // (the class words: the parse's, or the region kernel's; the groups with a record)
+        if (!cw) return SID_ESTATE;
+        sid_local_put_reg_kernel<true><<<(unsigned)nb, FTB, 0, st>>>(
+            base, c1, W->starts, W->hdr, n, nullptr, 0, SlotDiv{0, 0}, nullptr, 0, W->counts, cw, ctx->ws.str1,
+            ctx->ws.str2, W->code, W->hom, W->het, ct, W->bsum, 1u, W->boff, W->state, W->lb, out,
+            sel_word(ctx->opts.select));
+    } else if (sel) {
         auto put = W->cls_ready ? sid_local_put_sel_kernel<true> : sid_local_put_sel_kernel<false>;
         put<<<(unsigned)nb, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, nullptr, 0, SlotDiv{0, 0}, nullptr, 0,
                                           W->counts, cw, ctx->ws.str1, ctx->ws.str2, W->code, W->hom, W->het, ct,
@@ -4443,6 +4895,7 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
     const uint64_t slots = ntp * cap;
     if (slots > W->site_cap || ntp > W->tile_cap || slots >= (1ull << 32)) return SID_EINVAL;
     if (ntp * tile_nwv(cap) > W->site_cap / 32 + 1) return SID_EINVAL;   // (never: cap >= 64)
+    if (ctx->has_regions && slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (the region kernel's slot_tile: its exact range, as the writer's)
     W->lens_ready = false;
     W->cls_ready = false;
     W->slot_cap = cap;
@@ -4466,6 +4919,15 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
     auto serial = sel ? sid_tile_serial_kernel<true, true> : sid_tile_serial_kernel<true>;
     serial<<<TILE_SERIAL_GRID, TB, 0, st>>>(base, c1, W->fb, W->starts, W->lb, W->tcnt, ntp, cap, W->counts, W->hdr,
                                             (unsigned long long*)(W->state + 4), F);
+    if (ctx->has_regions) {   // the slots outside the region set: the skip word, and their groups' sums again
+        RegArgs<sid_off_t> A{};
+        A.text = base, A.len = c1, A.hdr = W->hdr, A.s1 = slots, A.tcnt = W->tcnt, A.cap = cap, A.cdiv = slot_div(cap);
+        A.twv = W->twv, A.nwv = tile_nwv(cap), A.cls = W->cls, A.code = W->code, A.hom = W->hom, A.het = W->het;
+        A.ct = ct, A.xm = sel_word(ctx->opts.select), A.len1 = LL.len1, A.len2 = LL.len2, A.bsum = W->bsum;
+        A.T = ctx->regtab;
+        if (quad) launch_region_mark<REG_TILE, false>(A, st);
+        else launch_region_mark<REG_TILE, true>(A, st);
+    }
     WCHECK(hipGetLastError());
     W->cls_ready = true;
     return fmt_scan(W, nb, st);
@@ -4527,6 +4989,12 @@ int sid_chunk_lynch_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     if (nb && V.empty) {   // no class: every site dropped (and no length table)
         WCHECK(hipMemsetAsync(W->bsum, 0, nb * 4, st));
     } else if (nb) {
+        if (ctx->has_regions) {   // the sites outside the region set: counts 0, which no class holds
+            RegArgs<sid_off_t> A{};
+            A.text = base, A.len = c1, A.starts = W->starts, A.hdr = W->hdr, A.s1 = n, A.counts = W->counts;
+            A.T = ctx->regtab;
+            launch_region_mark<REG_LYNCH, false>(A, st);
+        }
         (ctx->opts.select == SID_SELECT_HET ? sid_lynch_len_kernel<true> : sid_lynch_len_kernel<false>)
             <<<(unsigned)((nb + LPB - 1) / LPB), FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->counts, V, W->bsum);
     }
