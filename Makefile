@@ -11,8 +11,8 @@ HOSTFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Iinclude
 # EXTRA: A/B variants of the same sources (make BUILD=build_b EXTRA=-DNAME=VALUE)
 HIPFLAGS += $(EXTRA)
 
-KERNELS := local synth lynch textpath
-HOSTSRC := capi lynch_host parse emit regions run
+KERNELS := local synth lynch textpath inflate
+HOSTSRC := capi lynch_host parse emit regions bgzf run
 OBJS := $(KERNELS:%=$(BUILD)/%.o) $(HOSTSRC:%=$(BUILD)/%.o)
 HDRS := include/sid.h $(wildcard $(SRC)/*.h)
 

@@ -79,6 +79,7 @@ enum {
                             dereferences NULL (pileup.cpp:54,158): SIGSEGV          */
     SID_ELINE = 13,      /* a line that makes a chunk span 4 GiB or more (line
                             offsets on the device are 32-bit)                      */
+    SID_EBGZF = 14,      /* not a BGZF file, or a truncated or corrupt BGZF block   */
 };
 const char* sid_strerror(int status);
 int sid_last_hip_error(void);
@@ -152,6 +153,7 @@ int sid_regions_mark(const sid_regions* r, const struct sid_sites* s, size_t beg
 
 /* ------------------------------------------------------------- contexts -- */
 typedef struct sid_ctx sid_ctx;
+struct sid_bgzf;
 int sid_device_count(int* n);
 /* Binds `device` (hipSetDevice) for the calling thread and builds the
  * per-context constant tables (log table, chi-square constants). */
@@ -320,6 +322,41 @@ int sid_format_g6(double v, char* buf, size_t cap);
 int sid_format_g6_device(sid_ctx* ctx, const double* values, size_t n, char* out, void* stream);
 
 
+/* ------------------------------------------------ BGZF input ---------------
+ * Block-compressed gzip (samtools mpileup ... | bgzip): a concatenation of
+ * independent gzip members of at most 64 KiB of text each, the member's size
+ * in its header (BSIZE), the text's size (ISIZE) and CRC32 in its trailer.
+ *
+ * sid_bgzf_index: the members of a byte range, found by hopping over headers
+ *   and trailers (nothing is inflated).  SID_EBGZF and the compressed offset
+ *   of the offending member when the bytes there are no BGZF header (plain
+ *   gzip included), the member is truncated, or its ISIZE exceeds 64 KiB.
+ *   Empty members (the EOF marker) are legal anywhere, a missing EOF marker is
+ *   accepted, len == 0 is a valid empty input.
+ * sid_bgzf_block: member k's compressed offset and size, its text's offset in
+ *   the inflated text and size.
+ * sid_bgzf_inflate_host: every member inflated and its CRC32 checked, on the
+ *   host (no libz).  out == NULL sizes (*out_len); cap too small: SID_ENOMEM
+ *   and a sufficient *out_len.  SID_EBGZF: *err_offset = the bad member's
+ *   compressed offset.
+ * sid_bgzf_inflate_device: members [first_block, first_block + nblocks) of the
+ *   indexed range d_bytes (device memory, the whole range) inflated by the
+ *   GPU, one wave per member, CRC32 checked; member k's text lands at d_out +
+ *   toff(k) - toff(first_block).  cap too small: SID_ENOMEM, nothing launched.
+ *   SID_EBGZF: *err_block = the lowest bad member.  Synchronises.
+ * sid_crc32: zlib's crc32(), by the host build of the device routine. */
+typedef struct sid_bgzf sid_bgzf;
+int sid_bgzf_index(const void* bytes, size_t len, sid_bgzf** out, uint64_t* err_offset);
+size_t sid_bgzf_blocks(const sid_bgzf* z);
+uint64_t sid_bgzf_text_len(const sid_bgzf* z);
+int sid_bgzf_block(const sid_bgzf* z, size_t k, uint64_t* coff, uint32_t* csize, uint64_t* toff, uint32_t* isize);
+void sid_bgzf_free(sid_bgzf* z);
+int sid_bgzf_inflate_host(const void* bytes, size_t len, char* out, size_t cap, size_t* out_len,
+                          uint64_t* err_offset);
+int sid_bgzf_inflate_device(sid_ctx* ctx, const void* d_bytes /* device */, const sid_bgzf* z, size_t first_block,
+                            size_t nblocks, char* d_out /* device */, size_t cap, uint64_t* err_block, void* stream);
+uint32_t sid_crc32(uint32_t crc, const void* p, size_t n);
+
 /* ------------------------------------------------ streaming engine -------
  * The whole path of one sid run -- pileup text in, CSV records out, in file
  * order -- replacing readFile + callX + the output loop (call.cpp:11-20,
@@ -414,6 +451,13 @@ typedef struct {
     uint64_t tile_overflows_queued; /* of those, overflows with the device's next
                                     chunk already popped behind it (its run-ahead
                                     tile parse dropped, the chunk kept)            */
+    uint64_t bgzf_bytes;         /* BGZF sources: the compressed bytes of the members
+                                    uploaded in the first pass, a member that two
+                                    chunks share counted once (h2d_bytes counts it
+                                    twice); empty members outside every chunk (the
+                                    EOF marker) are not uploaded.  bytes_in stays
+                                    the text parsed                                 */
+    uint64_t bgzf_blocks;        /* ... and their number                            */
 } sid_run_stats;
 void sid_engine_cfg_default(sid_engine_cfg* cfg);
 int sid_engine_create(const sid_opts* opts, const sid_engine_cfg* cfg, sid_engine** out);
@@ -437,6 +481,18 @@ int sid_engine_placement(const sid_engine* e, int i, sid_placement* out);
 /* Sources.  The engine keeps the pointer / descriptor until the next source. */
 int sid_engine_source_text(sid_engine* e, const char* text, uint64_t len);          /* host memory */
 int sid_engine_source_file(sid_engine* e, int fd, uint64_t offset, uint64_t len);   /* regular file */
+/* BGZF-compressed pileup text (host memory / a regular file, mapped): the
+ * input is indexed at once (SID_EBGZF and the offending member's compressed
+ * offset in *err_offset when it is not BGZF; the engine then has no source);
+ * chunks are runs of whole members cut at line starts, their compressed bytes
+ * cross the bus and are inflated on the device (sid_bgzf_inflate_device's
+ * kernel) in front of the parse.  A member that does not inflate or fails its
+ * CRC32 makes the ingest return SID_EBGZF, err_offset = its compressed
+ * offset; inside a chunk it wins over a malformed line, across chunks the
+ * earliest chunk in file order wins.  For a parse error err_offset is the
+ * line's offset in the inflated text. */
+int sid_engine_source_bgzf(sid_engine* e, const void* bytes, uint64_t len, uint64_t* err_offset);
+int sid_engine_source_bgzf_file(sid_engine* e, int fd, uint64_t offset, uint64_t len, uint64_t* err_offset);
 /* Text already in HBM on the engine's first device (measurement): d_text must
  * be readable for 256 bytes past len. */
 int sid_engine_source_device_text(sid_engine* e, const char* d_text, uint64_t len);

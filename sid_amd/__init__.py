@@ -30,7 +30,7 @@ METHODS = {"local": METHOD_LOCAL, "likelihood_ratio": METHOD_LIKELIHOOD_RATIO,
 SID_OK = 0
 STATUS = {0: "SID_OK", 1: "SID_EINVAL", 2: "SID_EHIP", 3: "SID_ENOMEM", 4: "SID_EMALFORMED",
           5: "SID_EMISSING_MQ", 6: "SID_ENULLCHROM", 7: "SID_ESTATE", 8: "SID_EBADFUNC",
-          9: "SID_EEMPTY", 10: "SID_EIO", 11: "SID_ERANGE", 12: "SID_ENOBQ", 13: "SID_ELINE"}
+          9: "SID_EEMPTY", 10: "SID_EIO", 11: "SID_ERANGE", 12: "SID_ENOBQ", 13: "SID_ELINE", 14: "SID_EBGZF"}
 
 CODE_HET = 0x80
 CODE_DROPPED = 0x40
@@ -74,7 +74,7 @@ class RunStats(C.Structure):
                 ("emit_s", C.c_double), ("estimate", Estimate), ("chunks_registered", C.c_uint64),
                 ("register_s", C.c_double), ("h2d_s", C.c_double), ("h2d_bytes", C.c_uint64),
                 ("chunks_tiled", C.c_uint64), ("tile_overflows", C.c_uint64),
-                ("tile_overflows_queued", C.c_uint64)]
+                ("tile_overflows_queued", C.c_uint64), ("bgzf_bytes", C.c_uint64), ("bgzf_blocks", C.c_uint64)]
 
 
 class Placement(C.Structure):
@@ -145,6 +145,15 @@ SIGNATURES = [
     ("sid_call_quality", _I, [_P, _P, _P, _P, _P, _P]),
     ("sid_format_g6", _I, [_D, C.c_char_p, _SZ]),
     ("sid_format_g6_device", _I, [_P, _P, _SZ, _P, _P]),
+    ("sid_bgzf_index", _I, [_P, _SZ, C.POINTER(_P), C.POINTER(C.c_uint64)]),
+    ("sid_bgzf_blocks", _SZ, [_P]),
+    ("sid_bgzf_text_len", _U64, [_P]),
+    ("sid_bgzf_block", _I, [_P, _SZ, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                            C.POINTER(C.c_uint32)]),
+    ("sid_bgzf_free", None, [_P]),
+    ("sid_bgzf_inflate_host", _I, [_P, _SZ, _P, _SZ, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+    ("sid_bgzf_inflate_device", _I, [_P, _P, _P, _SZ, _SZ, _P, _SZ, C.POINTER(C.c_uint64), _P]),
+    ("sid_crc32", C.c_uint32, [C.c_uint32, _P, _SZ]),
     ("sid_engine_cfg_default", None, [C.POINTER(EngineCfg)]),
     ("sid_engine_create", _I, [C.POINTER(Opts), C.POINTER(EngineCfg), C.POINTER(_P)]),
     ("sid_engine_destroy", _I, [_P]),
@@ -153,6 +162,8 @@ SIGNATURES = [
     ("sid_engine_placement", _I, [_P, _I, C.POINTER(Placement)]),
     ("sid_engine_source_text", _I, [_P, _P, _U64]),
     ("sid_engine_source_file", _I, [_P, _I, _U64, _U64]),
+    ("sid_engine_source_bgzf", _I, [_P, _P, _U64, C.POINTER(C.c_uint64)]),
+    ("sid_engine_source_bgzf_file", _I, [_P, _I, _U64, _U64, C.POINTER(C.c_uint64)]),
     ("sid_engine_source_device_text", _I, [_P, _P, _U64]),
     ("sid_engine_source_synth", _I, [_P, _U64, _D, _U64, _U64, _U64, _U64, _I]),
     ("sid_engine_ingest", _I, [_P, C.POINTER(RunStats)]),
@@ -455,6 +466,107 @@ def synth_counts_host(seed: int, n: int, depth: float = 30.0, first: int = 0) ->
     return out
 
 
+# -------------------------------------------------------------- BGZF input --
+def _bgzf_error(st: int, what: str, off: int):
+    err = SidError(st, what)
+    err.offset = off   # SID_EBGZF: the bad member's compressed offset
+    return err
+
+
+class BgzfIndex:
+    """The block index of a BGZF byte range (sid_bgzf_index)."""
+
+    def __init__(self, data: bytes):
+        self.h = None
+        self.data = bytes(data)
+        h, off = C.c_void_p(), C.c_uint64(0)
+        st = lib().sid_bgzf_index(self.data, len(self.data), C.byref(h), C.byref(off))
+        if st != SID_OK:
+            raise _bgzf_error(st, "sid_bgzf_index", off.value)
+        self.h = h
+
+    def __len__(self):
+        return int(lib().sid_bgzf_blocks(self.h))
+
+    @property
+    def text_len(self) -> int:
+        return int(lib().sid_bgzf_text_len(self.h))
+
+    def block(self, k: int):
+        """(compressed offset, compressed size, text offset, text size) of member k."""
+        coff, csize, toff, isize = C.c_uint64(0), C.c_uint32(0), C.c_uint64(0), C.c_uint32(0)
+        check(lib().sid_bgzf_block(self.h, k, C.byref(coff), C.byref(csize), C.byref(toff), C.byref(isize)),
+              "sid_bgzf_block")
+        return coff.value, csize.value, toff.value, isize.value
+
+    def blocks(self):
+        return [self.block(k) for k in range(len(self))]
+
+    def close(self):
+        if getattr(self, "h", None) and _LIB is not None:
+            _LIB.sid_bgzf_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bgzf_index(data: bytes):
+    """The members of a BGZF byte range as (compressed offset, compressed
+    size, text offset, text size) tuples; SidError (SID_EBGZF, .offset) when
+    the bytes are not BGZF."""
+    z = BgzfIndex(data)
+    try:
+        return z.blocks()
+    finally:
+        z.close()
+
+
+def bgzf_inflate_host(data: bytes) -> bytes:
+    """sid_bgzf_inflate_host: every member inflated and CRC-checked on the host."""
+    data = bytes(data)
+    L = lib()
+    n, off = C.c_size_t(0), C.c_uint64(0)
+    st = L.sid_bgzf_inflate_host(data, len(data), None, 0, C.byref(n), C.byref(off))
+    if st != SID_OK:
+        raise _bgzf_error(st, "sid_bgzf_inflate_host", off.value)
+    buf = C.create_string_buffer(max(n.value, 1))
+    st = L.sid_bgzf_inflate_host(data, len(data), buf, n.value, C.byref(n), C.byref(off))
+    if st != SID_OK:
+        raise _bgzf_error(st, "sid_bgzf_inflate_host", off.value)
+    return buf.raw[: n.value]
+
+
+def bgzf_inflate_device(ctx: "Context", d_bytes, index: BgzfIndex, d_out, cap: int = None, first_block: int = 0,
+                        nblocks: int = None, stream=None):
+    """sid_bgzf_inflate_device: members [first_block, first_block + nblocks)
+    of the indexed range in device memory (a torch uint8 tensor or a raw
+    device pointer) inflated into d_out (likewise; cap bytes, a tensor's size
+    by default).  SidError (SID_EBGZF) carries .block, the lowest bad member."""
+    def ptr(t):
+        return t if isinstance(t, int) or t is None else t.data_ptr()
+    if nblocks is None:
+        nblocks = len(index) - first_block
+    if cap is None:
+        cap = d_out.numel() * d_out.element_size()
+    bad = C.c_uint64(0)
+    st = lib().sid_bgzf_inflate_device(ctx.h, ptr(d_bytes), index.h, first_block, nblocks, ptr(d_out), cap,
+                                       C.byref(bad), stream)
+    if st != SID_OK:
+        err = SidError(st, "sid_bgzf_inflate_device")
+        err.block = bad.value
+        raise err
+
+
+def crc32(data: bytes, crc: int = 0) -> int:
+    """sid_crc32: zlib.crc32 by the host build of the device routine."""
+    data = bytes(data)
+    return int(lib().sid_crc32(crc, data, len(data)))
+
+
 # ------------------------------------------------------------- device side --
 class Context:
     """One sid_ctx (one device, one host thread)."""
@@ -613,6 +725,31 @@ class Engine:
         if length is None:
             length = os.fstat(fd).st_size - offset
         check(lib().sid_engine_source_file(self.h, fd, offset, length), "source_file")
+
+    def source_bgzf(self, data: bytes):
+        """BGZF-compressed pileup text in host memory, inflated on the device."""
+        self._keep = C.create_string_buffer(data, len(data)) if data else None
+        off = C.c_uint64(0)
+        st = lib().sid_engine_source_bgzf(self.h, C.cast(self._keep, C.c_void_p) if data else None, len(data),
+                                          C.byref(off))
+        if st != SID_OK:
+            raise _bgzf_error(st, "source_bgzf", off.value)
+
+    def source_bgzf_host_ptr(self, ptr: int, n: int, keep=None):
+        """The same from host memory the caller owns (pinned, for measurements)."""
+        self._keep = keep
+        off = C.c_uint64(0)
+        st = lib().sid_engine_source_bgzf(self.h, ptr, n, C.byref(off))
+        if st != SID_OK:
+            raise _bgzf_error(st, "source_bgzf", off.value)
+
+    def source_bgzf_file(self, fd: int, offset: int = 0, length: int = None):
+        if length is None:
+            length = os.fstat(fd).st_size - offset
+        off = C.c_uint64(0)
+        st = lib().sid_engine_source_bgzf_file(self.h, fd, offset, length, C.byref(off))
+        if st != SID_OK:
+            raise _bgzf_error(st, "source_bgzf_file", off.value)
 
     def source_device_text(self, ptr: int, n: int, keep=None):
         self._keep = keep

@@ -45,6 +45,7 @@ extern "C" const char* sid_strerror(int status)
     case SID_ERANGE: return "value outside the device formatter's range";
     case SID_ENOBQ: return "no base-quality field";
     case SID_ELINE: return "a pileup line too long for one chunk (4 GiB)";
+    case SID_EBGZF: return "not a BGZF file, or a truncated or corrupt BGZF block";
     default: return "unknown status";
     }
 }

@@ -11,7 +11,17 @@
 // Extra long options (no short letter, so they cannot collide with the
 // reference's flags): --devices N, --threads N, --stats, --host-parse,
 // --chunk-bytes N, --hold-bytes N, --retain-bytes N, --host-hold N,
-// --only het|hom|all, --regions FILE.
+// --only het|hom|all, --regions FILE, --bgzf.
+//
+// --bgzf: the input is BGZF (samtools mpileup ... | bgzip), from a regular
+// file (mapped) or a pipe (read into memory) -- the reference pipeline's
+// `zcat input.plp.gz > input.plp` step: the compressed bytes cross the bus and
+// are inflated on the device in front of the parse (sid_engine_source_bgzf*);
+// with --host-parse they are inflated on the host (sid_bgzf_inflate_host).
+// "sid: FILE: not a BGZF file" (plain gzip or anything else) or "sid: FILE:
+// corrupt BGZF block at byte N" (N: the member's offset in the file) on
+// stderr, exit status 1, nothing on stdout; everything else is the run on the
+// inflated file's.
 //
 // --regions FILE (a BED file: chrom start end, 0-based half-open, or a chrom
 // alone for all of it; sid_regions_from_bed) writes the header and only the
@@ -67,6 +77,7 @@ struct Options {
     int threads = 0;
     bool stats = false;
     bool host_parse = false;   // parse and format on the host (sid_parse_text / sid_format_csv)
+    bool bgzf = false;         // --bgzf: the input is BGZF
     uint64_t chunk_bytes = 0;  // engine knobs (0 = defaults)
     uint64_t hold_bytes = 0;
     uint64_t host_hold = 0;   // --host-hold: sid_engine_cfg.host_hold_bytes
@@ -253,6 +264,7 @@ int main(int argc, char** argv)
                                          {"host-hold", required_argument, nullptr, 8},
                                          {"only", required_argument, nullptr, 9},
                                          {"regions", required_argument, nullptr, 10},
+                                         {"bgzf", no_argument, nullptr, 11},
                                          {nullptr, 0, nullptr, 0}};
     int flag;
     while ((flag = getopt_long(argc, argv, "E:Rhm:p:r:", LONG, nullptr)) != -1) {
@@ -318,6 +330,7 @@ int main(int argc, char** argv)
             opt.o.regions = rg;
             break;
         }
+        case 11: opt.bgzf = true; break;
         default: std::exit(EXIT_FAILURE);
         }
     }
@@ -447,6 +460,13 @@ int main(int argc, char** argv)
         return 0;
     };
     const char* HEADER = "chrom,pos,label,gt,hom_conf,het_conf,conf_type\n";
+    // --bgzf: the bytes are not BGZF from their first member on / a member further in is truncated or corrupt
+    auto bgzf_error = [&](uint64_t off, bool at_index) {
+        std::fflush(stdout);
+        if (at_index && off == 0) std::fprintf(stderr, "sid: %s: not a BGZF file\n", path);
+        else std::fprintf(stderr, "sid: %s: corrupt BGZF block at byte %llu\n", path, (unsigned long long)off);
+        std::exit(EXIT_FAILURE);
+    };
 
     // ------------------------------------------------ streaming engine path --
     if (!opt.host_parse) {
@@ -456,12 +476,20 @@ int main(int argc, char** argv)
             tc = now();
         }
         CHECK(eng_rc, "engine");
-        if (pre_map) CHECK(sid_engine_source_text(eng, pre_map, in.len), "input");   // (mapped above)
+        if (opt.bgzf) {
+            uint64_t off = 0;
+            const int zrc = pre_map ? sid_engine_source_bgzf(eng, pre_map, in.len, &off)
+                            : in.fd >= 0 && !in.data ? sid_engine_source_bgzf_file(eng, in.fd, 0, in.len, &off)
+                                                     : sid_engine_source_bgzf(eng, in.data, in.len, &off);
+            if (zrc == SID_EBGZF) bgzf_error(off, true);
+            CHECK(zrc, "input");
+        } else if (pre_map) CHECK(sid_engine_source_text(eng, pre_map, in.len), "input");   // (mapped above)
         else if (in.fd >= 0 && !in.data) CHECK(sid_engine_source_file(eng, in.fd, 0, in.len), "input");
         else CHECK(sid_engine_source_text(eng, in.data, in.len), "input");
         sid_run_stats st;
         std::memset(&st, 0, sizeof st);
         int rc = sid_engine_ingest(eng, &st);
+        if (rc == SID_EBGZF) bgzf_error(st.err_offset, false);
         if (rc != SID_OK) on_parse_error(rc);
         const double t1 = now();
         rc = sid_engine_estimate(eng, nullptr, &st.estimate);
@@ -504,7 +532,8 @@ int main(int argc, char** argv)
                          "\"chunks_retained\": %llu, \"chunks_reloaded\": %llu, \"bytes_in\": %llu, "
                          "\"bytes_out\": %llu, \"ingest_s\": %.6f, \"chunks_registered\": %llu, "
                          "\"register_s\": %.6f, \"h2d_s\": %.6f, \"h2d_bytes\": %llu, \"chunks_tiled\": %llu, "
-                         "\"tile_overflows\": %llu, \"tile_overflows_queued\": %llu, \"placement\": [%s], "
+                         "\"tile_overflows\": %llu, \"tile_overflows_queued\": %llu, \"bgzf_bytes\": %llu, "
+                         "\"bgzf_blocks\": %llu, \"placement\": [%s], "
                          "\"main_entry_unix\": %.6f, \"main_exit_unix\": %.6f}\n",
                          (unsigned long long)st.sites, D, T, tc - t0, t1 - t0, t2 - t1, t3 - t2, t3 - t0,
                          st.sites / std::max(1e-9, t3 - t0), (unsigned long long)st.chunks,
@@ -513,7 +542,8 @@ int main(int argc, char** argv)
                          (unsigned long long)st.bytes_out, st.ingest_s, (unsigned long long)st.chunks_registered,
                          st.register_s, st.h2d_s, (unsigned long long)st.h2d_bytes,
                          (unsigned long long)st.chunks_tiled, (unsigned long long)st.tile_overflows,
-                         (unsigned long long)st.tile_overflows_queued, place.c_str(),
+                         (unsigned long long)st.tile_overflows_queued, (unsigned long long)st.bgzf_bytes,
+                         (unsigned long long)st.bgzf_blocks, place.c_str(),
                          t_entry,
                          unix_now());
         // device memory, pinned staging and the mapping go with the process
@@ -527,6 +557,23 @@ int main(int argc, char** argv)
     {
         uint64_t bad = 0;
         map_input(in, true);
+        if (opt.bgzf) {   // inflated on the host, then as the plain file
+            std::string text;
+            size_t need = 0;
+            uint64_t off = 0;
+            int zrc = sid_bgzf_inflate_host(in.data, in.len, nullptr, 0, &need, &off);
+            if (zrc == SID_EBGZF) bgzf_error(off, true);
+            CHECK(zrc, "input");
+            text.resize(need);
+            zrc = sid_bgzf_inflate_host(in.data, in.len, &text[0], need, &need, &off);
+            if (zrc == SID_EBGZF) bgzf_error(off, false);
+            CHECK(zrc, "input");
+            if (in.map) munmap(in.map, in.len);
+            in.map = nullptr;
+            in.owned.swap(text);
+            in.data = in.owned.data();
+            in.len = in.owned.size();
+        }
         int prc = sid_parse_text(in.data, in.len, T, &sites, &bad);
         on_parse_error(prc);
         if (in.map) munmap(in.map, in.len);

@@ -48,6 +48,7 @@
 #include <thread>
 #include <vector>
 
+#include "bgzf_dev.h"
 #include "sid_internal.h"
 #include "synth.h"
 
@@ -232,9 +233,24 @@ struct ChunkRec {
     uint64_t host_len = 0;
     bool host1 = false;              // copied there during pass 1 (the emit only writes them)
     bool sunk = false;               // device sink: formatted in pass 1 and dropped (held_len bytes)
+    // BGZF sources: off / len are the compressed bytes uploaded (whole members); the chunk's lines are the
+    // inflated bytes [toff, toff + tlen), which start `toff - toff(member zb0)` bytes into its first member
+    uint64_t toff = 0, tlen = 0;
+    uint64_t zb0 = 0, znb = 0;       // its members [zb0, zb0 + znb) of the index
+    uint64_t share = 0;              // the bytes at the end of [off, off + len) that the next chunk uploads too
+    uint64_t zbad = ~0ull;           // the compressed offset of its first bad member
+    uint64_t kept_head = 0;          // the kept text starts there in `kept`
 };
 
-enum SrcKind { SRC_NONE, SRC_HOST, SRC_FILE, SRC_DEVICE, SRC_SYNTH_HOST, SRC_SYNTH_DEVICE };
+enum SrcKind { SRC_NONE, SRC_HOST, SRC_FILE, SRC_DEVICE, SRC_SYNTH_HOST, SRC_SYNTH_DEVICE, SRC_BGZF, SRC_BGZF_FILE };
+// BGZF input (host memory / a file's mapping): the compressed bytes move as the text of SRC_HOST / SRC_FILE does
+inline bool src_bgzf(int s) { return s == SRC_BGZF || s == SRC_BGZF_FILE; }
+inline bool src_host(int s) { return s == SRC_HOST || s == SRC_BGZF; }
+inline bool src_file(int s) { return s == SRC_FILE || s == SRC_BGZF_FILE; }
+// a BGZF chunk's text buffer: a member's worth in front of the first line (the chunk's first member is
+// written whole, its leading bytes -- the previous chunk's lines -- at negative offsets) and behind the
+// last (the last member's trailing bytes, the next chunk's lines)
+constexpr uint64_t ZHEAD = 65536;
 
 struct Loaded {
     uint64_t j = 0;
@@ -292,6 +308,13 @@ struct Dev {
     uint64_t pinned_cap = 0;
     sid_chunk_ws ws;
     uint64_t* h_small = nullptr;   // pinned, 16 words: [0] sites [4] error key [6..7] generator [8..11] formatter
+    // BGZF sources: the chunk's compressed bytes, member table, status words and result on the device (one
+    // buffer: the uploader waits for each chunk's inflate before it loads the next), and the table's
+    // pinned staging ([0] the result read back, from [16] the table)
+    char* zbuf = nullptr;
+    uint64_t zcap = 0;
+    char* ztab_h = nullptr;
+    uint64_t ztab_cap = 0;
     DevPool pool;
     // hold arena: the records formatted in pass 1, packed one after another
     // in segments of HBM kept across runs; a chunk reserves its upper bound
@@ -674,7 +697,9 @@ struct sid_engine {
     std::vector<std::unique_ptr<Dev>> devs;
     // source
     int src = SRC_NONE;
-    const char* text = nullptr;     // SRC_HOST / SRC_FILE (mapping) / SRC_DEVICE
+    const char* text = nullptr;     // SRC_HOST / SRC_FILE (mapping) / SRC_DEVICE; SRC_BGZF*: the compressed bytes
+    sid_bgzf* zidx = nullptr;       // SRC_BGZF*: the member index
+    std::atomic<uint64_t> z_bytes{0}, z_blocks{0};   // compressed bytes / members uploaded in pass 1
     uint64_t text_len = 0;
     bool reg_upload = false;        // SRC_HOST / SRC_FILE pageable: chunks registered for DMA (upload_register)
     void* map = nullptr;
@@ -950,6 +975,8 @@ static void drop_source(sid_engine* e)
         r.held = r.kept = r.pre = nullptr;
     }
     e->recs.clear();
+    sid_bgzf_free(e->zidx);
+    e->zidx = nullptr;
     e->src = SRC_NONE;
     e->text = nullptr;
     e->text_len = 0;
@@ -978,6 +1005,8 @@ extern "C" int sid_engine_destroy(sid_engine* e)
         for (hipEvent_t ev : d->h2d_free) (void)hipEventDestroy(ev);
         sid_chunk_release(&d->ws);
         if (d->h_small) (void)hipHostFree(d->h_small);
+        if (d->zbuf) (void)hipFree(d->zbuf);
+        if (d->ztab_h) (void)hipHostFree(d->ztab_h);
         for (hipStream_t s : {d->s_up, d->s_comp, d->s_d2h})
             if (s) (void)hipStreamDestroy(s);
         d->pool.release();
@@ -1101,6 +1130,104 @@ extern "C" int sid_engine_source_file(sid_engine* e, int fd, uint64_t offset, ui
     return SID_OK;
 }
 
+// BGZF chunks: runs of whole members of at most chunk_bytes of text (at least
+// one member), cut at line starts.  The cut in front of chunk j > 0 is one
+// past the first '\n' at or after the text offset of its nominal first member
+// (the line that straddles or starts at the boundary belongs to chunk j - 1;
+// no newline before the end: the end), found by inflating that member alone
+// on the host -- and the next ones while no newline appears.  A member that
+// does not inflate counts as one without a newline: it then lies inside a
+// chunk, whose device inflate reports it in file order.  Chunks whose cuts
+// coincide (a line longer than a chunk) are dropped.
+static void split_bgzf(sid_engine* e)
+{
+    const std::vector<sid_bgzf_blk>& B = e->zidx->blk;
+    const uint8_t* z = (const uint8_t*)e->text;
+    const uint64_t C = chunk_bytes(e), T = e->zidx->tlen;
+    e->recs.clear();
+    if (T == 0) return;
+    std::vector<uint64_t> cuts{0};
+    std::vector<uint8_t> buf(BGZF_MAX_ISIZE);
+    for (size_t k = 0; k < B.size();) {
+        uint64_t sum = 0;
+        do sum += B[k++].isize;
+        while (k < B.size() && sum + B[k].isize <= C);
+        if (k == B.size()) break;
+        uint64_t cut = T;
+        if (cuts.back() > B[k].toff) {
+            cut = cuts.back();   // the same newline: the previous cut's line runs past this member's start
+        } else {
+            for (size_t q = k; q < B.size(); ++q) {
+                if (!B[q].isize) continue;
+                if (sid_bgzf_inflate_block(z + B[q].coff, B[q].csize, B[q].isize, buf.data()) != BGZF_OK) continue;
+                if (const void* nl = std::memchr(buf.data(), '\n', B[q].isize)) {
+                    cut = B[q].toff + (uint64_t)((const uint8_t*)nl - buf.data()) + 1;
+                    break;
+                }
+            }
+        }
+        cuts.push_back(cut);
+    }
+    cuts.push_back(T);
+    // the member that holds text byte t (t < T)
+    auto holds = [&](uint64_t t) {
+        size_t lo = 0, hi = B.size();   // the last member with toff <= t: the empty ones in front of it share its toff
+        while (hi - lo > 1) {
+            const size_t mid = (lo + hi) / 2;
+            if (B[mid].toff <= t) lo = mid;
+            else hi = mid;
+        }
+        return lo;
+    };
+    for (size_t c = 0; c + 1 < cuts.size(); ++c) {
+        const uint64_t a = cuts[c], b = cuts[c + 1];
+        if (b <= a) continue;
+        const size_t b0 = holds(a), b1 = holds(b - 1);
+        ChunkRec r;
+        r.toff = a;
+        r.tlen = b - a;
+        r.zb0 = b0;
+        r.znb = b1 - b0 + 1;
+        r.off = B[b0].coff;
+        r.len = B[b1].coff + B[b1].csize - r.off;
+        r.share = b < T && holds(b) == b1 ? B[b1].csize : 0;
+        e->recs.push_back(r);
+    }
+}
+
+extern "C" int sid_engine_source_bgzf(sid_engine* e, const void* bytes, uint64_t len, uint64_t* err_offset)
+{
+    if (err_offset) *err_offset = 0;
+    if (!e || (!bytes && len)) return SID_EINVAL;
+    drop_source(e);
+    const int rc = sid_bgzf_index(bytes, len, &e->zidx, err_offset);
+    if (rc != SID_OK) return rc;
+    e->src = SRC_BGZF;
+    e->text = (const char*)bytes;
+    e->text_len = len;
+    e->reg_upload = upload_register() && len && !host_pinned(e->text);
+    split_bgzf(e);
+    assign_devices(e);
+    return SID_OK;
+}
+
+extern "C" int sid_engine_source_bgzf_file(sid_engine* e, int fd, uint64_t offset, uint64_t len, uint64_t* err_offset)
+{
+    if (err_offset) *err_offset = 0;
+    int rc = sid_engine_source_file(e, fd, offset, len);   // the mapping; its text chunks are replaced below
+    if (rc != SID_OK) return rc;
+    e->recs.clear();
+    rc = sid_bgzf_index(e->text, e->text_len, &e->zidx, err_offset);
+    if (rc != SID_OK) {
+        drop_source(e);
+        return rc;
+    }
+    e->src = e->map ? SRC_BGZF_FILE : SRC_BGZF;
+    split_bgzf(e);
+    assign_devices(e);
+    return SID_OK;
+}
+
 extern "C" int sid_engine_source_device_text(sid_engine* e, const char* d_text, uint64_t len)
 {
     if (!e || (!d_text && len)) return SID_EINVAL;
@@ -1212,7 +1339,7 @@ struct UploadReg {
     bool on;
     std::deque<Reg> regs;
     std::vector<hipEvent_t> evs;
-    UploadReg(sid_engine* e_, int pass) : e(e_), on(e_->reg_upload && (pass == 1 || e_->src == SRC_FILE)) {}
+    UploadReg(sid_engine* e_, int pass) : e(e_), on(e_->reg_upload && (pass == 1 || src_file(e_->src))) {}
     ~UploadReg()
     {
         for (auto& r : regs) {
@@ -1237,7 +1364,7 @@ struct UploadReg {
         if (!on || j == UINT64_MAX || find(j)) return;
         const ChunkRec& r = e->recs[j];
         const uint64_t pg = (uint64_t)sysconf(_SC_PAGESIZE);
-        const uintptr_t s = (uintptr_t)(e->text + r.off), t = s + r.len;
+        const uintptr_t s = (uintptr_t)(e->text + r.off), t = s + r.len - r.share;   // (pages are registered once)
         const uintptr_t a = (s + pg - 1) & ~(uintptr_t)(pg - 1), b = t & ~(uintptr_t)(pg - 1);
         if (b <= a || b - a < (1u << 20)) return;
         const double t0 = wall();
@@ -1365,14 +1492,17 @@ void uploader(sid_engine* e, Dev& d, const std::vector<uint64_t>& list, int pass
             continue;
         }
         if (pass == 2 && r.kept) {
-            L.base = r.kept;
+            L.base = r.kept + r.kept_head;
             L.c0 = 0;
             L.c1 = r.kept_len;
             if (!d.loaded.push(L)) break;
             continue;
         }
         // text length (synthetic sources: a bound until generated)
-        uint64_t need = e->src == SRC_SYNTH_HOST || e->src == SRC_SYNTH_DEVICE ? e->per_chunk_cap : r.len;
+        const bool bgzf = src_bgzf(e->src);
+        uint64_t need = e->src == SRC_SYNTH_HOST || e->src == SRC_SYNTH_DEVICE ? e->per_chunk_cap
+                        : bgzf                                                   ? r.tlen + 2 * ZHEAD
+                                                                                 : r.len;
         // keep it for pass 2?  Lynch always needs a second pass; local and
         // quality only once the hold budget ran out
         // (the device sink formats every -m local / quality chunk in pass 1:
@@ -1412,14 +1542,54 @@ void uploader(sid_engine* e, Dev& d, const std::vector<uint64_t>& list, int pass
             s.used = true;
         }
         uint64_t len = r.len;
-        if (e->src == SRC_HOST || e->src == SRC_FILE) {
+        // BGZF: the compressed bytes go to the device's staging buffer, the member table behind them
+        char* cdst = dst;
+        sid_bgzf_dblk* d_ztab = nullptr;
+        uint64_t zn = 0, zbad_empty = ~0ull;   // the members that hold text; the first bad empty one's offset
+        if (bgzf) {
+            const uint64_t zb = (r.len + 15) & ~(uint64_t)15, tb = r.znb * sizeof(sid_bgzf_dblk);
+            const uint64_t all = zb + tb + r.znb * 4 + 16;
+            if (d.zcap < all) {   // (the stream is idle: every BGZF chunk ends in a sync)
+                if (d.zbuf) (void)hipFree(d.zbuf);
+                d.zbuf = nullptr;
+                d.zcap = 0;
+                x = hipMalloc(&d.zbuf, all + (all >> 2));
+                if (x == hipSuccess) d.zcap = all + (all >> 2);
+            }
+            if (x == hipSuccess && d.ztab_cap < 16 + tb) {
+                if (d.ztab_h) (void)hipHostFree(d.ztab_h);
+                d.ztab_h = nullptr;
+                d.ztab_cap = 0;
+                x = hipHostMalloc((void**)&d.ztab_h, 16 + tb + (tb >> 2), hipHostMallocDefault);
+                if (x == hipSuccess) d.ztab_cap = 16 + tb + (tb >> 2);
+            }
+            if (x != hipSuccess) return (void)hipfail(e, x);
+            // (the kernel takes the members that hold text; an empty one is checked here, by the host build
+            // of the same decoder, and the lowest bad member of either kind is the chunk's)
+            sid_bgzf_dblk* h = (sid_bgzf_dblk*)(d.ztab_h + 16);
+            zn = 0;
+            zbad_empty = ~0ull;
+            for (uint64_t k = 0; k < r.znb; ++k) {
+                const sid_bgzf_blk& b = e->zidx->blk[r.zb0 + k];
+                uint8_t none;
+                if (b.isize) h[zn++] = sid_bgzf_dblk{b.coff - r.off, (int64_t)b.toff - (int64_t)r.toff, b.csize, b.isize};
+                else if (zbad_empty == ~0ull &&
+                         sid_bgzf_inflate_block((const uint8_t*)e->text + b.coff, b.csize, 0, &none) != BGZF_OK)
+                    zbad_empty = b.coff;
+            }
+            cdst = d.zbuf;
+            d_ztab = (sid_bgzf_dblk*)(d.zbuf + zb);
+            dst += ZHEAD;   // the chunk's first line
+            dcap -= ZHEAD;
+        }
+        if (src_host(e->src) || src_file(e->src)) {
             if (pass == 1 && len && !span.t0 && (span.t0 = d.h2d_event())) x = hipEventRecord(span.t0, d.s_up);
-            if (len && x == hipSuccess) x = reg.copy(dst, j, d.s_up);
+            if (len && x == hipSuccess) x = reg.copy(cdst, j, d.s_up);
             if (pass == 1 && span.t0 && x == hipSuccess) span.bytes += len;
             // the next chunk's pages pinned while this copy runs; the ones
             // whose copies are done released
             if (x == hipSuccess) reg.ahead(next_of(j));
-            if (e->src == SRC_FILE && x == hipSuccess && e->text_len > (8ull << 30)) {
+            if (src_file(e->src) && x == hipSuccess && e->text_len > (8ull << 30)) {
                 // large mapped inputs: drop the chunk's page-table entries once
                 // copied (the page cache keeps the data; RSS stays bounded)
                 x = hipStreamSynchronize(d.s_up);
@@ -1428,6 +1598,38 @@ void uploader(sid_engine* e, Dev& d, const std::vector<uint64_t>& list, int pass
                 const uint64_t a = (e->map_skew + r.off + pg - 1) & ~(pg - 1);
                 const uint64_t b = (e->map_skew + r.off + len) & ~(pg - 1);
                 if (b > a) (void)madvise((char*)e->map + a, b - a, MADV_DONTNEED);
+            }
+            if (bgzf && x == hipSuccess) {
+                // inflated on the upload stream into the text buffer, and waited for: a bad member is
+                // known before the chunk reaches the compute stage
+                uint32_t* d_status = (uint32_t*)(d_ztab + zn);
+                uint32_t* bad = (uint32_t*)d.ztab_h;
+                *bad = 0xffffffffu;
+                if (zn) x = hipMemcpyAsync(d_ztab, d.ztab_h + 16, zn * sizeof(sid_bgzf_dblk), hipMemcpyHostToDevice, d.s_up);
+                if (x == hipSuccess)
+                    x = sid_launch_bgzf_inflate((const uint8_t*)d.zbuf, d_ztab, (uint32_t)zn, (uint8_t*)dst, d_status,
+                                                d_status + zn, d.s_up);
+                if (x == hipSuccess) x = hipMemcpyAsync(bad, d_status + zn, 4, hipMemcpyDeviceToHost, d.s_up);
+                if (x == hipSuccess) x = hipStreamSynchronize(d.s_up);
+                if (x != hipSuccess) return (void)hipfail(e, x);
+                if (pass == 1) e->z_bytes += r.len - r.share, e->z_blocks += r.znb - (r.share != 0);   // (each member once)
+                len = r.tlen;
+                if (*bad != 0xffffffffu || zbad_empty != ~0ull) {
+                    if (pass == 2) return (void)fail(e, SID_EBGZF);   // cannot happen: pass 1 inflated the same bytes
+                    const sid_bgzf_dblk* h = (const sid_bgzf_dblk*)(d.ztab_h + 16);
+                    r.zbad = std::min<uint64_t>(zbad_empty, *bad != 0xffffffffu ? r.off + h[*bad].coff : UINT64_MAX);
+                    uint64_t cur = e->first_err.load();
+                    while (j < cur && !e->first_err.compare_exchange_weak(cur, j)) {
+                    }
+                    if (slot >= 0) {
+                        (void)hipEventRecord(d.slots[slot].ev_free, d.s_up);
+                        d.free_slots.push(slot);
+                    } else {
+                        d.pool.put(dst - ZHEAD, dcap + ZHEAD, d.s_up);
+                        d.retain_used -= dcap + ZHEAD;
+                    }
+                    continue;
+                }
             }
         } else if (e->src == SRC_SYNTH_HOST) {
             // generated by host threads into this device's pinned staging,
@@ -1489,8 +1691,9 @@ void uploader(sid_engine* e, Dev& d, const std::vector<uint64_t>& list, int pass
         }
         if (x != hipSuccess) return (void)hipfail(e, x);
         if (want_keep) {
-            r.kept = dst;
-            r.kept_cap = dcap;
+            r.kept_head = bgzf ? ZHEAD : 0;
+            r.kept = dst - r.kept_head;
+            r.kept_cap = dcap + r.kept_head;
             r.kept_len = len;
         }
         L.slot = slot;
@@ -2169,8 +2372,11 @@ static void reset_run(sid_engine* e)
         r.host1 = false;
         r.sunk = false;
         r.err = ~0ull;
+        r.zbad = ~0ull;
         r.parsed = 0;
     }
+    e->z_bytes = 0;
+    e->z_blocks = 0;
     for (auto& dp : e->devs) {
         Dev& d = *dp;
         d.hold_used = 0;
@@ -2363,7 +2569,7 @@ extern "C" int sid_engine_ingest(sid_engine* e, sid_run_stats* st)
     uint64_t sites = 0, bytes = 0, held = 0, kept = 0;
     for (auto& r : e->recs) {
         sites += r.parsed;
-        bytes += r.len;
+        bytes += src_bgzf(e->src) ? r.tlen : r.len;
         held += r.held != nullptr || r.host1 || r.sunk;
         kept += r.kept != nullptr;
     }
@@ -2384,17 +2590,26 @@ extern "C" int sid_engine_ingest(sid_engine* e, sid_run_stats* st)
         st->chunks_tiled = tiled;
         st->tile_overflows = tile_over;
         st->tile_overflows_queued = tile_oq;
+        st->bgzf_bytes = e->z_bytes.load();
+        st->bgzf_blocks = e->z_blocks.load();
     }
     timing_report(e, "ingest", wall() - t0);
     const uint64_t fe = e->first_err.load();
     if (fe != UINT64_MAX) {
         const ChunkRec& r = e->recs[fe];
+        if (r.zbad != ~0ull) {   // (a chunk with a bad member is not parsed: SID_EBGZF wins inside it)
+            if (st) {
+                st->status_kind = SID_EBGZF;
+                st->err_offset = r.zbad;
+            }
+            return SID_EBGZF;
+        }
         const unsigned kind = (unsigned)(r.err & 7);
         const int prc = kind == 1 ? SID_EMALFORMED : kind == 2 ? SID_ENULLCHROM : kind == 3 ? SID_EMISSING_MQ
                                                                                              : SID_ENOBQ;
         if (st) {
             st->status_kind = prc;
-            st->err_offset = r.off + (r.err >> 3);
+            st->err_offset = (src_bgzf(e->src) ? r.toff : r.off) + (r.err >> 3);
         }
         return prc;
     }
