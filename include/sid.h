@@ -44,6 +44,20 @@
  *     site; the caller's per-site arrays are not changed.  sid_create and
  *     sid_engine_create copy what they need: the object may be freed right
  *     after.  Host formatting: sid_regions_mark marks the codes first.
+ *   - Context (sid_opts.context = N, 0 .. 64; --context N): grep -C N over the
+ *     unselected output.  Let U be the records u_0 .. u_(R-1) of the run
+ *     without a selection, in file order (a site that prints no record has no
+ *     index in U), and S the indices the selections by label and region keep.
+ *     The same formatters then emit exactly the records u_i with
+ *     min over s in S of |i - s| <= N, byte for byte and in U's order: every
+ *     selected record with the N records before and after it.  The distance
+ *     is in records, not sites or positions.  S empty: the header alone.
+ *     Without a selection, or with N = 0, the output is what it is without
+ *     the option.  Header, stderr, exit status, the calls, the -R prior, the
+ *     Lynch estimate and Benjamini-Hochberg are unchanged, and the result does
+ *     not depend on chunk size, device count, lanes, budgets or source kind.
+ *     Any other N: SID_EINVAL from sid_create and sid_engine_create.  Host
+ *     formatting: sid_context_mark, after the two marks above.
  *   - Counts layout: profile_t (pileup.hpp:7) = 4 x uint16 {A,C,G,T} per site,
  *     array of structures, 8 bytes per site.
  */
@@ -109,12 +123,24 @@ typedef struct {
     const struct sid_regions* regions; /* --regions (default NULL = every site): the
                                     records emitted, by (chrom, pos); see
                                     sid_regions_* below                            */
+    int context;                 /* --context (default 0): with a selection, the N
+                                    records before and after every selected record
+                                    are emitted too (0 .. 64, else SID_EINVAL)      */
 } sid_opts;
 void sid_opts_default(sid_opts* o);
 /* Sets SID_CODE_DROPPED on the n host codes whose label is not `select`, so
  * that sid_format_csv skips them (SID_SELECT_ALL: nothing changes).
  * SID_EINVAL for another value of select or a NULL code with n != 0. */
 int sid_select_mark(uint8_t* code /* host */, size_t n, int select);
+/* The context on the host path (the analogue of sid_select_mark and
+ * sid_regions_mark, after them).  code_all: the n codes before any selection
+ * marked them -- the sites without SID_CODE_DROPPED are U's records; code: the
+ * codes after the marks -- its sites without SID_CODE_DROPPED are S.  Clears
+ * SID_CODE_DROPPED in code for every record of U within `context` records of
+ * one of S.  SID_EINVAL for a NULL pointer with n != 0 or a context outside
+ * 0 .. 64. */
+#define SID_CONTEXT_MAX 64
+int sid_context_mark(const uint8_t* code_all /* host */, uint8_t* code /* host */, size_t n, int context);
 
 /* ---------------------------------------------------------- region sets --
  * A set of (chrom, start, end) intervals in BED convention (0-based,
@@ -424,7 +450,8 @@ typedef struct {
     uint64_t bytes_in;           /* input text bytes                                 */
     uint64_t bytes_out;          /* CSV bytes written (header excluded; with a
                                     selection by label or region: the selected
-                                    records')                                       */
+                                    records', with a context theirs too; exact in
+                                    every sink mode)                                */
     uint64_t chunks_held;        /* formatted in the first pass                      */
     uint64_t chunks_retained;    /* text kept in HBM for the second pass             */
     uint64_t chunks_reloaded;    /* text read from the source a second time          */
@@ -520,7 +547,8 @@ int sid_engine_profile_load(sid_engine* e, const uint64_t* keys, const uint64_t*
 /* With host_hold_bytes: the CSV records of chunk `chunk` (0 .. stats.chunks-1,
  * file order) in the host arena, after the emit (device_sink 2: the records
  * are not written anywhere else), valid until the next ingest or source;
- * SID_ESTATE when that chunk's records did not go through the host arena. */
+ * SID_ESTATE when that chunk's records did not go through the host arena.
+ * With a context: exactly the bytes the chunk contributed to the output. */
 int sid_engine_records(sid_engine* e, uint64_t chunk, const char** bytes, uint64_t* len);
 /* Measurement: with profiling on, every stage of every chunk is bracketed by
  * a pair of HIP events on its device's compute stream; _read sums the stages'

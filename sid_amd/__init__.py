@@ -49,7 +49,7 @@ class Opts(C.Structure):
     """sid_opts = GlobalOptions (sid.cpp:11-17)."""
     _fields_ = [("method", C.c_int), ("estimate_prior", C.c_int), ("snp_prior", C.c_double),
                 ("significance_level", C.c_double), ("site_error_threshold", C.c_double), ("select", C.c_int),
-                ("regions", C.c_void_p)]
+                ("regions", C.c_void_p), ("context", C.c_int)]
 
 
 class Estimate(C.Structure):
@@ -99,6 +99,7 @@ SIGNATURES = [
     ("sid_version", C.c_char_p, []),
     ("sid_opts_default", None, [C.POINTER(Opts)]),
     ("sid_select_mark", _I, [_P, _SZ, _I]),
+    ("sid_context_mark", _I, [_P, _P, _SZ, _I]),
     ("sid_regions_from_bed", _I, [C.c_char_p, _SZ, C.POINTER(_P), C.POINTER(C.c_uint64)]),
     ("sid_regions_from_intervals", _I, [C.POINTER(C.c_char_p), _P, _P, _SZ, C.POINTER(_P)]),
     ("sid_regions_intervals", _SZ, [_P]),
@@ -276,7 +277,7 @@ class Regions:
 
 
 def make_opts(method="local", estimate_prior=False, snp_prior=-1.0, significance_level=0.05,
-              site_error_threshold=0.1, select="all", regions=None) -> Opts:
+              site_error_threshold=0.1, select="all", regions=None, context=0) -> Opts:
     o = Opts()
     lib().sid_opts_default(C.byref(o))
     o.method = METHODS[method] if isinstance(method, str) else int(method)
@@ -292,6 +293,8 @@ def make_opts(method="local", estimate_prior=False, snp_prior=-1.0, significance
     # (the pointer alone: sid_create / sid_engine_create copy the set, and the
     # caller keeps the Regions object until then)
     o.regions = regions._handle() if regions is not None else None
+    # (0 .. 64: sid_create / sid_engine_create return SID_EINVAL for another value)
+    o.context = int(context)
     return o
 
 
@@ -366,6 +369,18 @@ def select_mark(code: np.ndarray, select="all") -> np.ndarray:
         raise SidError(1, f"select: expected one of {sorted(SELECT)}, got {select!r}")
     check(lib().sid_select_mark(_ptr(out), out.size, SELECT[select] if isinstance(select, str) else int(select)),
           "sid_select_mark")
+    return out
+
+
+def context_mark(code_all: np.ndarray, code: np.ndarray, context: int) -> np.ndarray:
+    """sid_context_mark on a copy of `code` (the codes after select_mark /
+    regions_mark; code_all: the codes before them): every record within
+    `context` records of a selected one gets its record back."""
+    src = np.ascontiguousarray(code_all, dtype=np.uint8)
+    out = np.ascontiguousarray(code, dtype=np.uint8).copy()
+    if src.size != out.size:
+        raise SidError(1, "context_mark: one code of each array per site")
+    check(lib().sid_context_mark(_ptr(src), _ptr(out), out.size, int(context)), "sid_context_mark")
     return out
 
 

@@ -63,6 +63,7 @@ extern "C" void sid_opts_default(sid_opts* o)
     o->site_error_threshold = 0.1;
     o->select = SID_SELECT_ALL;
     o->regions = nullptr;
+    o->context = 0;
 }
 
 // GSL 2.7.1 specfunc/gamma.c lngamma_lanczos (x >= 0.5, away from 1 and 2,
@@ -130,11 +131,19 @@ extern "C" int sid_create(int device, const sid_opts* opts, sid_ctx** out)
     if (!out) return SID_EINVAL;
     *out = nullptr;
     if (opts && (opts->select < SID_SELECT_ALL || opts->select > SID_SELECT_HOM)) return SID_EINVAL;
+    if (opts && (opts->context < 0 || opts->context > SID_CONTEXT_MAX)) return SID_EINVAL;
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return sid_set_hip_error(e);
     sid_ctx* c = new sid_ctx();
     c->device = device;
     if (opts) c->opts = *opts; else sid_opts_default(&c->opts);
+    // a context around a selection: the unselected tables, tails and parse, and the marking stage selects
+    // (without a selection the context changes nothing)
+    if (c->opts.context > 0 && (c->opts.select != SID_SELECT_ALL || c->opts.regions)) {
+        c->cx_n = c->opts.context;
+        c->cx_select = c->opts.select;
+        c->opts.select = SID_SELECT_ALL;
+    }
     sid_build_local_k(c->opts, &c->K);
     // SID_TABLE_TAIL=0: the second-level class table off, its sites through
     // the fix-up (tests/test_local_gpu.py covers both)
@@ -173,7 +182,8 @@ extern "C" int sid_create(int device, const sid_opts* opts, sid_ctx** out)
         c->regtab = sid_regtab{(const uint64_t*)(b + L.c8),   (const uint32_t*)(b + L.clen), (const uint32_t*)(b + L.noff),
                                (const uint32_t*)(b + L.ibeg), (const int32_t*)(b + L.start), (const int32_t*)(b + L.end),
                                b + L.names, L.nc, L.ni};
-        c->has_regions = true;
+        c->has_regions = c->cx_n == 0;
+        c->cx_regions = c->cx_n != 0;
         c->opts.regions = nullptr;
     }
     if (e != hipSuccess) {

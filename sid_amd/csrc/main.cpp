@@ -11,7 +11,16 @@
 // Extra long options (no short letter, so they cannot collide with the
 // reference's flags): --devices N, --threads N, --stats, --host-parse,
 // --chunk-bytes N, --hold-bytes N, --retain-bytes N, --host-hold N,
-// --only het|hom|all, --regions FILE, --bgzf.
+// --only het|hom|all, --regions FILE, --bgzf, --context N.
+//
+// --context N (0 .. 64): grep -C N over the unselected output -- with --only
+// and / or --regions, every selected record comes with the N records before
+// and after it (records, not positions; sid_opts.context), chosen before the
+// records are formatted; the reference pipeline's identify-nonsyn.sh step
+// then reads its SNPs' neighbouring lines from the selected output.  Without
+// a selection, or with N = 0, nothing changes.  A value that is not a decimal
+// integer in 0 .. 64: "sid: --context: expected 0..64, got ARG" on stderr,
+// exit status 1, nothing on stdout.  Given twice, the last wins.
 //
 // --bgzf: the input is BGZF (samtools mpileup ... | bgzip), from a regular
 // file (mapped) or a pipe (read into memory) -- the reference pipeline's
@@ -265,6 +274,7 @@ int main(int argc, char** argv)
                                          {"only", required_argument, nullptr, 9},
                                          {"regions", required_argument, nullptr, 10},
                                          {"bgzf", no_argument, nullptr, 11},
+                                         {"context", required_argument, nullptr, 12},
                                          {nullptr, 0, nullptr, 0}};
     int flag;
     while ((flag = getopt_long(argc, argv, "E:Rhm:p:r:", LONG, nullptr)) != -1) {
@@ -331,6 +341,21 @@ int main(int argc, char** argv)
             break;
         }
         case 11: opt.bgzf = true; break;
+        case 12: {
+            int v = 0;
+            bool good = *optarg != 0 && std::strlen(optarg) <= 3;
+            for (const char* c = optarg; good && *c; ++c) {
+                good = *c >= '0' && *c <= '9';
+                v = v * 10 + (*c - '0');
+            }
+            if (!good || v > SID_CONTEXT_MAX) {
+                std::fflush(stdout);
+                std::fprintf(stderr, "sid: --context: expected 0..64, got %s\n", optarg);
+                std::exit(EXIT_FAILURE);
+            }
+            opt.o.context = v;
+            break;
+        }
         default: std::exit(EXIT_FAILURE);
         }
     }
@@ -687,8 +712,11 @@ int main(int argc, char** argv)
             }
             HCHECK(hipStreamSynchronize(s.stream), "D2H");
         });
+        std::vector<uint8_t> code_all;   // --context: the codes before the selections marked them
+        if (opt.o.context > 0 && (opt.o.select != SID_SELECT_ALL || regions)) code_all.assign(h_code, h_code + n);
         CHECK(sid_select_mark(h_code, n, opt.o.select), "select");   // --only: the other labels' sites get no record
         CHECK(sid_regions_mark(regions, sites, 0, n, h_code), "regions");   // --regions: nor the sites outside
+        if (!code_all.empty()) CHECK(sid_context_mark(code_all.data(), h_code, n, opt.o.context), "context");
         const size_t BLOCK = 1u << 18;
         const size_t nblocks = (n + BLOCK - 1) / BLOCK;
         std::vector<std::vector<char>> bufs(nblocks);

@@ -45,10 +45,12 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <string>
 #include <thread>
 #include <vector>
 
 #include "bgzf_dev.h"
+#include "context.h"
 #include "sid_internal.h"
 #include "synth.h"
 
@@ -240,6 +242,10 @@ struct ChunkRec {
     uint64_t share = 0;              // the bytes at the end of [off, off + len) that the next chunk uploads too
     uint64_t zbad = ~0ull;           // the compressed offset of its first bad member
     uint64_t kept_head = 0;          // the kept text starts there in `kept`
+    // a context (sid_opts.context): the chunk's descriptor, read back with its byte count, and the bytes it
+    // formatted (its forced edge records included; what the stitch keeps of them is decided at the emit)
+    sid_cx_desc cx{};
+    uint64_t cx_total = 0;
 };
 
 enum SrcKind { SRC_NONE, SRC_HOST, SRC_FILE, SRC_DEVICE, SRC_SYNTH_HOST, SRC_SYNTH_DEVICE, SRC_BGZF, SRC_BGZF_FILE };
@@ -308,6 +314,7 @@ struct Dev {
     uint64_t pinned_cap = 0;
     sid_chunk_ws ws;
     uint64_t* h_small = nullptr;   // pinned, 16 words: [0] sites [4] error key [6..7] generator [8..11] formatter
+    sid_cx_desc* h_cx = nullptr;   // pinned: the chunk's context descriptor, copied back beside the formatter's words
     // BGZF sources: the chunk's compressed bytes, member table, status words and result on the device (one
     // buffer: the uploader waits for each chunk's inflate before it loads the next), and the table's
     // pinned staging ([0] the result read back, from [16] the table)
@@ -731,6 +738,7 @@ struct sid_engine {
     std::vector<int> gen_dev;         // device whose stream recorded gen_ev
     uint64_t per_chunk_cap = 0;
     sid_estimate est{};
+    int cx_n = 0;                    // the context in effect (sid_ctx::cx_n: 0 without a selection)
     bool prof = false;
     double prof_ms[6] = {0, 0, 0, 0, 0, 0};   // sid_engine_prof order: index parse call hist fmt_len fmt_write
     uint64_t prof_chunks = 0;
@@ -896,6 +904,7 @@ extern "C" int sid_engine_create(const sid_opts* opts, const sid_engine_cfg* cfg
     if (!out) return SID_EINVAL;
     *out = nullptr;
     if (opts && (opts->select < SID_SELECT_ALL || opts->select > SID_SELECT_HOM)) return SID_EINVAL;
+    if (opts && (opts->context < 0 || opts->context > SID_CONTEXT_MAX)) return SID_EINVAL;
     int nvis = 0;
     if (hipGetDeviceCount(&nvis) != hipSuccess || nvis <= 0) return SID_EHIP;
     sid_engine* e = new sid_engine();
@@ -931,6 +940,7 @@ extern "C" int sid_engine_create(const sid_opts* opts, const sid_engine_cfg* cfg
             if (x == hipSuccess) x = hipStreamCreateWithFlags(&d->s_comp, hipStreamNonBlocking);
             if (x == hipSuccess) x = hipStreamCreateWithFlags(&d->s_d2h, hipStreamNonBlocking);
             if (x == hipSuccess) x = hipHostMalloc((void**)&d->h_small, 128, hipHostMallocDefault);
+            if (x == hipSuccess) x = hipHostMalloc((void**)&d->h_cx, sizeof(sid_cx_desc), hipHostMallocDefault);
             d->slots.resize(R);
             for (auto& s : d->slots) {
                 if (x == hipSuccess) x = hipEventCreateWithFlags(&s.ev_up, hipEventDisableTiming);
@@ -938,8 +948,8 @@ extern "C" int sid_engine_create(const sid_opts* opts, const sid_engine_cfg* cfg
             }
         });
         int rc = sid_create(d->device, &e->opts, &d->ctx);
-        d->ws.select = e->opts.select;   // (the formatters that take no context: sid_chunk_fmt_len / _put)
-        if (rc == SID_OK && d->ctx->has_regions) d->ws.regions = &d->ctx->regtab;   // (likewise: the context's copy)
+        // (the formatters that take no context, sid_chunk_fmt_len / _put: the options as the context holds them)
+        if (rc == SID_OK) sid_chunk_bind_context(&d->ws, d->ctx);
         qs.join();
         if (rc == SID_OK && x != hipSuccess) rc = sid_set_hip_error(x);
         rcs[i] = rc;
@@ -959,6 +969,7 @@ extern "C" int sid_engine_create(const sid_opts* opts, const sid_engine_cfg* cfg
             sid_engine_destroy(e);
             return rc;
         }
+    e->cx_n = e->devs[0]->ctx->cx_n;
     *out = e;
     return SID_OK;
 }
@@ -1005,6 +1016,7 @@ extern "C" int sid_engine_destroy(sid_engine* e)
         for (hipEvent_t ev : d->h2d_free) (void)hipEventDestroy(ev);
         sid_chunk_release(&d->ws);
         if (d->h_small) (void)hipHostFree(d->h_small);
+        if (d->h_cx) (void)hipHostFree(d->h_cx);
         if (d->zbuf) (void)hipFree(d->zbuf);
         if (d->ztab_h) (void)hipHostFree(d->ztab_h);
         for (hipStream_t s : {d->s_up, d->s_comp, d->s_d2h})
@@ -1884,6 +1896,8 @@ void compute(sid_engine* e, Dev& d, int pass)
                 if (rc != SID_OK) return (void)fail(e, rc);
                 // bytes, range flag, sites, parse error key, the most lines in a tile
                 x = hipMemcpyAsync(hs + 8, W.lb + 1, 5 * 8, hipMemcpyDeviceToHost, d.s_comp);
+                if (x == hipSuccess && e->cx_n)
+                    x = hipMemcpyAsync(d.h_cx, W.cx_desc, sizeof(sid_cx_desc), hipMemcpyDeviceToHost, d.s_comp);
                 if (x == hipSuccess && (done.ev = d.take_event())) x = hipEventRecord(done.ev, d.s_comp);
                 // the next chunk's tile parse behind this writer (stream order:
                 // it rewrites the slots and W.lb after the writer and the copy
@@ -2127,6 +2141,8 @@ void compute(sid_engine* e, Dev& d, int pass)
                 d.prof_end(5, pe);
                 if (rc != SID_OK) return (void)fail(e, rc);
                 x = hipMemcpyAsync(hs + 8, W.lb + 1, 32, hipMemcpyDeviceToHost, d.s_comp);   // bytes, flags, error
+                if (x == hipSuccess && e->cx_n)
+                    x = hipMemcpyAsync(d.h_cx, W.cx_desc, sizeof(sid_cx_desc), hipMemcpyDeviceToHost, d.s_comp);
                 // the next chunk's line index behind the formatter (stream
                 // order: it rewrites W.state only after the formatter has read it)
                 // (not when the tile path already took the next chunk: this
@@ -2191,6 +2207,10 @@ void compute(sid_engine* e, Dev& d, int pass)
         }
         if (out && hs[9]) return (void)fail(e, SID_ERANGE);
         const uint64_t bytes = hs[8];
+        if (e->cx_n) {   // (read back by the sync that brought the byte count)
+            r.cx = out ? *d.h_cx : sid_cx_desc{};   // (a chunk without sites: nothing ran, nothing to stitch)
+            r.cx_total = bytes;
+        }
         release_slot();
         if (pass == 2 && r.kept) {   // kept text done with: back to the pool after this stream's work
             d.pool.put(r.kept, r.kept_cap, d.s_comp);
@@ -2335,6 +2355,102 @@ void drain(sid_engine* e, Dev& d)
     d.out_q.close();
 }
 
+// The writer under a context (sid_opts.context): a chunk's bytes arrive in
+// file order, in pieces; the records between its two forced zones and the
+// head zone's (decided by the chunks in front) go out at once, the tail zone's
+// bytes (at most N records) are held until the stitch has seen enough of the
+// chunks behind to decide them -- the next chunk, as a rule.
+struct CxWriter {
+    sid_engine* e;
+    sid_write_fn write;
+    void* user;
+    sid_cx_stitch S;
+    std::vector<std::string> held;   // per chunk: its tail zone's bytes
+    size_t flushed = 0;              // the chunks whose held bytes are decided and written
+    size_t complete = 0;             // the chunks whose bytes have all arrived
+    bool ok = true;
+    const ChunkRec* r = nullptr;     // the chunk arriving
+    uint64_t pos = 0, t0 = 0;        // bytes of it seen; its tail zone starts at t0
+    sid_cx_range rg[2 * SID_CONTEXT_MAX + 1];
+    size_t nr = 0;
+
+    CxWriter(sid_engine* e_, sid_write_fn w, void* u) : e(e_), write(w), user(u), S(e_->cx_n), held(e_->recs.size()) {}
+    void put(const char* p, uint64_t len)
+    {
+        if (ok && len && write(user, p, len) != 0) ok = false;
+    }
+    void flush()
+    {
+        for (; flushed < std::min(S.resolved(), complete); ++flushed) {
+            const ChunkRec& c = e->recs[flushed];
+            std::string& h = held[flushed];
+            if (h.empty()) continue;
+            sid_cx_range g[2 * SID_CONTEXT_MAX + 1];
+            const uint64_t c0 = c.cx_total - h.size();
+            const size_t n = sid_cx_ranges(c.cx, e->cx_n, S.verdict(flushed), c.cx_total, g, nullptr);
+            for (size_t k = 0; k < n; ++k) {
+                const uint64_t a = std::max(g[k].off, c0), b = g[k].off + g[k].len;
+                if (b > a) put(h.data() + (a - c0), b - a);
+            }
+            std::string().swap(h);
+        }
+    }
+    void begin(uint64_t j)
+    {
+        r = &e->recs[j];
+        S.push(r->cx);
+        complete = j;   // (the chunks in front of it)
+        flush();
+        pos = 0;
+        uint64_t tail = 0;
+        for (uint32_t k = 0; k < sid_cx_zone(r->cx, e->cx_n); ++k) tail += r->cx.tail_len[k];
+        t0 = r->cx_total - std::min(tail, r->cx_total);
+        nr = sid_cx_ranges(r->cx, e->cx_n, S.verdict(j), r->cx_total, rg, nullptr);
+        held[j].reserve(r->cx_total - t0);
+    }
+    // the chunk's next bytes
+    void piece(uint64_t j, const char* p, uint64_t len)
+    {
+        const uint64_t lo = pos, hi = pos + len;
+        for (size_t k = 0; k < nr; ++k) {   // in front of the tail zone: decided
+            const uint64_t a = std::max(rg[k].off, lo), b = std::min({rg[k].off + rg[k].len, hi, t0});
+            if (b > a) put(p + (a - lo), b - a);
+        }
+        if (hi > t0) {
+            const uint64_t a = std::max(lo, t0);
+            held[j].append(p + (a - lo), hi - a);
+        }
+        pos = hi;
+    }
+    void finish()
+    {
+        S.finish();
+        complete = S.chunks();
+        flush();
+    }
+};
+
+// After the emit under a context: every chunk's final verdicts (all the
+// descriptors are there), the bytes they keep -- the run's bytes_out in every
+// sink mode -- and the chunks in the host arena cut down to them in place
+// (sid_engine_records).
+uint64_t cx_settle(sid_engine* e)
+{
+    sid_cx_stitch S(e->cx_n);
+    for (const auto& r : e->recs) S.push(r.cx);
+    S.finish();
+    uint64_t out = 0;
+    sid_cx_range g[2 * SID_CONTEXT_MAX + 1];
+    for (size_t j = 0; j < e->recs.size(); ++j) {
+        ChunkRec& r = e->recs[j];
+        uint64_t kept = 0;
+        const size_t n = sid_cx_ranges(r.cx, e->cx_n, S.verdict(j), r.cx_total, g, &kept);
+        out += kept;
+        if (r.host && r.host_len == r.cx_total) r.host_len = sid_cx_compact(const_cast<char*>(r.host), g, n);
+    }
+    return out;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------ phases --
@@ -2374,6 +2490,8 @@ static void reset_run(sid_engine* e)
         r.err = ~0ull;
         r.zbad = ~0ull;
         r.parsed = 0;
+        r.cx = sid_cx_desc{};
+        r.cx_total = 0;
     }
     e->z_bytes = 0;
     e->z_blocks = 0;
@@ -2742,9 +2860,23 @@ extern "C" int sid_engine_emit(sid_engine* e, const char* header, sid_write_fn w
     if (all_host) {
         uint64_t out = 0;
         bool ok = !(sink == 0 && header && write(user, header, std::strlen(header)) != 0);
-        for (const auto& r : e->recs) {
-            if (ok && sink == 0 && r.host_len && write(user, r.host, r.host_len) != 0) ok = false;
-            out += r.host_len;
+        if (e->cx_n) {   // the forced edge records decided, and cut out
+            if (sink == 0) {
+                CxWriter cw(e, write, user);
+                cw.ok = ok;
+                for (uint64_t j = 0; j < e->recs.size(); ++j) {
+                    cw.begin(j);
+                    cw.piece(j, e->recs[j].host, e->recs[j].host_len);
+                }
+                cw.finish();
+                ok = cw.ok;
+            }
+            out = cx_settle(e);
+        } else {
+            for (const auto& r : e->recs) {
+                if (ok && sink == 0 && r.host_len && write(user, r.host, r.host_len) != 0) ok = false;
+                out += r.host_len;
+            }
         }
         if (st) {
             st->chunks_reloaded = 0;
@@ -2770,6 +2902,7 @@ extern "C" int sid_engine_emit(sid_engine* e, const char* header, sid_write_fn w
             if (r.pre) d.pool.put(r.pre, r.pre_cap, nullptr);
             r.held = r.kept = r.pre = nullptr;
         }
+        if (e->cx_n) out = cx_settle(e);
         e->sink_bytes = out;
         if (st) {
             st->chunks_reloaded = 0;
@@ -2805,11 +2938,23 @@ extern "C" int sid_engine_emit(sid_engine* e, const char* header, sid_write_fn w
     if (sink != 1) {
         bool ok = true;
         if (sink == 0 && header && write(user, header, std::strlen(header)) != 0) ok = false;
+        // a context: the pieces go through the stitch (cxw; a chunk's descriptor is there before its first
+        // piece: the compute thread read it back before it queued the chunk)
+        std::unique_ptr<CxWriter> cxw;
+        if (e->cx_n && sink == 0) cxw.reset(new CxWriter(e, write, user));
+        bool cx_begun = false;
+        auto emit_bytes = [&](uint64_t j, const char* p, uint64_t len) {
+            if (!cxw) return !(sink == 0 && len && write(user, p, len) != 0);
+            if (!cx_begun) cxw->begin(j), cx_begun = true;
+            cxw->piece(j, p, len);
+            return cxw->ok;
+        };
         for (uint64_t j = 0; j < e->recs.size() && e->rc.load() == SID_OK; ++j) {
             Dev& d = *e->devs[e->recs[j].dev];
             const ChunkRec& rj = e->recs[j];
+            cx_begun = false;
             if (rj.host1) {   // copied back during the ingest (which waited for the copies)
-                if (ok && sink == 0 && rj.host_len && write(user, rj.host, rj.host_len) != 0) ok = false;
+                if (ok && !emit_bytes(j, rj.host, rj.host_len)) ok = false;
                 out_bytes += rj.host_len;
                 if (!ok) break;
                 continue;
@@ -2826,7 +2971,7 @@ extern "C" int sid_engine_emit(sid_engine* e, const char* header, sid_write_fn w
                         fail(e, SID_EHIP);
                         break;
                     }
-                    if (ok && sink == 0 && write(user, p.host, p.len) != 0) ok = false;
+                    if (ok && !emit_bytes(j, p.host, p.len)) ok = false;
                     out_bytes += p.len;
                 } else if (p.ps >= 0) {
                     const double w0 = wall();
@@ -2836,18 +2981,23 @@ extern "C" int sid_engine_emit(sid_engine* e, const char* header, sid_write_fn w
                         fail(e, SID_EHIP);
                         break;
                     }
-                    if (ok && sink == 0 && write(user, d.pinned[p.ps], p.len) != 0) ok = false;
+                    if (ok && !emit_bytes(j, d.pinned[p.ps], p.len)) ok = false;
                     out_bytes += p.len;
                     d.free_pinned.push(p.ps);
                 }
                 if (p.last) {
                     d.pool.put(p.buf, p.cap, nullptr);   // its D2H completed (event above)
                     got_last = true;
+                    if (cxw && !cx_begun) cxw->begin(j);   // (a chunk without bytes: its descriptor all the same)
                     break;
                 }
             }
             if (!ok) fail(e, SID_EIO);
             if (!got_last) break;
+        }
+        if (cxw && ok && e->rc.load() == SID_OK) {
+            cxw->finish();
+            ok = cxw->ok;
         }
         if (!ok) fail(e, SID_EIO);
         if (e->rc.load() != SID_OK) close_all(e);
@@ -2857,9 +3007,12 @@ extern "C" int sid_engine_emit(sid_engine* e, const char* header, sid_write_fn w
         (void)hipSetDevice(dp->device);
         if (hipDeviceSynchronize() != hipSuccess) fail(e, SID_EHIP);
     }
+    const bool cx_done = e->cx_n && e->rc.load() == SID_OK;
+    const uint64_t cx_out = cx_done ? cx_settle(e) : 0;
     if (st) {
         st->chunks_reloaded = e->reloaded.load();
         st->bytes_out = sink == 1 ? e->sink_bytes.load() : out_bytes.load();
+        if (cx_done) st->bytes_out = cx_out;
         st->emit_s = wall() - t0;
     }
     timing_report(e, "emit", wall() - t0);

@@ -124,6 +124,13 @@ struct sid_ctx {
     bool has_regions = false;
     char* d_regions = nullptr;   // the table's device buffer
     sid_regtab regtab;
+    // the context (sid_opts.context with a selection; else cx_n = 0 and nothing below is used): the parse,
+    // tables and tails are then the unselected ones (opts.select is SID_SELECT_ALL and has_regions false from
+    // sid_create on), and the marking stage (textpath.hip, sid_context_*_kernel) tests the label and the
+    // region itself
+    int cx_n = 0;
+    int cx_select = SID_SELECT_ALL;
+    bool cx_regions = false;   // regtab holds the set
     // measurement (sid_timing_enable / sid_timing_read)
     int timing = 0;
     std::vector<sid_timing_ev> ev_pool, ev_pending;
@@ -200,7 +207,21 @@ struct sid_chunk_ws {
     int select = 0;               // the owner's sid_opts.select, for the formatters that take no context
                                   // (sid_chunk_fmt_len / _put); set once by the owner
     const sid_regtab* regions = nullptr;   // likewise the owner's region set (its context's regtab), or null
+    // likewise the owner's context (sid_ctx::cx_n, cx_select, cx_regions ? &regtab : null), and the marking
+    // stage's buffers (sized with the sites): two ballots per 64 slots (is a record, is selected), a summary
+    // and the two carried distances per 512-slot group, the in-chunk verdicts of the forced records, and the
+    // chunk's descriptor (context.h), complete after the writer
+    int cx_n = 0;
+    int cx_select = 0;
+    const sid_regtab* cx_regions = nullptr;
+    unsigned long long* cx_bits = nullptr;
+    uint4* cx_sum = nullptr;
+    uint4* cx_car = nullptr;
+    uint8_t* cx_hk = nullptr;   // 2 x SID_CONTEXT_MAX bytes: head zone, tail zone
+    struct sid_cx_desc* cx_desc = nullptr;
 };
+// the owner's context options into its workspace (after sid_create)
+void sid_chunk_bind_context(sid_chunk_ws* W, const sid_ctx* ctx);
 int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites);
 void sid_chunk_release(sid_chunk_ws* W);
 int sid_chunk_index(sid_chunk_ws* W, const char* base, uint64_t c0, uint64_t c1, hipStream_t st);

@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "../../include/sid.h"
+#include "context.h"
 #include "fmt.h"
 #include "local_site.h"
 
@@ -3715,6 +3716,401 @@ static void launch_region_mark(const RegArgs<Off>& A, hipStream_t st)
 // stores (an exon-like set leaves most groups empty or with a few records).
 constexpr uint32_t REG_LDS_MIN = 2048;
 
+// ---------------------------------------------------------------- context --
+// The context (sid_opts.context = N with a selection; sid_ctx::cx_n): every
+// selected record with the N records before and after it, in record rank --
+// slots past a tile's count and sites that print no record do not count.  The
+// parse, tables and tails are the unselected ones; this stage tests the label
+// and the region itself and leaves the markers of the region stage (above) on
+// what falls outside the dilated set, in the same place of every formatter
+// family, so the region writers and the unselected Lynch / code writers follow
+// unchanged.  Three kernels, no atomics:
+//   flag   per slot two bits as wave ballots (is a record of U, is selected),
+//          per 512-slot group {records, has a selected one, records before its
+//          first, records after its last}
+//   scan   one block over the groups' summaries: forward the records since the
+//          last selected one, backward the records until the next, both
+//          saturated at N + 1 (whole groups and tiles may be empty), and the
+//          groups' first ranks; the chunk's descriptor (context.h)
+//   mark   a record's distance to the nearest selected one from its group's
+//          ballots and the two carried distances; the chunk's first and last
+//          min(N, records) records are forced (kept whatever the verdict, which
+//          goes into the descriptor for the engine's stitch: their neighbours
+//          are another chunk's); the markers, and -m local's group sums again
+// and after the writer, sid_context_edge_kernel reads the forced records'
+// byte lengths off the chunk's first and last few KB of records.
+template <class Off>
+struct CxArgs {
+    RegArgs<Off> A;               // the region stage's view of the sites (A.T: the set, when reg)
+    const char* str1;             // -m local: the class entries ([0] tail length, [1] het)
+    const char* str2;
+    sid_lynch_fmt V;              // REG_LYNCH: the classes
+    uint32_t sel;                 // SID_SELECT_*: the label selected (ALL: every label)
+    uint32_t reg;                 // a region set selects too
+    uint32_t N;
+    uint32_t force;               // the chunk's edge records are forced (not for a whole text at once)
+    unsigned long long* bits;     // per wave of slots: [0] records, [1] selected
+    uint4* sum;                   // per group (the flag kernel)
+    uint4* car;                   // per group: x records since the last selected one in front of it, y records
+                                  // until the next one behind it, z its first record's rank
+    uint8_t* hk;                  // in-chunk verdicts: [k] head zone, [SID_CONTEXT_MAX + k] tail zone
+    sid_cx_desc* desc;
+};
+
+// the slot's site as the region stage loads it: the class word (-m local) and whether the slot holds a site
+template <int MODE, bool OPT, class Off>
+__device__ __forceinline__ bool cx_site(const RegArgs<Off>& A, uint64_t i, uint32_t* w)
+{
+    *w = 0;
+    if (i >= A.s1) return false;
+    if (MODE == REG_TILE) {
+        *w = A.cls[i];
+        const uint32_t t = slot_tile((uint32_t)i, A.cdiv);
+        const uint32_t j = (uint32_t)i - __umul24(t, A.cap);
+        return j < A.tcnt[t] && *w != SID_CLS_SKIP;
+    }
+    if (MODE == REG_DENSE) {
+        if (OPT) {   // (no class words yet: written here, for the mark kernel and the writer)
+            const LocalLen LL{A.len1, A.len2, nullptr, nullptr, nullptr, nullptr};
+            (void)local_site_word<false>(A.counts[i], A.len1, LL, w);
+            A.cls[i] = *w;
+        } else {
+            *w = A.cls[i];
+        }
+        return *w != SID_CLS_SKIP;
+    }
+    return true;
+}
+
+template <int MODE, bool OPT, class Off>
+__device__ __forceinline__ Head cx_head(const RegArgs<Off>& A, uint64_t i, uint32_t w, Reader& R)
+{
+    if (MODE == REG_TILE) {
+        if (OPT && cls_compact(w)) {   // (the entry: tile_wave_store)
+            const uint32_t t = slot_tile((uint32_t)i, A.cdiv);
+            const uint32_t j = (uint32_t)i - __umul24(t, A.cap);
+            const ulonglong2 te = A.twv[__umul24(t, A.nwv) + (j >> 6)];
+            Head h{0, 0, 0, 0};
+            h.clen = (uint32_t)(te.y >> 32) & 0xFFFu;
+            h.pos = (int32_t)((uint32_t)te.y + ((w >> 20) & (SID_CLS_DPOS - 1)));
+            h.c8 = te.x;
+            return h;
+        }
+        return slot_head(R, *(const ulonglong2*)(A.hdr + 2 * i));
+    }
+    return site_head(R, A.starts + i, A.hdr ? A.hdr + 2 * i : nullptr);
+}
+
+// -m local: the class entry's first two bytes (tail length, 0xFF: the fix-up's site; het)
+__device__ __forceinline__ uint32_t cx_entry(uint32_t w, const char* str1, const char* str2)
+{
+    if (w == SID_CLS_MISS) return 0xFFu;
+    const uint32_t k = w & 0xFFFFFu;
+    const char* e = k < SID_TAB_N ? str1 + (size_t)k * SID_STR_BYTES : str2 + (size_t)(k - SID_TAB_N) * SID_STR_BYTES;
+    return *(const uint16_t*)e;
+}
+
+template <int MODE, bool OPT, class Off>
+__global__ __launch_bounds__(FTB) void sid_context_flag_kernel(const CxArgs<Off> C)
+{
+    const RegArgs<Off>& A = C.A;
+    __shared__ unsigned long long mr[FTB / 64], ms[FTB / 64];
+    const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
+    Reader R{A.text, A.len};
+    uint32_t w;
+    const bool site = cx_site<MODE, OPT>(A, i, &w);
+    bool rec = false, het = false;
+    if (site) {
+        if (MODE == REG_TILE || MODE == REG_DENSE) {
+            const uint32_t e = cx_entry(w, C.str1, C.str2);
+            if ((e & 0xFFu) == 0xFFu) {   // the fix-up's site: its code
+                const uint32_t c = A.code[i];
+                rec = !(c & SID_CODE_DROPPED);
+                het = (c & SID_CODE_HET) != 0;
+            } else {
+                rec = (e & 0xFFu) != 0;
+                het = (e >> 8) & 1u;
+            }
+        } else if (MODE == REG_LYNCH) {
+            const uint32_t idx = lynch_class(A.counts[i], C.V);
+            if (idx != 0xFFFFFFFFu) {
+                const char* t = C.V.lstr + (size_t)idx * SID_LSTR_BYTES;
+                rec = t[0] != 0;
+                het = t[9] == 'e';   // "het," / "hom,"
+            }
+        } else {
+            const uint32_t c = A.code[i];
+            rec = !(c & SID_CODE_DROPPED);
+            het = (c & SID_CODE_HET) != 0;
+        }
+    }
+    bool sel = rec && (C.sel == SID_SELECT_ALL || het == (C.sel == SID_SELECT_HET));
+    if (C.reg) {   // (uniform)
+        Head h{0, 0, 0, 0};
+        if (sel) h = cx_head<MODE, OPT>(A, i, w, R);
+        sel = reg_inside(R, h, sel, A.T);
+    }
+    const unsigned long long br = __ballot(rec), bs = __ballot(sel);
+    const uint32_t wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        const uint64_t gw = (uint64_t)blockIdx.x * (FTB / 64) + wv;
+        C.bits[2 * gw] = br;
+        C.bits[2 * gw + 1] = bs;
+        mr[wv] = br;
+        ms[wv] = bs;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t n = 0, has = 0, lead = 0, trail = 0;
+        for (int k = 0; k < FTB / 64; ++k) {
+            const unsigned long long r = mr[k], s = ms[k];
+            if (s) {
+                const int lo = __ffsll(s) - 1, hi = 63 - __clzll((long long)s);
+                if (!has) lead = n + __popcll(r & ((1ull << lo) - 1ull));
+                has = 1;
+                trail = hi == 63 ? 0u : (uint32_t)__popcll(r >> (hi + 1));
+            } else {
+                trail += __popcll(r);
+            }
+            n += __popcll(r);
+        }
+        C.sum[blockIdx.x] = make_uint4(n, has, lead, trail);
+    }
+}
+
+constexpr int CX_SCAN_TB = 1024;
+__global__ __launch_bounds__(CX_SCAN_TB) void sid_context_scan_kernel(const uint4* __restrict__ sum, uint32_t G, uint32_t N,
+                                                                     uint4* __restrict__ car, uint8_t* __restrict__ hk,
+                                                                     sid_cx_desc* __restrict__ desc)
+{
+    __shared__ uint32_t s_cnt[CX_SCAN_TB], s_has[CX_SCAN_TB], s_tr[CX_SCAN_TB], s_ld[CX_SCAN_TB];
+    __shared__ uint32_t s_since[CX_SCAN_TB], s_until[CX_SCAN_TB], s_rank[CX_SCAN_TB];
+    const uint32_t t = threadIdx.x, cap = N + 1;
+    const uint32_t per = (G + CX_SCAN_TB - 1) / CX_SCAN_TB;
+    const uint32_t g0 = (uint32_t)min((uint64_t)t * per, (uint64_t)G), g1 = (uint32_t)min((uint64_t)g0 + per, (uint64_t)G);
+    auto sat = [cap](uint64_t v) { return (uint32_t)(v < cap ? v : cap); };
+    uint32_t cnt = 0, has = 0, tr = 0, ld = 0;
+    for (uint32_t g = g0; g < g1; ++g) {
+        const uint4 v = sum[g];
+        if (v.y) {
+            if (!has) ld = sat((uint64_t)cnt + v.z);
+            has = 1;
+            tr = sat(v.w);
+        } else {
+            tr = sat((uint64_t)tr + v.x);
+        }
+        cnt += v.x;   // (below 2^32: a chunk's slots are)
+    }
+    s_cnt[t] = cnt, s_has[t] = has, s_tr[t] = tr, s_ld[t] = ld;
+    if (t < 2 * SID_CONTEXT_MAX) hk[t] = 0;
+    if (t < SID_CONTEXT_MAX) desc->head_len[t] = 0, desc->tail_len[t] = 0;
+    __syncthreads();
+    if (t == 0) {
+        uint32_t since = cap, rank = 0, any = 0;
+        for (int k = 0; k < CX_SCAN_TB; ++k) {
+            s_since[k] = since;
+            s_rank[k] = rank;
+            since = s_has[k] ? s_tr[k] : sat((uint64_t)since + s_cnt[k]);
+            rank += s_cnt[k];
+            any |= s_has[k];
+        }
+        uint32_t until = cap;
+        for (int k = CX_SCAN_TB - 1; k >= 0; --k) {
+            s_until[k] = until;
+            until = s_has[k] ? s_ld[k] : sat((uint64_t)until + s_cnt[k]);
+        }
+        desc->records = rank;
+        desc->has_sel = any;
+        desc->lead = until;
+        desc->trail = since;
+        desc->head_keep = 0;
+        desc->tail_keep = 0;
+    }
+    __syncthreads();
+    uint32_t since = s_since[t], rank = s_rank[t];
+    for (uint32_t g = g0; g < g1; ++g) {
+        const uint4 v = sum[g];
+        car[g] = make_uint4(since, 0, rank, 0);
+        since = v.y ? sat(v.w) : sat((uint64_t)since + v.x);
+        rank += v.x;
+    }
+    uint32_t until = s_until[t];
+    for (uint32_t g = g1; g-- > g0;) {
+        const uint4 v = sum[g];
+        ((uint32_t*)(car + g))[1] = until;
+        until = v.y ? sat(v.z) : sat((uint64_t)until + v.x);
+    }
+}
+
+// MODE REG_DENSE: always on class words (the flag kernel wrote them where the parse had not)
+template <int MODE, bool OPT, class Off>
+__global__ __launch_bounds__(FTB) void sid_context_mark_kernel(const CxArgs<Off> C)
+{
+    const RegArgs<Off>& A = C.A;
+    __shared__ unsigned long long mr[FTB / 64], ms[FTB / 64];
+    const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
+    if (threadIdx.x < FTB / 64) {
+        const uint64_t gw = (uint64_t)blockIdx.x * (FTB / 64) + threadIdx.x;
+        mr[threadIdx.x] = C.bits[2 * gw];
+        ms[threadIdx.x] = C.bits[2 * gw + 1];
+    }
+    __syncthreads();
+    const uint4 cr = C.car[blockIdx.x];
+    const uint32_t N = C.N, R = C.desc->records;
+    const int wv = (int)(threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool rec = (mr[wv] >> lane) & 1ull;
+    bool keep = false;
+    if (rec) {
+        const unsigned long long le = lane == 63 ? ~0ull : (1ull << (lane + 1)) - 1ull, ge = ~0ull << lane;
+        // the records from the nearest selected one in front (it excluded) to this one (included)
+        uint32_t dp = 0, dn = 0;
+        {
+            unsigned long long s = ms[wv] & le;
+            uint32_t acc = 0;
+            int k = wv;
+            unsigned long long r = mr[wv] & le;
+            bool found = false;
+            for (;;) {
+                if (s) {
+                    const int p = 63 - __clzll((long long)s);
+                    dp = acc + (p == 63 ? 0u : (uint32_t)__popcll(r >> (p + 1)));
+                    found = true;
+                    break;
+                }
+                acc += __popcll(r);
+                if (--k < 0) break;
+                s = ms[k], r = mr[k];
+            }
+            if (!found) dp = min(acc + cr.x, N + 1);   // (acc <= 512, cr.x <= N + 1)
+        }
+        // ... and from this one (included) to the nearest selected one behind (excluded)
+        {
+            unsigned long long s = ms[wv] & ge;
+            uint32_t acc = 0;
+            int k = wv;
+            unsigned long long r = mr[wv] & ge;
+            bool found = false;
+            for (;;) {
+                if (s) {
+                    const int p = __ffsll(s) - 1;
+                    dn = acc + (uint32_t)__popcll(r & ((1ull << p) - 1ull));
+                    found = true;
+                    break;
+                }
+                acc += __popcll(r);
+                if (++k >= FTB / 64) break;
+                s = ms[k], r = mr[k];
+            }
+            if (!found) dn = min(acc + cr.y, N + 1);
+        }
+        keep = min(dp, dn) <= N;
+        if (C.force) {
+            uint32_t rank = cr.z + (uint32_t)__popcll(mr[wv] & (le >> 1));
+            for (int k = 0; k < wv; ++k) rank += __popcll(mr[k]);
+            const uint32_t z = min(N, R);
+            if (rank < z) C.hk[rank] = keep;
+            if (rank >= R - z) C.hk[SID_CONTEXT_MAX + rank - (R - z)] = keep;
+            keep = keep || rank < z || rank >= R - z;
+        }
+    }
+    const bool drop = rec && !keep;
+    if (MODE == REG_LYNCH) {
+        if (drop) A.counts[i] = 0;
+        return;
+    }
+    if (MODE == REG_CODE) {
+        if (drop) A.code[i] |= SID_CODE_DROPPED;
+        return;
+    }
+    if (!__syncthreads_or(drop)) return;   // nothing dropped: the group's sum stands
+    if (!__syncthreads_or(keep)) {         // nothing kept: a group without bytes (the writers pass over it)
+        if (threadIdx.x == 0) A.bsum[blockIdx.x] = 0;
+        return;
+    }
+    if (drop) A.cls[i] = SID_CLS_SKIP;
+    int l = 0;
+    if (keep) {
+        Reader Rd{A.text, A.len};
+        const uint32_t w = A.cls[i];
+        const Head h = cx_head<MODE, OPT>(A, i, w, Rd);
+        const uint32_t e = cx_entry(w, C.str1, C.str2);
+        if ((e & 0xFFu) == 0xFFu) l = miss_len<3>(h, A.code[i], A.hom[i], A.het[i], A.ct);
+        else l = local_rec_len(h, e & 0xFFu);
+    }
+    const uint32_t tot = block_sum<FTB>((uint32_t)l);
+    if (threadIdx.x == 0) A.bsum[blockIdx.x] = tot;
+}
+
+// After the writer: the byte lengths of the chunk's forced records off its
+// records (block 0: the first min(N, records) from the front; block 1: the
+// last ones from the back; a record ends in '\n'), and the verdict bytes packed
+// into the descriptor's masks.  One wave each, 64 bytes a step.
+__global__ __launch_bounds__(64) void sid_context_edge_kernel(const char* __restrict__ out,
+                                                              const unsigned long long* __restrict__ total_p, uint32_t N,
+                                                              const uint8_t* __restrict__ hk, sid_cx_desc* desc)
+{
+    const uint64_t total = *total_p;
+    const uint32_t z = min(N, desc->records), lane = threadIdx.x;
+    if (blockIdx.x == 0) {
+        const unsigned long long m = __ballot(lane < z && hk[lane]);
+        if (lane == 0) desc->head_keep = m;
+        uint64_t pos = 0, start = 0;
+        uint32_t cnt = 0;
+        while (cnt < z && pos < total) {   // (wave-uniform)
+            unsigned long long nl = __ballot(pos + lane < total && out[pos + lane] == '\n');
+            while (nl && cnt < z) {
+                const uint64_t end = pos + (uint64_t)(__ffsll(nl) - 1) + 1;
+                nl &= nl - 1;
+                if (lane == 0) desc->head_len[cnt] = (uint32_t)(end - start);
+                start = end;
+                ++cnt;
+            }
+            pos += 64;
+        }
+    } else {
+        const unsigned long long m = __ballot(lane < z && hk[SID_CONTEXT_MAX + lane]);
+        if (lane == 0) desc->tail_keep = m;
+        uint64_t hi = total, end = total;
+        uint32_t cnt = 0;
+        while (cnt < z && hi > 0) {
+            const uint64_t lo = hi >= 64 ? hi - 64 : 0;
+            unsigned long long nl = __ballot(lo + lane < hi && out[lo + lane] == '\n');
+            while (nl && cnt < z) {
+                const int b = 63 - __clzll((long long)nl);
+                nl &= ~(1ull << b);
+                const uint64_t q = lo + (uint64_t)b;
+                if (q + 1 == end) continue;   // (the record's own newline)
+                if (lane == 0) desc->tail_len[z - 1 - cnt] = (uint32_t)(end - (q + 1));
+                end = q + 1;
+                ++cnt;
+            }
+            hi = lo;
+        }
+        if (cnt < z && end > 0 && lane == 0) desc->tail_len[z - 1 - cnt] = (uint32_t)end;   // (from the chunk's first byte)
+    }
+}
+
+// the stage for the groups of A's sites (none: the empty descriptor)
+template <int MODE, bool OPT, class Off>
+static void launch_context_mark(CxArgs<Off>& C, const sid_chunk_ws* W, const sid_ctx* ctx, hipStream_t st,
+                                bool force = true)
+{
+    C.sel = (uint32_t)W->cx_select, C.reg = W->cx_regions != nullptr, C.N = (uint32_t)W->cx_n, C.force = force;
+    if (W->cx_regions) C.A.T = *W->cx_regions;
+    if (ctx) C.str1 = ctx->ws.str1, C.str2 = ctx->ws.str2;
+    C.bits = W->cx_bits, C.sum = W->cx_sum, C.car = W->cx_car, C.hk = W->cx_hk, C.desc = W->cx_desc;
+    const uint64_t nb = (C.A.s1 - C.A.s0 + FTB - 1) / FTB;
+    if (nb) sid_context_flag_kernel<MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(C);
+    sid_context_scan_kernel<<<1, CX_SCAN_TB, 0, st>>>(C.sum, (uint32_t)nb, C.N, C.car, C.hk, C.desc);
+    if (nb) sid_context_mark_kernel<MODE, (MODE == REG_TILE && OPT), Off><<<(unsigned)nb, FTB, 0, st>>>(C);
+}
+
+static void launch_context_edge(const sid_chunk_ws* W, const char* out, hipStream_t st)
+{
+    sid_context_edge_kernel<<<2, 64, 0, st>>>(out, W->lb + 1, (uint32_t)W->cx_n, W->cx_hk, W->cx_desc);
+}
+
 // tails of the U classes (one thread each), then the dense codes' lengths
 __global__ __launch_bounds__(256) void sid_lynch_str_kernel(const uint8_t* __restrict__ pcode,
                                                            const double* __restrict__ cc, uint32_t U, CType ct,
@@ -4280,6 +4676,28 @@ extern "C" int sid_dtext_format(sid_ctx* ctx, const sid_dtext* T, size_t begin, 
         hip(hipGetLastError());
         d_code = d_rcode;
     }
+    // a context: the records outside the dilated selection likewise (the whole range at once: no forced
+    // edges), with buffers of this call's own
+    void* d_cx = nullptr;
+    if (rc == SID_OK && nb && ctx->cx_n) {
+        const uint64_t ng = (n + FTB - 1) / FTB;
+        const size_t o_sum = ng * (FTB / 64) * 16, o_car = o_sum + ng * 16, o_hk = o_car + ng * 16;
+        const size_t o_desc = (o_hk + 2 * SID_CONTEXT_MAX + 15) & ~(size_t)15;
+        if (hip(hipMalloc(&d_cx, o_desc + sizeof(sid_cx_desc))) && hip(hipMalloc(&d_rcode, end)) &&
+            hip(hipMemcpyAsync(d_rcode + begin, d_code + begin, n, hipMemcpyDeviceToDevice, st))) {
+            sid_chunk_ws X;
+            sid_chunk_bind_context(&X, ctx);
+            X.cx_bits = (unsigned long long*)d_cx, X.cx_sum = (uint4*)((char*)d_cx + o_sum);
+            X.cx_car = (uint4*)((char*)d_cx + o_car), X.cx_hk = (uint8_t*)d_cx + o_hk;
+            X.cx_desc = (sid_cx_desc*)((char*)d_cx + o_desc);
+            CxArgs<uint64_t> C{};
+            C.A.text = T->d_text, C.A.len = T->len, C.A.starts = T->d_starts, C.A.hdr = T->d_hdr, C.A.s0 = begin, C.A.s1 = end;
+            C.A.code = d_rcode;
+            launch_context_mark<REG_CODE, false>(C, &X, nullptr, st, false);
+            hip(hipGetLastError());
+            d_code = d_rcode;
+        }
+    }
     if (rc == SID_OK && nb) {
         hip(hipMemsetAsync(d_bad, 0, 4, st));
         hip(hipMemsetAsync(d_base, 0, 8, st));
@@ -4345,7 +4763,7 @@ extern "C" int sid_dtext_format(sid_ctx* ctx, const sid_dtext* T, size_t begin, 
     for (int b = 0; b < 2; ++b) (void)hipEventDestroy(done[b]);
     (void)hipEventDestroy(written);
     (void)hipStreamDestroy(cs);
-    for (void* p : {(void*)d_bsum, (void*)d_boff, (void*)d_base, (void*)d_bad, (void*)d_rcode})
+    for (void* p : {(void*)d_bsum, (void*)d_boff, (void*)d_base, (void*)d_bad, (void*)d_rcode, d_cx})
         if (p) (void)hipFree(p);
     return rc;
 }
@@ -4489,6 +4907,11 @@ int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites)
     // queued work are not released under it (growth is rare: the first
     // chunks, or a chunk far above the usual lines per byte)
     if (!W->state) WCHECK(hipMalloc(&W->state, 8 * sizeof(uint64_t)));
+    if (W->cx_n && !W->cx_desc) {   // the context's descriptor and the forced records' verdict bytes
+        WCHECK(hipMalloc(&W->cx_desc, sizeof(sid_cx_desc)));
+        WCHECK(hipMalloc(&W->cx_hk, 2 * SID_CONTEXT_MAX));
+        WCHECK(hipMemset(W->cx_desc, 0, sizeof(sid_cx_desc)));
+    }
     const uint64_t tiles = ((bytes + 16 + IX_TILE - 1) / IX_TILE + 1) * IX_SUB;   // 4 KiB tiles, in whole index tiles
     if (tiles > W->tile_cap) {
         const uint64_t t = std::max<uint64_t>(tiles, W->tile_cap + W->tile_cap / 2);
@@ -4508,8 +4931,10 @@ int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites)
         const uint64_t m = std::max<uint64_t>(sites, W->site_cap + W->site_cap / 2);
         for (void* p : {(void*)W->starts, (void*)W->counts, (void*)W->code, (void*)W->hom, (void*)W->het,
                         (void*)W->bsum, (void*)W->boff, (void*)W->hdr, (void*)W->fb, (void*)W->lb, (void*)W->cls,
-                        (void*)W->twv})
+                        (void*)W->twv, (void*)W->cx_bits, (void*)W->cx_sum, (void*)W->cx_car})
             if (p) (void)hipFree(p);
+        W->cx_bits = nullptr;
+        W->cx_sum = W->cx_car = nullptr;
         W->lb = nullptr;
         W->cls = nullptr;
         W->twv = nullptr;
@@ -4534,6 +4959,12 @@ int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites)
         WCHECK(hipMalloc(&W->bsum, ((nb * 4 + 7) & ~(size_t)7) + scan_ws_bytes(nb)));
         WCHECK(hipMalloc(&W->boff, (nb + 1) * 8));
         WCHECK(hipMalloc(&W->lb, std::max<uint64_t>(nb + 5, 8) * 8));
+        if (W->cx_n) {   // per 512-slot group: 8 waves' two ballots, the summary, the carried distances
+            const uint64_t ng = (m + FTB - 1) / FTB + 1;
+            WCHECK(hipMalloc(&W->cx_bits, ng * (FTB / 64) * 16));
+            WCHECK(hipMalloc(&W->cx_sum, ng * sizeof(uint4)));
+            WCHECK(hipMalloc(&W->cx_car, ng * sizeof(uint4)));
+        }
         W->site_cap = m;
     }
     return SID_OK;
@@ -4543,13 +4974,26 @@ void sid_chunk_release(sid_chunk_ws* W)
 {
     for (void* p : {(void*)W->starts, (void*)W->counts, (void*)W->code, (void*)W->hom, (void*)W->het,
                     (void*)W->bsum, (void*)W->boff, (void*)W->tcnt, (void*)W->toff, (void*)W->state,
-                    (void*)W->hdr, (void*)W->fb, (void*)W->masks, (void*)W->lb, (void*)W->cls, (void*)W->twv})
+                    (void*)W->hdr, (void*)W->fb, (void*)W->masks, (void*)W->lb, (void*)W->cls, (void*)W->twv,
+                    (void*)W->cx_bits, (void*)W->cx_sum, (void*)W->cx_car, (void*)W->cx_hk, (void*)W->cx_desc})
         if (p) (void)hipFree(p);
     const int select = W->select;   // (the owner's options, not the buffers')
     const sid_regtab* regions = W->regions;
+    const int cx_n = W->cx_n, cx_select = W->cx_select;
+    const sid_regtab* cx_regions = W->cx_regions;
     *W = sid_chunk_ws{};
     W->select = select;
     W->regions = regions;
+    W->cx_n = cx_n, W->cx_select = cx_select, W->cx_regions = cx_regions;
+}
+
+void sid_chunk_bind_context(sid_chunk_ws* W, const sid_ctx* ctx)
+{
+    W->select = ctx->opts.select;   // (SID_SELECT_ALL under a context: the marking stage selects)
+    W->regions = ctx->has_regions ? &ctx->regtab : nullptr;
+    W->cx_n = ctx->cx_n;
+    W->cx_select = ctx->cx_select;
+    W->cx_regions = ctx->cx_regions ? &ctx->regtab : nullptr;
 }
 
 // blocks of the strided index kernels (count kernel, index stage per 50M
@@ -4668,6 +5112,11 @@ int sid_chunk_fmt_len(sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n
         A.xm = sel_word(W->select), A.T = *W->regions;
         launch_region_mark<REG_CODE, false>(A, st);
     }
+    if (W->cx_n) {   // the context: the records outside the dilated selection, dropped likewise
+        CxArgs<sid_off_t> C{};
+        C.A.text = base, C.A.len = c1, C.A.starts = W->starts, C.A.hdr = W->hdr, C.A.s1 = n, C.A.code = W->code;
+        launch_context_mark<REG_CODE, false>(C, W, nullptr, st);
+    }
     if (nb) sid_fmt_blen_kernel<<<(unsigned)nb, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->code, W->hom,
                                                               W->het, ct, W->bsum, W->lb, sel_word(W->select));
     WCHECK(hipGetLastError());
@@ -4684,6 +5133,7 @@ int sid_chunk_fmt_put(sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n
                             ? SID_OK : SID_EHIP;
     sid_fmt_put_kernel<<<(unsigned)nb, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->code, W->hom, W->het, ct,
                                                     W->boff, W->state, W->lb, out, sel_word(W->select));
+    if (W->cx_n) launch_context_edge(W, out, st);
     WCHECK(hipGetLastError());
     return SID_OK;
 }
@@ -4736,6 +5186,16 @@ int sid_chunk_local_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
             W->cls_ready = true;
         }
     }
+    if (ctx->cx_n) {   // the context (no groups: the empty descriptor)
+        CxArgs<sid_off_t> C{};
+        RegArgs<sid_off_t>& A = C.A;
+        A.text = base, A.len = c1, A.starts = W->starts, A.hdr = W->hdr, A.s1 = n, A.cls = W->cls;
+        A.counts = W->counts, A.code = W->code, A.hom = W->hom, A.het = W->het, A.ct = ct;
+        A.len1 = ctx->ws.len1, A.len2 = ctx->ws.len2, A.bsum = W->bsum;
+        if (W->cls_ready) launch_context_mark<REG_DENSE, false>(C, W, ctx, st);
+        else launch_context_mark<REG_DENSE, true>(C, W, ctx, st);
+        if (nb) W->cls_ready = true;
+    }
     W->lens_ready = false;
     WCHECK(hipGetLastError());
     return fmt_scan(W, nb, st);
@@ -4755,7 +5215,7 @@ int sid_chunk_local_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
         if (W->slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (slot_tile's exact range: a 4 GiB chunk has fewer)
         const SlotDiv cdiv = slot_div(W->slot_cap);
         const uint32_t xm = sel_word(ctx->opts.select);
-        if (ctx->has_regions) {   // per group, by its record bytes (REG_LDS_MIN): the LDS assembly or the byte stores
+        if (ctx->has_regions || ctx->cx_n) {   // per group, by its record bytes (REG_LDS_MIN): the LDS assembly or the byte stores
             auto put = W->tile_quad ? sid_local_put_reg_kernel<true, false> : sid_local_put_reg_kernel<true, true>;
             put<<<(unsigned)nbs, FTB, 0, st>>>(base, c1, nullptr, W->hdr, W->slots, W->tcnt, W->slot_cap, cdiv, W->twv,
                                                tile_nwv(W->slot_cap), W->counts, W->cls, ctx->ws.str1, ctx->ws.str2,
@@ -4767,6 +5227,7 @@ int sid_chunk_local_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
                                                                     ctx->ws.str1, ctx->ws.str2, W->code, W->hom, W->het,
                                                                     ct, W->bsum, W->boff, W->state, W->lb, out, xm,
                                                                     REG_LDS_MIN);
+            if (ctx->cx_n) launch_context_edge(W, out, st);
             WCHECK(hipGetLastError());
             return SID_OK;
         }
@@ -4812,7 +5273,7 @@ int sid_chunk_local_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     if (nb == 0) return hipMemcpyAsync(W->lb + 4, W->state + 4, 8, hipMemcpyDeviceToDevice, st) == hipSuccess
                             ? SID_OK : SID_EHIP;
     const uint32_t* cw = W->cls_ready ? W->cls : nullptr;
-    if (ctx->has_regions) {   // (the class words: the parse's, or the region kernel's; the groups with a record)
+    if (ctx->has_regions || ctx->cx_n) {   // (the class words: the parse's, or the marking kernel's; the groups with a record)
         if (!cw) return SID_ESTATE;
         sid_local_put_reg_kernel<true><<<(unsigned)nb, FTB, 0, st>>>(
             base, c1, W->starts, W->hdr, n, nullptr, 0, SlotDiv{0, 0}, nullptr, 0, W->counts, cw, ctx->ws.str1,
@@ -4829,6 +5290,7 @@ int sid_chunk_local_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
                                           W->counts, cw, ctx->ws.str1, ctx->ws.str2, W->code, W->hom, W->het, ct,
                                           W->boff, W->state, W->lb, out);
     }
+    if (ctx->cx_n) launch_context_edge(W, out, st);
     WCHECK(hipGetLastError());
     return SID_OK;
 }
@@ -4895,7 +5357,7 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
     const uint64_t slots = ntp * cap;
     if (slots > W->site_cap || ntp > W->tile_cap || slots >= (1ull << 32)) return SID_EINVAL;
     if (ntp * tile_nwv(cap) > W->site_cap / 32 + 1) return SID_EINVAL;   // (never: cap >= 64)
-    if (ctx->has_regions && slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (the region kernel's slot_tile: its exact range, as the writer's)
+    if ((ctx->has_regions || ctx->cx_n) && slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (the marking kernels' slot_tile: its exact range, as the writer's)
     W->lens_ready = false;
     W->cls_ready = false;
     W->slot_cap = cap;
@@ -4906,6 +5368,10 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
     if (nb) WCHECK(hipMemsetAsync(W->bsum, 0, nb * 4, st));
     if (ntp == 0) {
         WCHECK(hipMemsetAsync(W->state + 4, 0xFF, sizeof(uint64_t), st));
+        if (ctx->cx_n) {   // (the empty descriptor)
+            CxArgs<sid_off_t> C{};
+            launch_context_mark<REG_TILE, false>(C, W, ctx, st);
+        }
         return fmt_scan(W, nb, st);
     }
     uint32_t* miss = W->fb + 2 * W->site_cap;
@@ -4927,6 +5393,15 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
         A.T = ctx->regtab;
         if (quad) launch_region_mark<REG_TILE, false>(A, st);
         else launch_region_mark<REG_TILE, true>(A, st);
+    }
+    if (ctx->cx_n) {   // the context: the slots outside the dilated selection likewise
+        CxArgs<sid_off_t> C{};
+        RegArgs<sid_off_t>& A = C.A;
+        A.text = base, A.len = c1, A.hdr = W->hdr, A.s1 = slots, A.tcnt = W->tcnt, A.cap = cap, A.cdiv = slot_div(cap);
+        A.twv = W->twv, A.nwv = tile_nwv(cap), A.cls = W->cls, A.code = W->code, A.hom = W->hom, A.het = W->het;
+        A.ct = ct, A.bsum = W->bsum;
+        if (quad) launch_context_mark<REG_TILE, false>(C, W, ctx, st);
+        else launch_context_mark<REG_TILE, true>(C, W, ctx, st);
     }
     WCHECK(hipGetLastError());
     W->cls_ready = true;
@@ -4986,6 +5461,13 @@ int sid_chunk_lynch_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     if (n > W->site_cap) return SID_EINVAL;
     WCHECK(hipMemsetAsync(W->lb, 0, 8 * 8, st));   // [1] bytes, [2] range flag
     const uint64_t nb = (n + FTB - 1) / FTB;
+    if (ctx->cx_n) {   // the context: counts 0 likewise (no class or no site: the empty descriptor)
+        CxArgs<sid_off_t> C{};
+        RegArgs<sid_off_t>& A = C.A;
+        A.text = base, A.len = c1, A.starts = W->starts, A.hdr = W->hdr, A.s1 = V.empty ? 0 : n, A.counts = W->counts;
+        C.V = V;
+        launch_context_mark<REG_LYNCH, false>(C, W, nullptr, st);
+    }
     if (nb && V.empty) {   // no class: every site dropped (and no length table)
         WCHECK(hipMemsetAsync(W->bsum, 0, nb * 4, st));
     } else if (nb) {
@@ -5019,6 +5501,7 @@ int sid_chunk_lynch_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     else
         (ctx->opts.select != SID_SELECT_ALL ? sid_lynch_put_kernel<true> : sid_lynch_put_kernel<false>)
             <<<(unsigned)nb, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->counts, V, W->boff, W->state, W->lb, out);
+    if (ctx->cx_n) launch_context_edge(W, out, st);
     WCHECK(hipGetLastError());
     return SID_OK;
 }
