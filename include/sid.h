@@ -58,6 +58,27 @@
  *     not depend on chunk size, device count, lanes, budgets or source kind.
  *     Any other N: SID_EINVAL from sid_create and sid_engine_create.  Host
  *     formatting: sid_context_mark, after the two marks above.
+ *   - Windows (sid_opts.window = W, 0 = off, 1 .. 2^31-1; --windows W): a
+ *     summary of the run along the input, beside the records.  The sites are the
+ *     non-empty lines in file order; a site's chrom is its first token, its pos
+ *     the integer its record prints (atoi: possibly 0 or negative) and its
+ *     window index wi = floor((pos - 1) / W) in 64-bit signed arithmetic.  A row
+ *     is a maximal run of consecutive sites with byte-equal chrom and equal wi:
+ *     chrom; start = wi W and end = start + W (BED, as the region sets: the row
+ *     holds the positions with start < pos <= end); sites, the lines of the
+ *     run; records, those of them that print a record in the unselected output
+ *     (the Lynch methods print none below coverage 4); het and hom, those
+ *     records by label (records = het + hom).  Sorted input gives one row per
+ *     window that has a site; a position that goes back or a chrom that
+ *     returns opens a further row, as uniq -c would (no sorting, no hashing).
+ *     Like the calls and the estimate the rows see every site: the selections
+ *     by label and region and the context do not change them, and the option
+ *     changes neither the records, stderr nor the exit status.  The rows do
+ *     not depend on chunk size, device count, lanes, budgets, source kind or
+ *     sink mode; a chunk counts once however often it is parsed.  A run that
+ *     fails has no rows.  Any other W: SID_EINVAL from sid_create and
+ *     sid_engine_create.  Host path: sid_windows_host, on the codes before any
+ *     mark.
  *   - Counts layout: profile_t (pileup.hpp:7) = 4 x uint16 {A,C,G,T} per site,
  *     array of structures, 8 bytes per site.
  */
@@ -126,6 +147,9 @@ typedef struct {
     int context;                 /* --context (default 0): with a selection, the N
                                     records before and after every selected record
                                     are emitted too (0 .. 64, else SID_EINVAL)      */
+    int window;                  /* --windows (default 0 = off): the window size of
+                                    the per-window summary (sid_engine_windows);
+                                    negative: SID_EINVAL                            */
 } sid_opts;
 void sid_opts_default(sid_opts* o);
 /* Sets SID_CODE_DROPPED on the n host codes whose label is not `select`, so
@@ -176,6 +200,29 @@ int sid_regions_contains(const sid_regions* r, const char* chrom, size_t chrom_l
 void sid_regions_free(sid_regions* r);
 int sid_regions_mark(const sid_regions* r, const struct sid_sites* s, size_t begin, size_t end,
                      uint8_t* code /* host */);
+
+/* -------------------------------------------------------------- windows --
+ * The rows of the windowed summary (Conventions).  chrom is not NUL-terminated.
+ *
+ * sid_windows_host: the rows of sites [begin, end) on the host path (the
+ *   analogue of sid_select_mark and its siblings): code_all are the codes
+ *   before any selection marked them.  *rows is freed with sid_windows_free.
+ *   SID_EINVAL for a window outside 1 .. 2^31-1, a range outside the sites or
+ *   a NULL pointer.
+ * sid_windows_format: "chrom,start,end,sites,records,het,hom\n" (with_header)
+ *   and a line per row, the integers in decimal.  Returns bytes written in
+ *   *len, or SID_ENOMEM if cap is too small (then *len is a sufficient size),
+ *   as sid_format_csv. */
+typedef struct {
+    const char* chrom;
+    uint32_t chrom_len;
+    int64_t start, end;
+    uint64_t sites, records, het, hom;
+} sid_window;
+int sid_windows_host(const struct sid_sites* s, size_t begin, size_t end, const uint8_t* code_all /* host */,
+                     int window, sid_window** rows, size_t* n);
+void sid_windows_free(sid_window* rows);
+int sid_windows_format(const sid_window* rows, size_t n, int with_header, char* buf, size_t cap, size_t* len);
 
 /* ------------------------------------------------------------- contexts -- */
 typedef struct sid_ctx sid_ctx;
@@ -336,6 +383,12 @@ int sid_dtext_format(sid_ctx* ctx, const sid_dtext* t, size_t begin, size_t end,
                      const double* hom_conf, const double* het_conf, const char* conf_type,
                      sid_write_fn write, void* user, void* stream);
 int sid_dtext_free(sid_dtext* t);
+/* The windowed summary (Conventions; the context's sid_opts.window, else
+ * SID_ESTATE) of sites [begin, end) of a resident shard with the given device
+ * codes: the window stage of the engine over one range, without chunk edges.
+ * *rows is freed with sid_windows_free.  Synchronises. */
+int sid_dtext_windows(sid_ctx* ctx, const sid_dtext* t, size_t begin, size_t end, const uint8_t* code /* device */,
+                      sid_window** rows, size_t* n, void* stream);
 /* -m quality (call.cpp:291-372) over a shard parsed by a context whose method
  * is SID_METHOD_QUALITY (7 fields per line): the read bases and both quality
  * fields are read from the resident text.  snp_prior / significance_level
@@ -485,6 +538,8 @@ typedef struct {
                                     EOF marker) are not uploaded.  bytes_in stays
                                     the text parsed                                 */
     uint64_t bgzf_blocks;        /* ... and their number                            */
+    uint64_t window_rows;        /* sid_opts.window: the rows of the summary (after
+                                    the chunks' rows are stitched; set by the emit)  */
 } sid_run_stats;
 void sid_engine_cfg_default(sid_engine_cfg* cfg);
 int sid_engine_create(const sid_opts* opts, const sid_engine_cfg* cfg, sid_engine** out);
@@ -550,6 +605,11 @@ int sid_engine_profile_load(sid_engine* e, const uint64_t* keys, const uint64_t*
  * SID_ESTATE when that chunk's records did not go through the host arena.
  * With a context: exactly the bytes the chunk contributed to the output. */
 int sid_engine_records(sid_engine* e, uint64_t chunk, const char** bytes, uint64_t* len);
+/* The windowed summary of the run (sid_opts.window != 0), after a successful
+ * sid_engine_emit in every device_sink mode: the rows in file order, owned by
+ * the engine and valid until the next ingest or source.  SID_ESTATE before
+ * that, after a failed run, or without the option. */
+int sid_engine_windows(sid_engine* e, const sid_window** rows, size_t* n);
 /* Measurement: with profiling on, every stage of every chunk is bracketed by
  * a pair of HIP events on its device's compute stream; _read sums the stages'
  * device time over the chunks and devices since the last read (synchronises). */

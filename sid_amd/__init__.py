@@ -50,6 +50,21 @@ class Opts(C.Structure):
     _fields_ = [("method", C.c_int), ("estimate_prior", C.c_int), ("snp_prior", C.c_double),
                 ("significance_level", C.c_double), ("site_error_threshold", C.c_double), ("select", C.c_int),
                 ("regions", C.c_void_p), ("context", C.c_int)]
+    # sid_opts.window, the int behind `context`: the structure's last four bytes (its size is a multiple
+    # of the 8-byte alignment of its doubles and pointer, so they belong to it).  The field list above
+    # ends at `context`, as its users have it; `window` reads and writes those bytes
+    WINDOW_OFFSET = 52
+
+    @property
+    def window(self) -> int:
+        return C.c_int.from_address(C.addressof(self) + self.WINDOW_OFFSET).value
+
+    @window.setter
+    def window(self, v: int):
+        C.c_int.from_address(C.addressof(self) + self.WINDOW_OFFSET).value = int(v)
+
+
+assert Opts.WINDOW_OFFSET == Opts.context.offset + 4 and C.sizeof(Opts) == Opts.WINDOW_OFFSET + 4
 
 
 class Estimate(C.Structure):
@@ -74,7 +89,14 @@ class RunStats(C.Structure):
                 ("emit_s", C.c_double), ("estimate", Estimate), ("chunks_registered", C.c_uint64),
                 ("register_s", C.c_double), ("h2d_s", C.c_double), ("h2d_bytes", C.c_uint64),
                 ("chunks_tiled", C.c_uint64), ("tile_overflows", C.c_uint64),
-                ("tile_overflows_queued", C.c_uint64), ("bgzf_bytes", C.c_uint64), ("bgzf_blocks", C.c_uint64)]
+                ("tile_overflows_queued", C.c_uint64), ("bgzf_bytes", C.c_uint64), ("bgzf_blocks", C.c_uint64),
+                ("window_rows", C.c_uint64)]
+
+
+class Window(C.Structure):
+    """sid_window: one row of the windowed summary (chrom is not NUL-terminated)."""
+    _fields_ = [("chrom", C.c_void_p), ("chrom_len", C.c_uint32), ("start", C.c_int64), ("end", C.c_int64),
+                ("sites", C.c_uint64), ("records", C.c_uint64), ("het", C.c_uint64), ("hom", C.c_uint64)]
 
 
 class Placement(C.Structure):
@@ -100,6 +122,11 @@ SIGNATURES = [
     ("sid_opts_default", None, [C.POINTER(Opts)]),
     ("sid_select_mark", _I, [_P, _SZ, _I]),
     ("sid_context_mark", _I, [_P, _P, _SZ, _I]),
+    ("sid_windows_host", _I, [_P, _SZ, _SZ, _P, _I, C.POINTER(C.POINTER(Window)), C.POINTER(C.c_size_t)]),
+    ("sid_windows_free", None, [C.POINTER(Window)]),
+    ("sid_windows_format", _I, [C.POINTER(Window), _SZ, _I, _P, _SZ, C.POINTER(C.c_size_t)]),
+    ("sid_dtext_windows", _I, [_P, _P, _SZ, _SZ, _P, C.POINTER(C.POINTER(Window)), C.POINTER(C.c_size_t), _P]),
+    ("sid_engine_windows", _I, [_P, C.POINTER(C.POINTER(Window)), C.POINTER(C.c_size_t)]),
     ("sid_regions_from_bed", _I, [C.c_char_p, _SZ, C.POINTER(_P), C.POINTER(C.c_uint64)]),
     ("sid_regions_from_intervals", _I, [C.POINTER(C.c_char_p), _P, _P, _SZ, C.POINTER(_P)]),
     ("sid_regions_intervals", _SZ, [_P]),
@@ -277,7 +304,7 @@ class Regions:
 
 
 def make_opts(method="local", estimate_prior=False, snp_prior=-1.0, significance_level=0.05,
-              site_error_threshold=0.1, select="all", regions=None, context=0) -> Opts:
+              site_error_threshold=0.1, select="all", regions=None, context=0, window=0) -> Opts:
     o = Opts()
     lib().sid_opts_default(C.byref(o))
     o.method = METHODS[method] if isinstance(method, str) else int(method)
@@ -295,7 +322,70 @@ def make_opts(method="local", estimate_prior=False, snp_prior=-1.0, significance
     o.regions = regions._handle() if regions is not None else None
     # (0 .. 64: sid_create / sid_engine_create return SID_EINVAL for another value)
     o.context = int(context)
+    # (0 = off, 1 .. 2^31-1: a negative value is SID_EINVAL there too)
+    o.window = int(window)
     return o
+
+
+def _window_rows(rows, n: int) -> list:
+    """sid_window rows as tuples (chrom, start, end, sites, records, het, hom)."""
+    out = []
+    for k in range(n):
+        r = rows[k]
+        chrom = C.string_at(r.chrom, r.chrom_len) if r.chrom_len else b""
+        out.append((chrom, r.start, r.end, r.sites, r.records, r.het, r.hom))
+    return out
+
+
+def windows_host(sites: "Sites", code_all: np.ndarray, window: int, begin: int = 0, end: int = None) -> list:
+    """sid_windows_host: the rows of the windowed summary of sites [begin, end)
+    from their codes before any selection marked them."""
+    code_all = np.ascontiguousarray(code_all, np.uint8)
+    if end is None:
+        end = len(sites)
+    if code_all.size != len(sites):
+        raise SidError(1, "windows_host: one code per site")
+    rows, n = C.POINTER(Window)(), C.c_size_t(0)
+    check(lib().sid_windows_host(sites.handle, begin, end, _ptr(code_all), int(window), C.byref(rows), C.byref(n)),
+          "sid_windows_host")
+    try:
+        return _window_rows(rows, n.value)
+    finally:
+        lib().sid_windows_free(rows)
+
+
+def windows_format(rows, header: bool = True) -> bytes:
+    """sid_windows_format over rows as windows_host / Engine.windows return them."""
+    rows = list(rows)
+    arr = (Window * max(len(rows), 1))()
+    keep = []
+    for k, (chrom, start, end, sites, records, het, hom) in enumerate(rows):
+        b = C.create_string_buffer(bytes(chrom), len(chrom))
+        keep.append(b)
+        arr[k] = Window(C.cast(b, C.c_void_p).value if len(chrom) else None, len(chrom), start, end, sites, records,
+                        het, hom)
+    n = C.c_size_t(0)
+    st = lib().sid_windows_format(arr, len(rows), int(bool(header)), None, 0, C.byref(n))
+    if st not in (SID_OK, 3):
+        check(st, "sid_windows_format")
+    buf = C.create_string_buffer(max(n.value, 1))
+    check(lib().sid_windows_format(arr, len(rows), int(bool(header)), buf, n.value, C.byref(n)),
+          "sid_windows_format")
+    return buf.raw[:n.value]
+
+
+def dtext_windows(ctx: "Context", dtext: "DText", code_ptr, begin: int = 0, end: int = None, stream=None) -> list:
+    """sid_dtext_windows: the window stage over sites [begin, end) of a
+    resident shard with the given device codes (the context's `window`)."""
+    if end is None:
+        end = len(dtext)
+    rows, n = C.POINTER(Window)(), C.c_size_t(0)
+    check(lib().sid_dtext_windows(ctx.h, dtext.h, begin, end, code_ptr, C.byref(rows), C.byref(n), stream),
+          "sid_dtext_windows")
+    try:
+        return _window_rows(rows, n.value)
+    finally:
+        lib().sid_windows_free(rows)
 
 
 def device_count() -> int:
@@ -841,6 +931,13 @@ class Engine:
             out.append(C.string_at(p, n) if n else b"")
         return b"".join(out)
 
+    def windows(self) -> list:
+        """The windowed summary of the last run (window != 0), after emit:
+        tuples (chrom, start, end, sites, records, het, hom) in file order."""
+        rows, n = C.POINTER(Window)(), C.c_size_t(0)
+        check(lib().sid_engine_windows(self.h, C.byref(rows), C.byref(n)), "sid_engine_windows")
+        return _window_rows(rows, n.value)
+
     def profile(self, enable=True):
         check(lib().sid_engine_profile(self.h, int(bool(enable))), "sid_engine_profile")
 
@@ -854,6 +951,7 @@ class Engine:
         est = self.estimate()
         out, st2 = self.emit(header, sink)
         st.bytes_out, st.emit_s, st.chunks_reloaded = st2.bytes_out, st2.emit_s, st2.chunks_reloaded
+        st.window_rows = st2.window_rows
         st.estimate = est
         return out, st
 

@@ -64,6 +64,7 @@ extern "C" void sid_opts_default(sid_opts* o)
     o->select = SID_SELECT_ALL;
     o->regions = nullptr;
     o->context = 0;
+    o->window = 0;
 }
 
 // GSL 2.7.1 specfunc/gamma.c lngamma_lanczos (x >= 0.5, away from 1 and 2,
@@ -132,6 +133,7 @@ extern "C" int sid_create(int device, const sid_opts* opts, sid_ctx** out)
     *out = nullptr;
     if (opts && (opts->select < SID_SELECT_ALL || opts->select > SID_SELECT_HOM)) return SID_EINVAL;
     if (opts && (opts->context < 0 || opts->context > SID_CONTEXT_MAX)) return SID_EINVAL;
+    if (opts && opts->window < 0) return SID_EINVAL;
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return sid_set_hip_error(e);
     sid_ctx* c = new sid_ctx();
@@ -139,8 +141,12 @@ extern "C" int sid_create(int device, const sid_opts* opts, sid_ctx** out)
     if (opts) c->opts = *opts; else sid_opts_default(&c->opts);
     // a context around a selection: the unselected tables, tails and parse, and the marking stage selects
     // (without a selection the context changes nothing)
-    if (c->opts.context > 0 && (c->opts.select != SID_SELECT_ALL || c->opts.regions)) {
-        c->cx_n = c->opts.context;
+    const bool cx = c->opts.context > 0 && (c->opts.select != SID_SELECT_ALL || c->opts.regions);
+    // a selection by label under --windows goes the same way with N = 0: the window stage needs every
+    // site's label, which the selecting parse and the filtered tables do not keep
+    if (cx || (c->opts.window > 0 && c->opts.select != SID_SELECT_ALL)) {
+        c->cx_on = true;
+        c->cx_n = cx ? c->opts.context : 0;
         c->cx_select = c->opts.select;
         c->opts.select = SID_SELECT_ALL;
     }
@@ -182,8 +188,8 @@ extern "C" int sid_create(int device, const sid_opts* opts, sid_ctx** out)
         c->regtab = sid_regtab{(const uint64_t*)(b + L.c8),   (const uint32_t*)(b + L.clen), (const uint32_t*)(b + L.noff),
                                (const uint32_t*)(b + L.ibeg), (const int32_t*)(b + L.start), (const int32_t*)(b + L.end),
                                b + L.names, L.nc, L.ni};
-        c->has_regions = c->cx_n == 0;
-        c->cx_regions = c->cx_n != 0;
+        c->has_regions = !c->cx_on;
+        c->cx_regions = c->cx_on;
         c->opts.regions = nullptr;
     }
     if (e != hipSuccess) {

@@ -11,7 +11,19 @@
 // Extra long options (no short letter, so they cannot collide with the
 // reference's flags): --devices N, --threads N, --stats, --host-parse,
 // --chunk-bytes N, --hold-bytes N, --retain-bytes N, --host-hold N,
-// --only het|hom|all, --regions FILE, --bgzf, --context N.
+// --only het|hom|all, --regions FILE, --bgzf, --context N, --windows W,
+// --windows-out FILE.
+//
+// --windows W --windows-out FILE (W in 1 .. 2147483647): beside the records,
+// the windowed summary of the run (sid_opts.window, sid.h Conventions) as CSV
+// into FILE -- "chrom,start,end,sites,records,het,hom" and a line per run of
+// consecutive sites with one chrom and one window floor((pos - 1) / W) --
+// written after the records; stdout, stderr and the exit status are as
+// without them, whatever --only, --regions and --context select.  One
+// without the other: "sid: --windows and --windows-out go together"; a W
+// that is no such integer: "sid: --windows: expected 1..2147483647, got ARG";
+// a FILE that cannot be created: "sid: --windows-out: could not open FILE";
+// each on stderr with exit status 1 and nothing on stdout.
 //
 // --context N (0 .. 64): grep -C N over the unselected output -- with --only
 // and / or --regions, every selected record comes with the N records before
@@ -263,6 +275,7 @@ int main(int argc, char** argv)
     sid_opts_default(&opt.o);
     sid_regions* regions = nullptr;   // --regions (kept for the run: --host-parse marks with it)
     std::atexit(free_regions);   // (the ways out that do not go through finish)
+    const char* windows_out = nullptr;   // --windows-out
     static const struct option LONG[] = {{"devices", required_argument, nullptr, 1},
                                          {"threads", required_argument, nullptr, 2},
                                          {"stats", no_argument, nullptr, 3},
@@ -275,6 +288,8 @@ int main(int argc, char** argv)
                                          {"regions", required_argument, nullptr, 10},
                                          {"bgzf", no_argument, nullptr, 11},
                                          {"context", required_argument, nullptr, 12},
+                                         {"windows", required_argument, nullptr, 13},
+                                         {"windows-out", required_argument, nullptr, 14},
                                          {nullptr, 0, nullptr, 0}};
     int flag;
     while ((flag = getopt_long(argc, argv, "E:Rhm:p:r:", LONG, nullptr)) != -1) {
@@ -356,8 +371,40 @@ int main(int argc, char** argv)
             opt.o.context = v;
             break;
         }
+        case 13: {
+            long long v = 0;
+            bool good = *optarg != 0 && std::strlen(optarg) <= 10;
+            for (const char* c = optarg; good && *c; ++c) {
+                good = *c >= '0' && *c <= '9';
+                v = v * 10 + (*c - '0');
+            }
+            if (!good || v < 1 || v > 2147483647LL) {
+                std::fflush(stdout);
+                std::fprintf(stderr, "sid: --windows: expected 1..2147483647, got %s\n", optarg);
+                std::exit(EXIT_FAILURE);
+            }
+            opt.o.window = (int)v;   // (given twice: the last wins)
+            break;
+        }
+        case 14: windows_out = optarg; break;
         default: std::exit(EXIT_FAILURE);
         }
+    }
+    if ((opt.o.window > 0) != (windows_out != nullptr)) {
+        std::fflush(stdout);
+        std::fputs("sid: --windows and --windows-out go together\n", stderr);
+        std::exit(EXIT_FAILURE);
+    }
+    if (windows_out) {   // the file must be creatable; it is written after the records (a failed run leaves none)
+        const bool was = ::access(windows_out, F_OK) == 0;
+        const int fd = ::open(windows_out, O_WRONLY | O_CREAT, 0666);
+        if (fd < 0) {
+            std::fflush(stdout);
+            std::fprintf(stderr, "sid: --windows-out: could not open %s\n", windows_out);
+            std::exit(EXIT_FAILURE);
+        }
+        ::close(fd);
+        if (!was) ::unlink(windows_out);
     }
     if (optind >= argc) {
         std::fflush(stdout);
@@ -459,7 +506,9 @@ int main(int argc, char** argv)
     };
     auto make_ctx = [&](int d) {
         Shard& s = sh[d];
-        CHECK(sid_create(d % ndev, &opt.o, &s.ctx), "context");
+        sid_opts o = opt.o;
+        o.window = 0;   // (this path's rows come from the host codes: sid_windows_host)
+        CHECK(sid_create(d % ndev, &o, &s.ctx), "context");
         HCHECK(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking), "stream");
     };
     auto alloc_out = [&](Shard& s) {
@@ -485,6 +534,25 @@ int main(int argc, char** argv)
         return 0;
     };
     const char* HEADER = "chrom,pos,label,gt,hom_conf,het_conf,conf_type\n";
+    // --windows-out: the rows as CSV, after the records
+    auto write_windows = [&](const sid_window* rows, size_t nrows) {
+        size_t need = 0;
+        (void)sid_windows_format(rows, nrows, 1, nullptr, 0, &need);
+        std::string csv(need, '\0');
+        CHECK(sid_windows_format(rows, nrows, 1, &csv[0], need, &need), "windows");
+        const int fd = ::open(windows_out, O_WRONLY | O_CREAT | O_TRUNC, 0666);
+        size_t off = 0;
+        while (fd >= 0 && off < csv.size()) {
+            const ssize_t w = ::write(fd, csv.data() + off, csv.size() - off);
+            if (w <= 0) break;
+            off += (size_t)w;
+        }
+        if (fd < 0 || off < csv.size() || ::close(fd) != 0) {
+            std::fflush(stdout);
+            std::fprintf(stderr, "sid: --windows-out: could not write %s\n", windows_out);
+            std::exit(EXIT_FAILURE);
+        }
+    };
     // --bgzf: the bytes are not BGZF from their first member on / a member further in is truncated or corrupt
     auto bgzf_error = [&](uint64_t off, bool at_index) {
         std::fflush(stdout);
@@ -535,6 +603,12 @@ int main(int argc, char** argv)
         rc = sid_engine_emit(eng, HEADER, write_all, nullptr, &st);
         if (rc == SID_EIO) std::exit(EXIT_FAILURE);
         CHECK(rc, "emit");
+        if (windows_out) {
+            const sid_window* rows = nullptr;
+            size_t nrows = 0;
+            CHECK(sid_engine_windows(eng, &rows, &nrows), "windows");
+            write_windows(rows, nrows);
+        }
         const double t3 = now();
         std::string place;   // per pipeline: its GPU, the CPUs its threads ran on, its pinned buffers' NUMA nodes
         if (opt.stats)
@@ -558,7 +632,7 @@ int main(int argc, char** argv)
                          "\"bytes_out\": %llu, \"ingest_s\": %.6f, \"chunks_registered\": %llu, "
                          "\"register_s\": %.6f, \"h2d_s\": %.6f, \"h2d_bytes\": %llu, \"chunks_tiled\": %llu, "
                          "\"tile_overflows\": %llu, \"tile_overflows_queued\": %llu, \"bgzf_bytes\": %llu, "
-                         "\"bgzf_blocks\": %llu, \"placement\": [%s], "
+                         "\"bgzf_blocks\": %llu, \"window_rows\": %llu, \"placement\": [%s], "
                          "\"main_entry_unix\": %.6f, \"main_exit_unix\": %.6f}\n",
                          (unsigned long long)st.sites, D, T, tc - t0, t1 - t0, t2 - t1, t3 - t2, t3 - t0,
                          st.sites / std::max(1e-9, t3 - t0), (unsigned long long)st.chunks,
@@ -568,7 +642,7 @@ int main(int argc, char** argv)
                          st.register_s, st.h2d_s, (unsigned long long)st.h2d_bytes,
                          (unsigned long long)st.chunks_tiled, (unsigned long long)st.tile_overflows,
                          (unsigned long long)st.tile_overflows_queued, (unsigned long long)st.bgzf_bytes,
-                         (unsigned long long)st.bgzf_blocks, place.c_str(),
+                         (unsigned long long)st.bgzf_blocks, (unsigned long long)st.window_rows, place.c_str(),
                          t_entry,
                          unix_now());
         // device memory, pinned staging and the mapping go with the process
@@ -693,6 +767,7 @@ int main(int argc, char** argv)
     // ----------------------------------------------------------------- emit --
     std::fputs(HEADER, stdout);
     std::fflush(stdout);
+    size_t window_rows = 0;
     {
         uint8_t* h_code = nullptr;
         double *h_hom = nullptr, *h_het = nullptr;
@@ -712,6 +787,10 @@ int main(int argc, char** argv)
             }
             HCHECK(hipStreamSynchronize(s.stream), "D2H");
         });
+        sid_window* wrows = nullptr;   // --windows: from the codes before the selections mark them
+        size_t nwrows = 0;
+        if (windows_out) CHECK(sid_windows_host(sites, 0, n, h_code, opt.o.window, &wrows, &nwrows), "windows");
+        window_rows = nwrows;
         std::vector<uint8_t> code_all;   // --context: the codes before the selections marked them
         if (opt.o.context > 0 && (opt.o.select != SID_SELECT_ALL || regions)) code_all.assign(h_code, h_code + n);
         CHECK(sid_select_mark(h_code, n, opt.o.select), "select");   // --only: the other labels' sites get no record
@@ -751,15 +830,17 @@ int main(int argc, char** argv)
             std::vector<char>().swap(bufs[b]);
         }
         for (auto& x : th) x.join();
+        if (windows_out) write_windows(wrows, nwrows);
+        sid_windows_free(wrows);
     }
     double t3 = now();
     if (opt.stats) {
         std::fprintf(stderr,
                      "{\"sites\": %zu, \"devices\": %d, \"threads\": %d, \"path\": \"%s\", \"parse_s\": %.6f, "
                      "\"device_s\": %.6f, \"emit_s\": %.6f, \"total_s\": %.6f, \"sites_per_s\": %.1f, "
-                     "\"main_entry_unix\": %.6f, \"main_exit_unix\": %.6f}\n",
+                     "\"window_rows\": %zu, \"main_entry_unix\": %.6f, \"main_exit_unix\": %.6f}\n",
                      n, D, T, "host", t1 - t0, t2 - t1, t3 - t2, t3 - t0,
-                     n / std::max(1e-9, t3 - t0), t_entry, unix_now());
+                     n / std::max(1e-9, t3 - t0), window_rows, t_entry, unix_now());
     }
     // device memory, pinned staging and mappings go with the process: freeing
     // gigabytes of HBM and pinned host memory one by one only delays the exit

@@ -51,6 +51,7 @@
 
 #include "bgzf_dev.h"
 #include "context.h"
+#include "windows.h"
 #include "sid_internal.h"
 #include "synth.h"
 
@@ -246,6 +247,9 @@ struct ChunkRec {
     // formatted (its forced edge records included; what the stitch keeps of them is decided at the emit)
     sid_cx_desc cx{};
     uint64_t cx_total = 0;
+    // the windowed summary (sid_opts.window): the chunk's rows, read back with its byte count by the pass
+    // that formats it -- once, whichever pass and path that is
+    sid_win_chunk win;
 };
 
 enum SrcKind { SRC_NONE, SRC_HOST, SRC_FILE, SRC_DEVICE, SRC_SYNTH_HOST, SRC_SYNTH_DEVICE, SRC_BGZF, SRC_BGZF_FILE };
@@ -257,6 +261,11 @@ inline bool src_file(int s) { return s == SRC_FILE || s == SRC_BGZF_FILE; }
 // written whole, its leading bytes -- the previous chunk's lines -- at negative offsets) and behind the
 // last (the last member's trailing bytes, the next chunk's lines)
 constexpr uint64_t ZHEAD = 65536;
+
+// sid_chunk_ws::win_eager: four words of counts, the first rows, the first name bytes
+constexpr size_t WIN_H_ROWS = 32, WIN_H_NAMES = WIN_H_ROWS + SID_WIN_EAGER_ROWS * sizeof(sid_win_row);
+constexpr size_t WIN_H_BYTES = WIN_H_NAMES + SID_WIN_EAGER_NAMES;
+static_assert(WIN_H_BYTES == SID_WIN_EAGER_BYTES, "the device's packed block");
 
 struct Loaded {
     uint64_t j = 0;
@@ -739,6 +748,9 @@ struct sid_engine {
     uint64_t per_chunk_cap = 0;
     sid_estimate est{};
     int cx_n = 0;                    // the context in effect (sid_ctx::cx_n: 0 without a selection)
+    bool cx_on = false;              // ... and whether its route is (sid_ctx::cx_on)
+    sid_win_table win;               // sid_opts.window: the run's rows, stitched by the emit
+    bool win_ready = false;
     bool prof = false;
     double prof_ms[6] = {0, 0, 0, 0, 0, 0};   // sid_engine_prof order: index parse call hist fmt_len fmt_write
     uint64_t prof_chunks = 0;
@@ -905,6 +917,7 @@ extern "C" int sid_engine_create(const sid_opts* opts, const sid_engine_cfg* cfg
     *out = nullptr;
     if (opts && (opts->select < SID_SELECT_ALL || opts->select > SID_SELECT_HOM)) return SID_EINVAL;
     if (opts && (opts->context < 0 || opts->context > SID_CONTEXT_MAX)) return SID_EINVAL;
+    if (opts && opts->window < 0) return SID_EINVAL;
     int nvis = 0;
     if (hipGetDeviceCount(&nvis) != hipSuccess || nvis <= 0) return SID_EHIP;
     sid_engine* e = new sid_engine();
@@ -970,6 +983,7 @@ extern "C" int sid_engine_create(const sid_opts* opts, const sid_engine_cfg* cfg
             return rc;
         }
     e->cx_n = e->devs[0]->ctx->cx_n;
+    e->cx_on = e->devs[0]->ctx->cx_on;
     *out = e;
     return SID_OK;
 }
@@ -986,6 +1000,8 @@ static void drop_source(sid_engine* e)
         r.held = r.kept = r.pre = nullptr;
     }
     e->recs.clear();
+    e->win.clear();
+    e->win_ready = false;
     sid_bgzf_free(e->zidx);
     e->zidx = nullptr;
     e->src = SRC_NONE;
@@ -1760,6 +1776,40 @@ void compute(sid_engine* e, Dev& d, int pass)
     // slots a tile, the next_quad shape)
     bool next_tiled = false, next_quad = false;
     uint32_t next_lg = 0;
+    // the windowed summary: the workspace's set (sid_chunk_ws::win_cur) a chunk's stage wrote -- the next
+    // chunk's tile parse takes the other one before this chunk's rows are read
+    const bool windows = e->opts.window > 0;
+    int next_wset = 0;
+    // (the stage's last kernel stores its counts and first rows into the set's pinned block: win_eager)
+    // after the sync: the set held every row and name of the chunk
+    auto win_fits = [&](int b) {
+        const uint64_t* hw = (const uint64_t*)W.win_eager[b];
+        return hw[0] <= W.win_cap[b] && hw[1] <= W.win_ncap[b];
+    };
+    // ... and the sizes the next chunks' sets get (the tile path has no round trip to size them in)
+    auto win_want = [&](int b) {
+        const uint64_t* hw = (const uint64_t*)W.win_eager[b];
+        W.win_want_rows = std::max<uint64_t>(W.win_want_rows, hw[0] + hw[0] / 2);
+        W.win_want_names = std::max<uint64_t>(W.win_want_names, hw[1] + hw[1] / 2);
+    };
+    // the chunk's rows into its record: the pinned copy, or (more rows than it holds) a copy of their own
+    auto win_take = [&](int b, sid_win_chunk& c) {
+        const char* hb = W.win_eager[b];
+        const uint64_t* hw = (const uint64_t*)hb;
+        const uint64_t nr = hw[0], nn = hw[1];
+        c.rows.resize(nr);
+        c.names.resize(nn);
+        if (nr <= SID_WIN_EAGER_ROWS && nn <= SID_WIN_EAGER_NAMES) {
+            if (nr) std::memcpy(c.rows.data(), hb + WIN_H_ROWS, nr * sizeof(sid_win_row));
+            if (nn) std::memcpy(&c.names[0], hb + WIN_H_NAMES, nn);
+            return hipSuccess;
+        }
+        hipError_t x = hipSuccess;
+        if (nr) x = hipMemcpyAsync(c.rows.data(), W.win_rows[b], nr * sizeof(sid_win_row), hipMemcpyDeviceToHost, d.s_comp);
+        if (x == hipSuccess && nn) x = hipMemcpyAsync(&c.names[0], W.win_names[b], nn, hipMemcpyDeviceToHost, d.s_comp);
+        if (x == hipSuccess) x = sync();
+        return x;
+    };
     auto take = [&](Loaded& out) {
         if (have_next) {
             out = nextL;
@@ -1820,6 +1870,7 @@ void compute(sid_engine* e, Dev& d, int pass)
         bool sunk = false;       // pass 1, device sink: a scratch buffer, dropped
         hipEvent_t pe = nullptr;
         uint64_t n = 0;
+        int wset = pre_tiled ? next_wset : -1;   // the window stage's set of this chunk (none: no stage ran)
         // the tile path: this chunk's records and byte count done (recorded
         // before the next chunk's tile parse is queued behind the writer: the
         // host and the records' D2H wait for this, not for that parse, which
@@ -1886,6 +1937,7 @@ void compute(sid_engine* e, Dev& d, int pass)
                     pe = d.prof_begin(P);
                     rc = sid_chunk_tile_local(d.ctx, &W, L.base, L.c0, L.c1, lg, quad, e->conf_type, d.s_comp);
                     d.prof_end(1, pe);
+                    wset = W.win_cur;
                 }
                 if (rc == SID_OK) {
                     pe = d.prof_begin(P);
@@ -1896,7 +1948,7 @@ void compute(sid_engine* e, Dev& d, int pass)
                 if (rc != SID_OK) return (void)fail(e, rc);
                 // bytes, range flag, sites, parse error key, the most lines in a tile
                 x = hipMemcpyAsync(hs + 8, W.lb + 1, 5 * 8, hipMemcpyDeviceToHost, d.s_comp);
-                if (x == hipSuccess && e->cx_n)
+                if (x == hipSuccess && e->cx_on)
                     x = hipMemcpyAsync(d.h_cx, W.cx_desc, sizeof(sid_cx_desc), hipMemcpyDeviceToHost, d.s_comp);
                 if (x == hipSuccess && (done.ev = d.take_event())) x = hipEventRecord(done.ev, d.s_comp);
                 // the next chunk's tile parse behind this writer (stream order:
@@ -1923,6 +1975,7 @@ void compute(sid_engine* e, Dev& d, int pass)
                         d.prof_end(1, pe2);
                         if (rc2 != SID_OK) return (void)fail(e, rc2);
                         next_tiled = x == hipSuccess;
+                        next_wset = W.win_cur;
                         next_lg = lg2;
                         next_quad = q2;
                     }
@@ -1930,7 +1983,10 @@ void compute(sid_engine* e, Dev& d, int pass)
                 if (x == hipSuccess) x = done.ev ? sync_ev(done.ev) : sync();
                 if (x != hipSuccess) return (void)hipfail(e, x);
                 const uint64_t maxl = hs[12];
-                if (maxl <= lg) {
+                // (rows or names beyond the stage's set: the two-pass path sizes it; the next chunks' sets grow)
+                const bool win_over = windows && maxl <= lg && !win_fits(wset);
+                if (win_over) win_want(wset);
+                if (maxl <= lg && !win_over) {
                     tiled = true;
                     ++d.tiled;
                     n = hs[10];
@@ -1945,9 +2001,11 @@ void compute(sid_engine* e, Dev& d, int pass)
                     cap = 0;
                     via_host = sunk = false;
                     done.drop();
-                    ++d.tile_overflows;
-                    d.tile_over_queued += have_next;
-                    d.tile_over(maxl, quad);
+                    if (!win_over) {
+                        ++d.tile_overflows;
+                        d.tile_over_queued += have_next;
+                        d.tile_over(maxl, quad);
+                    }
                     // this chunk goes the two-pass way through the workspace:
                     // the next chunk's tile parse is dropped (it runs again)
                     W.slot_cap = 0;
@@ -2134,6 +2192,7 @@ void compute(sid_engine* e, Dev& d, int pass)
                               : sid_chunk_fmt_len(&W, L.base, L.c1, n, e->conf_type, d.s_comp);
                 d.prof_end(4, pe);
                 if (rc != SID_OK) return (void)fail(e, rc);
+                wset = W.win_cur;
                 pe = d.prof_begin(P);
                 rc = fused    ? sid_chunk_local_put(d.ctx, &W, L.base, L.c1, n, e->conf_type, out, d.s_comp)
                      : lfused ? sid_chunk_lynch_put(d.ctx, &W, L.base, L.c1, n, out, d.s_comp)
@@ -2141,7 +2200,7 @@ void compute(sid_engine* e, Dev& d, int pass)
                 d.prof_end(5, pe);
                 if (rc != SID_OK) return (void)fail(e, rc);
                 x = hipMemcpyAsync(hs + 8, W.lb + 1, 32, hipMemcpyDeviceToHost, d.s_comp);   // bytes, flags, error
-                if (x == hipSuccess && e->cx_n)
+                if (x == hipSuccess && e->cx_on)
                     x = hipMemcpyAsync(d.h_cx, W.cx_desc, sizeof(sid_cx_desc), hipMemcpyDeviceToHost, d.s_comp);
                 // the next chunk's line index behind the formatter (stream
                 // order: it rewrites W.state only after the formatter has read it)
@@ -2207,9 +2266,18 @@ void compute(sid_engine* e, Dev& d, int pass)
         }
         if (out && hs[9]) return (void)fail(e, SID_ERANGE);
         const uint64_t bytes = hs[8];
-        if (e->cx_n) {   // (read back by the sync that brought the byte count)
+        if (e->cx_on) {   // (read back by the sync that brought the byte count)
             r.cx = out ? *d.h_cx : sid_cx_desc{};   // (a chunk without sites: nothing ran, nothing to stitch)
             r.cx_total = bytes;
+        }
+        if (windows) {   // (likewise; a chunk without sites: no stage ran, no row)
+            r.win.clear();
+            if (out) {
+                if (wset < 0 || !win_fits(wset)) return (void)fail(e, SID_ESTATE);   // (the two-pass stage sized its set)
+                win_want(wset);
+                x = win_take(wset, r.win);
+                if (x != hipSuccess) return (void)hipfail(e, x);
+            }
         }
         release_slot();
         if (pass == 2 && r.kept) {   // kept text done with: back to the pool after this stream's work
@@ -2492,7 +2560,10 @@ static void reset_run(sid_engine* e)
         r.parsed = 0;
         r.cx = sid_cx_desc{};
         r.cx_total = 0;
+        r.win.clear();
     }
+    e->win.clear();
+    e->win_ready = false;
     e->z_bytes = 0;
     e->z_blocks = 0;
     for (auto& dp : e->devs) {
@@ -2841,8 +2912,37 @@ extern "C" int sid_engine_estimate(sid_engine* e, const sid_estimate* given, sid
     return SID_OK;
 }
 
+static int emit_records(sid_engine* e, const char* header, sid_write_fn write, void* user, sid_run_stats* st);
+
+// the records, then (sid_opts.window) the chunks' rows stitched in file order
 extern "C" int sid_engine_emit(sid_engine* e, const char* header, sid_write_fn write, void* user,
                                sid_run_stats* st)
+{
+    const int rc = emit_records(e, header, write, user, st);
+    if (e && e->opts.window > 0 && rc != SID_ESTATE && rc != SID_EINVAL) {
+        e->win.clear();
+        e->win_ready = rc == SID_OK;
+        if (rc == SID_OK) {
+            e->win.window = e->opts.window;
+            for (const auto& r : e->recs) sid_win_stitch_push(&e->win, r.win);
+            e->win.finish();
+        }
+        if (st) st->window_rows = e->win.rows.size();
+    }
+    return rc;
+}
+
+extern "C" int sid_engine_windows(sid_engine* e, const sid_window** rows, size_t* n)
+{
+    if (!e || !rows || !n) return SID_EINVAL;
+    *rows = nullptr, *n = 0;
+    if (e->opts.window <= 0 || !e->win_ready) return SID_ESTATE;
+    *rows = e->win.rows.data();
+    *n = e->win.rows.size();
+    return SID_OK;
+}
+
+static int emit_records(sid_engine* e, const char* header, sid_write_fn write, void* user, sid_run_stats* st)
 {
     if (!e || !e->ingested || !e->estimated) return SID_ESTATE;
     const int sink = e->cfg.device_sink;   // 0 write, 1 HBM only, 2 D2H only
@@ -2860,7 +2960,7 @@ extern "C" int sid_engine_emit(sid_engine* e, const char* header, sid_write_fn w
     if (all_host) {
         uint64_t out = 0;
         bool ok = !(sink == 0 && header && write(user, header, std::strlen(header)) != 0);
-        if (e->cx_n) {   // the forced edge records decided, and cut out
+        if (e->cx_on) {   // the forced edge records decided, and cut out
             if (sink == 0) {
                 CxWriter cw(e, write, user);
                 cw.ok = ok;
@@ -2902,7 +3002,7 @@ extern "C" int sid_engine_emit(sid_engine* e, const char* header, sid_write_fn w
             if (r.pre) d.pool.put(r.pre, r.pre_cap, nullptr);
             r.held = r.kept = r.pre = nullptr;
         }
-        if (e->cx_n) out = cx_settle(e);
+        if (e->cx_on) out = cx_settle(e);
         e->sink_bytes = out;
         if (st) {
             st->chunks_reloaded = 0;
@@ -2941,7 +3041,7 @@ extern "C" int sid_engine_emit(sid_engine* e, const char* header, sid_write_fn w
         // a context: the pieces go through the stitch (cxw; a chunk's descriptor is there before its first
         // piece: the compute thread read it back before it queued the chunk)
         std::unique_ptr<CxWriter> cxw;
-        if (e->cx_n && sink == 0) cxw.reset(new CxWriter(e, write, user));
+        if (e->cx_on && sink == 0) cxw.reset(new CxWriter(e, write, user));
         bool cx_begun = false;
         auto emit_bytes = [&](uint64_t j, const char* p, uint64_t len) {
             if (!cxw) return !(sink == 0 && len && write(user, p, len) != 0);
@@ -3007,7 +3107,7 @@ extern "C" int sid_engine_emit(sid_engine* e, const char* header, sid_write_fn w
         (void)hipSetDevice(dp->device);
         if (hipDeviceSynchronize() != hipSuccess) fail(e, SID_EHIP);
     }
-    const bool cx_done = e->cx_n && e->rc.load() == SID_OK;
+    const bool cx_done = e->cx_on && e->rc.load() == SID_OK;
     const uint64_t cx_out = cx_done ? cx_settle(e) : 0;
     if (st) {
         st->chunks_reloaded = e->reloaded.load();

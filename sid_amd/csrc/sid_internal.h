@@ -131,6 +131,9 @@ struct sid_ctx {
     int cx_n = 0;
     int cx_select = SID_SELECT_ALL;
     bool cx_regions = false;   // regtab holds the set
+    // the route's switch: a context in effect, or (cx_n = 0) a selection by label under sid_opts.window, whose
+    // stage reads every site's label in front of the marking stage
+    bool cx_on = false;
     // measurement (sid_timing_enable / sid_timing_read)
     int timing = 0;
     std::vector<sid_timing_ev> ev_pool, ev_pending;
@@ -212,6 +215,7 @@ struct sid_chunk_ws {
     // and the two carried distances per 512-slot group, the in-chunk verdicts of the forced records, and the
     // chunk's descriptor (context.h), complete after the writer
     int cx_n = 0;
+    bool cx_on = false;
     int cx_select = 0;
     const sid_regtab* cx_regions = nullptr;
     unsigned long long* cx_bits = nullptr;
@@ -219,7 +223,31 @@ struct sid_chunk_ws {
     uint4* cx_car = nullptr;
     uint8_t* cx_hk = nullptr;   // 2 x SID_CONTEXT_MAX bytes: head zone, tail zone
     struct sid_cx_desc* cx_desc = nullptr;
+    // the window stage (the owner's sid_opts.window; windows.h, textpath.hip sid_window_*_kernel), in front
+    // of the marking stages: per 64 slots four ballots, two keys, the head count and its scan (sized with
+    // the sites), and two sets of {counts, rows, name blob} used in turn -- a chunk's tile parse runs behind
+    // the previous chunk's writer, before the host has read that chunk's rows.  win_cnt: [0] the chunk's
+    // rows, [1] the bytes of their names over 8 bytes (above win_cap / win_ncap: the rest was dropped).
+    // win_want_*: the sizes the owner asks for, taken when a set is next used
+    int window = 0;
+    unsigned long long* win_bits = nullptr;
+    void* win_key = nullptr;
+    uint32_t* win_hcnt = nullptr;
+    uint64_t* win_roff = nullptr;
+    unsigned long long* win_cnt[2] = {nullptr, nullptr};
+    struct sid_win_row* win_rows[2] = {nullptr, nullptr};
+    char* win_names[2] = {nullptr, nullptr};
+    char* win_eager[2] = {nullptr, nullptr};   // pinned host memory: the set's counts, first rows and first name
+                                               // bytes, packed by the stage's last kernel (SID_WIN_EAGER_BYTES)
+    unsigned long long* win_h = nullptr;       // pinned: the counts read back to size a set
+    uint32_t win_cap[2] = {0, 0}, win_ncap[2] = {0, 0};
+    uint64_t win_want_rows = 0, win_want_names = 0;
+    int win_cur = 0;            // the set the last stage wrote
 };
+// the rows and name bytes that reach the host with every chunk's byte count (more: a copy of their own),
+// behind four words of counts: one small block (sid_window_pack_kernel; 40 B a row)
+constexpr uint32_t SID_WIN_EAGER_ROWS = 64, SID_WIN_EAGER_NAMES = 512;
+constexpr size_t SID_WIN_EAGER_BYTES = 32 + SID_WIN_EAGER_ROWS * 40 + SID_WIN_EAGER_NAMES;
 // the owner's context options into its workspace (after sid_create)
 void sid_chunk_bind_context(sid_chunk_ws* W, const sid_ctx* ctx);
 int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites);

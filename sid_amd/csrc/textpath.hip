@@ -42,6 +42,7 @@
 #include "../../include/sid.h"
 #include "context.h"
 #include "fmt.h"
+#include "windows.h"
 #include "local_site.h"
 
 namespace {
@@ -4111,6 +4112,332 @@ static void launch_context_edge(const sid_chunk_ws* W, const char* out, hipStrea
     sid_context_edge_kernel<<<2, 64, 0, st>>>(out, W->lb + 1, (uint32_t)W->cx_n, W->cx_hk, W->cx_desc);
 }
 
+// ---------------------------------------------------------------- windows --
+// The windowed summary (sid_opts.window = W; windows.h): the rows of a chunk,
+// a row being a maximal run of consecutive sites with equal (chrom, wi), wi =
+// floor((pos - 1) / W).  The stage reads what the marking stages above read --
+// the slot's site, class word / counts / code and Head, through their loaders
+// -- and runs in front of them, on the unselected labels.  Four steps:
+//   flag   per slot: holds a site, prints a record, is het (wave ballots), and
+//          whether its key differs from the previous site's of its wave (the
+//          ballot's nearest lower lane, its key by shuffle); per wave its first
+//          and last site's key.  A wave's first site waits for the link.
+//   link   one thread per wave: the nearest earlier wave with a site (slots
+//          past a tile's count, empty tiles and empty groups lie between) and
+//          its last key against this wave's first; the chunk's first site is a
+//          head.  The wave's head count, and the bytes of the heads' long names.
+//   scan   exclusive scan of the waves' head counts: their first row's index,
+//          and the chunk's rows (win_cnt[0], read back with the byte count).
+//   fill   a lane per head: its row's key, the chrom's bytes over 8 copied out
+//          of the text, and the popcounts of the three ballots masked to its
+//          run's lanes added to the row; lane 0 adds the lanes in front of the
+//          wave's first head to the row before.  A run of many waves costs three
+//          atomic adds a wave, not one a site.  Rows from `cap` on and names
+//          past `ncap` are dropped: the caller sees the counts and runs the
+//          chunk again with larger buffers.
+// Chroms over 8 bytes compare on their bytes in the text (as reg_name_eq).
+struct WinKey {
+    uint64_t c8;
+    int64_t wi;
+    uint64_t cb;     // clen > 8: the chrom's offset in the text
+    uint32_t clen;
+    uint32_t pad;
+};
+static_assert(sizeof(WinKey) == 32, "two keys a wave");
+
+template <class Off>
+struct WinArgs {
+    RegArgs<Off> A;               // the region stage's view of the sites
+    const char* str1;             // -m local: the class entries ([0] tail length, [1] het)
+    const char* str2;
+    sid_lynch_fmt V;              // REG_LYNCH: the classes
+    int64_t W;
+    unsigned long long* bits;     // per wave of slots: [0] sites [1] records [2] het records [3] heads
+    WinKey* key;                  // per wave: [0] its first site's key, [1] its last site's
+    uint32_t* hcnt;               // per wave: its heads
+    const uint64_t* roff;         // ... and its first head's row
+    unsigned long long* cnt;      // [0] rows [1] name bytes [2] the fill's name cursor
+    sid_win_row* rows;
+    uint32_t cap;
+    char* names;
+    uint32_t ncap;
+};
+
+// bytes [8, clen) of two chroms in the text
+__device__ __noinline__ bool win_name_eq(const char* text, uint64_t len, uint64_t a, uint64_t b, uint32_t clen)
+{
+    if (a == b) return true;
+    Reader Ra{text, len}, Rb{text, len};
+    for (uint32_t j = 8; j < clen; ++j)
+        if (Ra.at(a + j) != Rb.at(b + j)) return false;
+    return true;
+}
+
+__device__ __forceinline__ bool win_key_eq(const char* text, uint64_t len, const WinKey& a, const WinKey& b)
+{
+    if (a.c8 != b.c8 || a.clen != b.clen || a.wi != b.wi) return false;
+    return a.clen <= 8 || win_name_eq(text, len, a.cb, b.cb, a.clen);
+}
+
+__device__ __forceinline__ int64_t win_index(int32_t pos, int64_t W)
+{
+    // (pos - 1 >= 0 and W fit 32 bits: a 32-bit division for every site but those at pos <= 0)
+    if (pos >= 1) return (int64_t)((uint32_t)(pos - 1) / (uint32_t)W);
+    const int64_t p = (int64_t)pos - 1;
+    return -((-p + W - 1) / W);
+}
+
+// the slot's site as the marking stages load it (the unselected parse: no skip word is stored), without
+// their stores
+template <int MODE, bool OPT, class Off>
+__device__ __forceinline__ bool win_site(const RegArgs<Off>& A, uint64_t i, uint32_t* w)
+{
+    *w = 0;
+    if (i >= A.s1) return false;
+    if (MODE == REG_TILE) {
+        *w = A.cls[i];
+        const uint32_t t = slot_tile((uint32_t)i, A.cdiv);
+        const uint32_t j = (uint32_t)i - __umul24(t, A.cap);
+        return j < A.tcnt[t] && *w != SID_CLS_SKIP;
+    }
+    if (MODE == REG_DENSE) {
+        if (OPT) {   // (no class words yet: from the counts)
+            const LocalLen LL{A.len1, A.len2, nullptr, nullptr, nullptr, nullptr};
+            (void)local_site_word<false>(A.counts[i], A.len1, LL, w);
+        } else {
+            *w = A.cls[i];
+        }
+        return *w != SID_CLS_SKIP;
+    }
+    return true;
+}
+
+template <int MODE, bool OPT, class Off>
+__device__ __forceinline__ WinKey win_key(const RegArgs<Off>& A, uint64_t i, uint32_t w, Reader& R, int64_t W)
+{
+    const Head h = cx_head<MODE, OPT>(A, i, w, R);
+    WinKey k;
+    k.c8 = reg_c8(R, h);
+    k.wi = win_index(h.pos, W);
+    k.cb = h.clen > 8 ? h.cb : 0;
+    k.clen = h.clen;
+    k.pad = 0;
+    return k;
+}
+
+template <int MODE, bool OPT, class Off>
+__global__ __launch_bounds__(FTB) void sid_window_flag_kernel(const WinArgs<Off> C)
+{
+    const RegArgs<Off>& A = C.A;
+    const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
+    const uint64_t gw = ((uint64_t)blockIdx.x * FTB + threadIdx.x) >> 6;
+    const uint32_t lane = threadIdx.x & 63u;
+    Reader R{A.text, A.len};
+    uint32_t w;
+    const bool site = win_site<MODE, OPT>(A, i, &w);
+    bool rec = false, het = false;
+    WinKey k{0, 0, 0, 0, 0};
+    if (site) {
+        if (MODE == REG_TILE || MODE == REG_DENSE) {
+            const uint32_t e = cx_entry(w, C.str1, C.str2);
+            if ((e & 0xFFu) == 0xFFu) {   // the fix-up's site: its code
+                const uint32_t c = A.code[i];
+                rec = !(c & SID_CODE_DROPPED);
+                het = (c & SID_CODE_HET) != 0;
+            } else {
+                rec = (e & 0xFFu) != 0;
+                het = (e >> 8) & 1u;
+            }
+        } else if (MODE == REG_LYNCH) {
+            const uint32_t idx = C.V.empty ? 0xFFFFFFFFu : lynch_class(A.counts[i], C.V);
+            if (idx != 0xFFFFFFFFu) {
+                const char* t = C.V.lstr + (size_t)idx * SID_LSTR_BYTES;
+                rec = t[0] != 0;
+                het = t[9] == 'e';   // "het," / "hom,"
+            }
+        } else {
+            const uint32_t c = A.code[i];
+            rec = !(c & SID_CODE_DROPPED);
+            het = (c & SID_CODE_HET) != 0;
+        }
+        k = win_key<MODE, OPT>(A, i, w, R, C.W);
+    }
+    const unsigned long long bs = __ballot(site);
+    if (!bs) {   // (wave-uniform) no site: the link passes over the wave
+        if (lane == 0) C.bits[4 * gw] = 0;
+        return;
+    }
+    // the previous site of the wave: the ballot's nearest lower lane
+    const unsigned long long pm = bs & ((1ull << lane) - 1ull);
+    const int src = pm ? 63 - __clzll((long long)pm) : (int)lane;
+    WinKey p;
+    p.c8 = shfl64(k.c8, src);
+    p.wi = (int64_t)shfl64((uint64_t)k.wi, src);
+    p.cb = shfl64(k.cb, src);
+    p.clen = (uint32_t)__shfl((int)k.clen, src, 64);
+    const bool head = site && pm && !win_key_eq(A.text, A.len, k, p);
+    const unsigned long long br = __ballot(rec), bh = __ballot(rec && het), bd = __ballot(head);
+    const uint32_t nb = wave_sum(head && k.clen > 8 ? k.clen : 0u);
+    if (lane == 0) {
+        C.bits[4 * gw] = bs;
+        C.bits[4 * gw + 1] = br;
+        C.bits[4 * gw + 2] = bh;
+        C.bits[4 * gw + 3] = bd;
+        if (nb) atomicAdd(C.cnt + 1, (unsigned long long)nb);
+    }
+    if (site && !pm) C.key[2 * gw] = k;
+    if (site && !(bs >> lane >> 1)) C.key[2 * gw + 1] = k;
+}
+
+__global__ __launch_bounds__(TB) void sid_window_link_kernel(const char* __restrict__ text, uint64_t len, uint64_t nw,
+                                                             unsigned long long* __restrict__ bits,
+                                                             const WinKey* __restrict__ key,
+                                                             uint32_t* __restrict__ hcnt, unsigned long long* cnt)
+{
+    const uint64_t g = (uint64_t)blockIdx.x * TB + threadIdx.x;
+    if (g >= nw) return;
+    const unsigned long long bs = bits[4 * g];
+    uint32_t n = 0;
+    if (bs) {
+        unsigned long long hd = bits[4 * g + 3];
+        uint64_t v = g;
+        while (v > 0 && bits[4 * (v - 1)] == 0) --v;   // (the sites' ballots: no thread writes them here)
+        const WinKey a = key[2 * g];
+        bool head = true;   // the chunk's first site
+        if (v > 0) {
+            const WinKey b = key[2 * (v - 1) + 1];
+            head = !win_key_eq(text, len, a, b);
+        }
+        if (head) {
+            hd |= bs & (~bs + 1ull);
+            bits[4 * g + 3] = hd;
+            if (a.clen > 8) atomicAdd(cnt + 1, (unsigned long long)a.clen);
+        }
+        n = (uint32_t)__popcll(hd);
+    }
+    hcnt[g] = n;
+}
+
+template <int MODE, bool OPT, class Off>
+__global__ __launch_bounds__(FTB) void sid_window_fill_kernel(const WinArgs<Off> C)
+{
+    const RegArgs<Off>& A = C.A;
+    const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
+    const uint64_t gw = ((uint64_t)blockIdx.x * FTB + threadIdx.x) >> 6;
+    const uint32_t lane = threadIdx.x & 63u;
+    const unsigned long long bs = C.bits[4 * gw];
+    if (!bs) return;   // (wave-uniform)
+    const unsigned long long br = C.bits[4 * gw + 1], bh = C.bits[4 * gw + 2], hd = C.bits[4 * gw + 3];
+    const uint64_t r0 = C.roff[gw];
+    const unsigned long long below = (1ull << lane) - 1ull;
+    if ((hd >> lane) & 1ull) {
+        const uint64_t r = r0 + (uint64_t)__popcll(hd & below);
+        // the run's lanes: from this one to the next head's
+        const unsigned long long up = hd >> lane >> 1;
+        unsigned long long m = ~below;
+        if (up) m &= (1ull << (lane + (uint32_t)__ffsll(up))) - 1ull;   // (the next head's lane <= 63)
+        if (r < C.cap) {
+            Reader R{A.text, A.len};
+            uint32_t w;
+            (void)win_site<MODE, OPT>(A, i, &w);
+            const WinKey k = win_key<MODE, OPT>(A, i, w, R, C.W);
+            sid_win_row* row = C.rows + r;
+            uint32_t name = 0;
+            if (k.clen > 8) {
+                const unsigned long long at = atomicAdd(C.cnt + 2, (unsigned long long)k.clen);
+                name = (uint32_t)min(at, (unsigned long long)0xFFFFFFFFu);
+                if (at + k.clen <= C.ncap)
+                    for (uint32_t j = 0; j < k.clen; ++j) C.names[at + j] = (char)R.at(k.cb + j);
+            }
+            row->wi = k.wi;
+            row->c8 = k.c8;
+            row->clen = k.clen;
+            row->name = name;
+            atomicAdd(&row->sites, (uint32_t)__popcll(bs & m));
+            atomicAdd(&row->records, (uint32_t)__popcll(br & m));
+            atomicAdd(&row->het, (uint32_t)__popcll(bh & m));
+        }
+    }
+    if (lane == 0) {   // the sites in front of the wave's first head: the run of the row before
+        const unsigned long long m = hd ? (hd & (~hd + 1ull)) - 1ull : ~0ull;
+        if ((bs & m) && r0 > 0 && r0 - 1 < C.cap) {
+            sid_win_row* row = C.rows + (r0 - 1);
+            atomicAdd(&row->sites, (uint32_t)__popcll(bs & m));
+            if (br & m) atomicAdd(&row->records, (uint32_t)__popcll(br & m));
+            if (bh & m) atomicAdd(&row->het, (uint32_t)__popcll(bh & m));
+        }
+    }
+}
+
+// The counts, the first SID_WIN_EAGER_ROWS rows and the first SID_WIN_EAGER_NAMES name bytes packed into one
+// small block of pinned host memory, stored by the kernel itself (3 KB; a chunk of 128 MiB at W = 100,000
+// has some 16 rows): the host reads it after the sync that brings the chunk's byte count.  No copy is
+// queued for it: a small device-to-host copy waits on the copy engine behind the records' copies, a
+// millisecond a chunk (measured: C3's PCIe step 111 -> 150 ms with a 16-byte copy per chunk in the stage)
+__global__ __launch_bounds__(256) void sid_window_pack_kernel(const unsigned long long* __restrict__ cnt,
+                                                              const sid_win_row* __restrict__ rows, uint32_t cap,
+                                                              const char* __restrict__ names, uint32_t ncap,
+                                                              char* __restrict__ eager)
+{
+    const uint32_t t = threadIdx.x;
+    if (t < 4) ((unsigned long long*)eager)[t] = t < 3 ? cnt[t] : 0ull;
+    const uint64_t nr = min(min((uint64_t)cnt[0], (uint64_t)cap), (uint64_t)SID_WIN_EAGER_ROWS);
+    const uint64_t* src = (const uint64_t*)rows;
+    uint64_t* dst = (uint64_t*)(eager + 32);
+    for (uint64_t k = t; k < nr * (sizeof(sid_win_row) / 8); k += 256) dst[k] = src[k];
+    const uint64_t nn = min(min((uint64_t)cnt[1], (uint64_t)ncap), (uint64_t)SID_WIN_EAGER_NAMES);
+    char* dn = eager + 32 + SID_WIN_EAGER_ROWS * sizeof(sid_win_row);
+    for (uint64_t k = t; k < nn; k += 256) dn[k] = names[k];
+}
+
+// the counts alone into pinned host memory (the sizing round trip of window_stage)
+__global__ __launch_bounds__(64) void sid_window_cnt_kernel(const unsigned long long* __restrict__ cnt,
+                                                            unsigned long long* __restrict__ host)
+{
+    if (threadIdx.x < 2) host[threadIdx.x] = cnt[threadIdx.x];
+}
+
+// the stage's device buffers for `slots` slots: sid_chunk_ws's win_* (the engine) or a call's own
+struct WinBufs {
+    unsigned long long* bits;
+    WinKey* key;
+    uint32_t* hcnt;     // followed by the scan's workspace
+    uint64_t* roff;
+    unsigned long long* cnt;
+    sid_win_row* rows;
+    uint32_t cap;
+    char* names;
+    uint32_t ncap;
+};
+static uint64_t win_waves(uint64_t slots) { return (slots + FTB - 1) / FTB * (FTB / 64); }
+static size_t win_hcnt_bytes(uint64_t nw) { return ((std::max<uint64_t>(nw, 1) * 4 + 7) & ~(size_t)7) + scan_ws_bytes(nw); }
+
+// flag, link and scan for A's slots: afterwards cnt[0] = the rows, cnt[1] = their long names' bytes
+template <int MODE, bool OPT, class Off>
+static void launch_window_count(WinArgs<Off>& C, const WinBufs& B, hipStream_t st)
+{
+    C.bits = B.bits, C.key = B.key, C.hcnt = B.hcnt, C.roff = B.roff, C.cnt = B.cnt;
+    C.rows = B.rows, C.cap = B.cap, C.names = B.names, C.ncap = B.ncap;
+    const uint64_t nb = (C.A.s1 - C.A.s0 + FTB - 1) / FTB, nw = nb * (FTB / 64);
+    (void)hipMemsetAsync(B.cnt, 0, 3 * 8, st);
+    if (!nb) return;
+    sid_window_flag_kernel<MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(C);
+    sid_window_link_kernel<<<(unsigned)((nw + TB - 1) / TB), TB, 0, st>>>(C.A.text, C.A.len, nw, B.bits, B.key, B.hcnt,
+                                                                          B.cnt);
+    launch_scan(B.hcnt, nw, B.roff, (uint64_t*)B.cnt, nullptr,
+                (uint64_t*)((char*)B.hcnt + ((nw * 4 + 7) & ~(size_t)7)), st);
+}
+// the rows (the first B.cap of them) after launch_window_count
+template <int MODE, bool OPT, class Off>
+static void launch_window_fill(WinArgs<Off>& C, const WinBufs& B, hipStream_t st)
+{
+    C.rows = B.rows, C.cap = B.cap, C.names = B.names, C.ncap = B.ncap;
+    const uint64_t nb = (C.A.s1 - C.A.s0 + FTB - 1) / FTB;
+    if (!nb || !B.cap) return;
+    (void)hipMemsetAsync(B.rows, 0, (size_t)B.cap * sizeof(sid_win_row), st);
+    sid_window_fill_kernel<MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(C);
+}
+
 // tails of the U classes (one thread each), then the dense codes' lengths
 __global__ __launch_bounds__(256) void sid_lynch_str_kernel(const uint8_t* __restrict__ pcode,
                                                            const double* __restrict__ cc, uint32_t U, CType ct,
@@ -4679,7 +5006,7 @@ extern "C" int sid_dtext_format(sid_ctx* ctx, const sid_dtext* T, size_t begin, 
     // a context: the records outside the dilated selection likewise (the whole range at once: no forced
     // edges), with buffers of this call's own
     void* d_cx = nullptr;
-    if (rc == SID_OK && nb && ctx->cx_n) {
+    if (rc == SID_OK && nb && ctx->cx_on) {
         const uint64_t ng = (n + FTB - 1) / FTB;
         const size_t o_sum = ng * (FTB / 64) * 16, o_car = o_sum + ng * 16, o_hk = o_car + ng * 16;
         const size_t o_desc = (o_hk + 2 * SID_CONTEXT_MAX + 15) & ~(size_t)15;
@@ -4766,6 +5093,68 @@ extern "C" int sid_dtext_format(sid_ctx* ctx, const sid_dtext* T, size_t begin, 
     for (void* p : {(void*)d_bsum, (void*)d_boff, (void*)d_base, (void*)d_bad, (void*)d_rcode, d_cx})
         if (p) (void)hipFree(p);
     return rc;
+}
+
+// The window stage over a resident shard (the engine's, without chunk edges): buffers of this call's own,
+// the rows sized from the counts.
+extern "C" int sid_dtext_windows(sid_ctx* ctx, const sid_dtext* T, size_t begin, size_t end, const uint8_t* d_code,
+                                 sid_window** rows, size_t* n, void* stream)
+{
+    if (!ctx || !T || !rows || !n) return SID_EINVAL;
+    *rows = nullptr, *n = 0;
+    if (end > T->nsites || begin > end || (end > begin && !d_code)) return SID_EINVAL;
+    if (ctx->opts.window <= 0) return SID_ESTATE;
+    TCHECK(hipSetDevice(T->device));
+    hipStream_t st = (hipStream_t)stream;
+    sid_win_table tab;
+    tab.window = ctx->opts.window;
+    const size_t m = end - begin;
+    if (m == 0) return sid_win_export(tab, rows, n);
+    const uint64_t nw = win_waves(m);
+    const size_t o_key = nw * 32, o_hcnt = o_key + nw * 2 * sizeof(WinKey);
+    const size_t o_roff = (o_hcnt + win_hcnt_bytes(nw) + 15) & ~(size_t)15, o_cnt = o_roff + nw * 8;
+    char* d_ws = nullptr;
+    void* d_rows = nullptr;
+    char* d_names = nullptr;
+    int rc = SID_OK;
+    auto hip = [&](hipError_t x) {
+        if (x != hipSuccess && rc == SID_OK) rc = sid_set_hip_error(x);
+        return rc == SID_OK;
+    };
+    sid_win_chunk ch;
+    unsigned long long need[2] = {0, 0};
+    if (hip(hipMalloc(&d_ws, o_cnt + 4 * 8))) {
+        WinBufs B{(unsigned long long*)d_ws, (WinKey*)(d_ws + o_key), (uint32_t*)(d_ws + o_hcnt),
+                  (uint64_t*)(d_ws + o_roff), (unsigned long long*)(d_ws + o_cnt), nullptr, 0, nullptr, 0};
+        WinArgs<uint64_t> C{};
+        C.A.text = T->d_text, C.A.len = T->len, C.A.starts = T->d_starts, C.A.hdr = T->d_hdr, C.A.s0 = begin, C.A.s1 = end;
+        C.A.code = const_cast<uint8_t*>(d_code);
+        C.W = ctx->opts.window;
+        launch_window_count<REG_CODE, false>(C, B, st);
+        hip(hipGetLastError());
+        hip(hipMemcpyAsync(need, B.cnt, sizeof need, hipMemcpyDeviceToHost, st));
+        hip(hipStreamSynchronize(st));
+        if (rc == SID_OK && need[0] >= (1ull << 32)) rc = SID_ENOMEM;
+        if (rc == SID_OK && need[0] && hip(hipMalloc(&d_rows, need[0] * sizeof(sid_win_row))) &&
+            hip(hipMalloc(&d_names, std::max<size_t>(need[1], 16)))) {
+            B.rows = (sid_win_row*)d_rows, B.cap = (uint32_t)need[0];
+            B.names = d_names, B.ncap = (uint32_t)std::min<unsigned long long>(need[1], 0xFFFFFFFFull);
+            launch_window_fill<REG_CODE, false>(C, B, st);
+            hip(hipGetLastError());
+            ch.rows.resize(need[0]);
+            ch.names.resize(need[1]);
+            hip(hipMemcpyAsync(ch.rows.data(), d_rows, need[0] * sizeof(sid_win_row), hipMemcpyDeviceToHost, st));
+            if (need[1]) hip(hipMemcpyAsync(&ch.names[0], d_names, need[1], hipMemcpyDeviceToHost, st));
+            hip(hipStreamSynchronize(st));
+        }
+    }
+    for (void* p : {(void*)d_ws, d_rows, (void*)d_names})
+        if (p) (void)hipFree(p);
+    if (rc != SID_OK) return rc;
+    for (const sid_win_row& r : ch.rows)
+        if (r.clen > 8 && (uint64_t)r.name + r.clen > ch.names.size()) return SID_ESTATE;
+    sid_win_stitch_push(&tab, ch);
+    return sid_win_export(tab, rows, n);
 }
 
 extern "C" int sid_format_g6(double v, char* buf, size_t cap)
@@ -4901,16 +5290,86 @@ static uint64_t chunk_tiles(uint64_t c0, uint64_t c1)
     return std::max<uint64_t>((c1 - t0 + TILE - 1) / TILE, 1);
 }
 
+// set b of the window stage's rows and names: at least `rows` rows and `names` bytes (grow-only; hipFree
+// waits for the queued work)
+static int win_fit(sid_chunk_ws* W, int b, uint64_t rows, uint64_t names)
+{
+    if (rows >= (1ull << 32) || names >= (1ull << 32)) return SID_ENOMEM;
+    if (rows > W->win_cap[b]) {
+        if (W->win_rows[b]) (void)hipFree(W->win_rows[b]);
+        W->win_rows[b] = nullptr;
+        W->win_cap[b] = 0;
+        WCHECK(hipMalloc(&W->win_rows[b], rows * sizeof(sid_win_row)));
+        W->win_cap[b] = (uint32_t)rows;
+    }
+    if (names > W->win_ncap[b]) {
+        if (W->win_names[b]) (void)hipFree(W->win_names[b]);
+        W->win_names[b] = nullptr;
+        W->win_ncap[b] = 0;
+        WCHECK(hipMalloc(&W->win_names[b], names));
+        W->win_ncap[b] = (uint32_t)names;
+    }
+    return SID_OK;
+}
+
+// The window stage of one chunk, in front of its marking stages: the next set's counts, rows and names.
+// size (the two-pass formatters, whose caller waits for the device anyway): when the set could be too
+// small for the slots or the text, the counts are read back and the set grown before the fill -- no
+// allocation follows the sites, and W = 1 (a row per site) still fits.  Without it (the tile path: no
+// host round trip) the fill drops what does not fit and the caller, who reads the counts with the byte
+// count, runs the chunk again through the two-pass path.
+template <int MODE, bool OPT, class Off>
+static int window_stage(WinArgs<Off>& C, sid_chunk_ws* W, const sid_ctx* ctx, uint64_t text_bytes, bool size,
+                        hipStream_t st)
+{
+    C.W = W->window;
+    if (ctx) C.str1 = ctx->ws.str1, C.str2 = ctx->ws.str2;
+    const int b = (W->win_cur ^= 1);
+    int rc = win_fit(W, b, W->win_want_rows, W->win_want_names);
+    if (rc != SID_OK) return rc;
+    auto bufs = [&] {
+        return WinBufs{W->win_bits, (WinKey*)W->win_key, W->win_hcnt, W->win_roff, W->win_cnt[b],
+                       W->win_rows[b], W->win_cap[b], W->win_names[b], W->win_ncap[b]};
+    };
+    WinBufs B = bufs();
+    launch_window_count<MODE, OPT>(C, B, st);
+    if (size && (C.A.s1 - C.A.s0 > B.cap || text_bytes > B.ncap)) {
+        unsigned long long* need = W->win_h;   // (pinned, stored by a kernel: no copy behind the records' copies)
+        sid_window_cnt_kernel<<<1, 64, 0, st>>>(B.cnt, need);
+        WCHECK(hipStreamSynchronize(st));
+        if (need[0] > B.cap || need[1] > B.ncap) {
+            rc = win_fit(W, b, need[0] + need[0] / 4, need[1] + need[1] / 4);
+            if (rc != SID_OK) return rc;
+            B = bufs();
+        }
+    }
+    launch_window_fill<MODE, OPT>(C, B, st);
+    sid_window_pack_kernel<<<1, 256, 0, st>>>(B.cnt, B.rows, B.cap, B.names, B.ncap, W->win_eager[b]);
+    WCHECK(hipGetLastError());
+    return SID_OK;
+}
+
 int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites)
 {
     // grow-only; hipFree waits for the device, so buffers still in use by
     // queued work are not released under it (growth is rare: the first
     // chunks, or a chunk far above the usual lines per byte)
     if (!W->state) WCHECK(hipMalloc(&W->state, 8 * sizeof(uint64_t)));
-    if (W->cx_n && !W->cx_desc) {   // the context's descriptor and the forced records' verdict bytes
+    if (W->cx_on && !W->cx_desc) {   // the context's descriptor and the forced records' verdict bytes
         WCHECK(hipMalloc(&W->cx_desc, sizeof(sid_cx_desc)));
         WCHECK(hipMalloc(&W->cx_hk, 2 * SID_CONTEXT_MAX));
         WCHECK(hipMemset(W->cx_desc, 0, sizeof(sid_cx_desc)));
+    }
+    if (W->window && !W->win_h) WCHECK(hipHostMalloc((void**)&W->win_h, 4 * 8, hipHostMallocDefault));
+    if (W->window && !W->win_cnt[0]) {   // the window stage's two sets of counts, rows and names
+        for (int b = 0; b < 2; ++b) {
+            WCHECK(hipMalloc(&W->win_cnt[b], 4 * 8));
+            WCHECK(hipMemset(W->win_cnt[b], 0, 4 * 8));
+            WCHECK(hipHostMalloc((void**)&W->win_eager[b], SID_WIN_EAGER_BYTES, hipHostMallocDefault));
+            std::memset(W->win_eager[b], 0, SID_WIN_EAGER_BYTES);
+            const int rc = win_fit(W, b, 16384, 65536);
+            if (rc != SID_OK) return rc;
+        }
     }
     const uint64_t tiles = ((bytes + 16 + IX_TILE - 1) / IX_TILE + 1) * IX_SUB;   // 4 KiB tiles, in whole index tiles
     if (tiles > W->tile_cap) {
@@ -4931,8 +5390,10 @@ int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites)
         const uint64_t m = std::max<uint64_t>(sites, W->site_cap + W->site_cap / 2);
         for (void* p : {(void*)W->starts, (void*)W->counts, (void*)W->code, (void*)W->hom, (void*)W->het,
                         (void*)W->bsum, (void*)W->boff, (void*)W->hdr, (void*)W->fb, (void*)W->lb, (void*)W->cls,
-                        (void*)W->twv, (void*)W->cx_bits, (void*)W->cx_sum, (void*)W->cx_car})
+                        (void*)W->twv, (void*)W->cx_bits, (void*)W->cx_sum, (void*)W->cx_car, (void*)W->win_bits,
+                        W->win_key, (void*)W->win_hcnt, (void*)W->win_roff})
             if (p) (void)hipFree(p);
+        W->win_bits = nullptr, W->win_key = nullptr, W->win_hcnt = nullptr, W->win_roff = nullptr;
         W->cx_bits = nullptr;
         W->cx_sum = W->cx_car = nullptr;
         W->lb = nullptr;
@@ -4959,11 +5420,18 @@ int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites)
         WCHECK(hipMalloc(&W->bsum, ((nb * 4 + 7) & ~(size_t)7) + scan_ws_bytes(nb)));
         WCHECK(hipMalloc(&W->boff, (nb + 1) * 8));
         WCHECK(hipMalloc(&W->lb, std::max<uint64_t>(nb + 5, 8) * 8));
-        if (W->cx_n) {   // per 512-slot group: 8 waves' two ballots, the summary, the carried distances
+        if (W->cx_on) {   // per 512-slot group: 8 waves' two ballots, the summary, the carried distances
             const uint64_t ng = (m + FTB - 1) / FTB + 1;
             WCHECK(hipMalloc(&W->cx_bits, ng * (FTB / 64) * 16));
             WCHECK(hipMalloc(&W->cx_sum, ng * sizeof(uint4)));
             WCHECK(hipMalloc(&W->cx_car, ng * sizeof(uint4)));
+        }
+        if (W->window) {   // per 64 slots: four ballots, two keys, the head count (+ scan workspace) and its scan
+            const uint64_t nw = win_waves(m) + FTB / 64;
+            WCHECK(hipMalloc(&W->win_bits, nw * 32));
+            WCHECK(hipMalloc(&W->win_key, nw * 2 * sizeof(WinKey)));
+            WCHECK(hipMalloc(&W->win_hcnt, win_hcnt_bytes(nw)));
+            WCHECK(hipMalloc(&W->win_roff, nw * 8));
         }
         W->site_cap = m;
     }
@@ -4975,16 +5443,25 @@ void sid_chunk_release(sid_chunk_ws* W)
     for (void* p : {(void*)W->starts, (void*)W->counts, (void*)W->code, (void*)W->hom, (void*)W->het,
                     (void*)W->bsum, (void*)W->boff, (void*)W->tcnt, (void*)W->toff, (void*)W->state,
                     (void*)W->hdr, (void*)W->fb, (void*)W->masks, (void*)W->lb, (void*)W->cls, (void*)W->twv,
-                    (void*)W->cx_bits, (void*)W->cx_sum, (void*)W->cx_car, (void*)W->cx_hk, (void*)W->cx_desc})
+                    (void*)W->cx_bits, (void*)W->cx_sum, (void*)W->cx_car, (void*)W->cx_hk, (void*)W->cx_desc,
+                    (void*)W->win_bits, W->win_key, (void*)W->win_hcnt, (void*)W->win_roff, (void*)W->win_cnt[0],
+                    (void*)W->win_cnt[1], (void*)W->win_rows[0], (void*)W->win_rows[1], (void*)W->win_names[0],
+                    (void*)W->win_names[1]})
         if (p) (void)hipFree(p);
+    for (void* p : {(void*)W->win_h, (void*)W->win_eager[0], (void*)W->win_eager[1]})
+        if (p) (void)hipHostFree(p);
     const int select = W->select;   // (the owner's options, not the buffers')
     const sid_regtab* regions = W->regions;
     const int cx_n = W->cx_n, cx_select = W->cx_select;
+    const bool cx_on = W->cx_on;
     const sid_regtab* cx_regions = W->cx_regions;
+    const int window = W->window;
     *W = sid_chunk_ws{};
+    W->window = window;
     W->select = select;
     W->regions = regions;
     W->cx_n = cx_n, W->cx_select = cx_select, W->cx_regions = cx_regions;
+    W->cx_on = cx_on;
 }
 
 void sid_chunk_bind_context(sid_chunk_ws* W, const sid_ctx* ctx)
@@ -4992,6 +5469,8 @@ void sid_chunk_bind_context(sid_chunk_ws* W, const sid_ctx* ctx)
     W->select = ctx->opts.select;   // (SID_SELECT_ALL under a context: the marking stage selects)
     W->regions = ctx->has_regions ? &ctx->regtab : nullptr;
     W->cx_n = ctx->cx_n;
+    W->cx_on = ctx->cx_on;
+    W->window = ctx->opts.window;
     W->cx_select = ctx->cx_select;
     W->cx_regions = ctx->cx_regions ? &ctx->regtab : nullptr;
 }
@@ -5106,13 +5585,19 @@ int sid_chunk_fmt_len(sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n
     if (n > W->site_cap) return SID_EINVAL;
     WCHECK(hipMemsetAsync(W->lb, 0, 8 * 8, st));
     const uint64_t nb = (n + FTB - 1) / FTB;
+    if (W->window) {   // the windowed summary, on the codes as the call left them
+        WinArgs<sid_off_t> C{};
+        C.A.text = base, C.A.len = c1, C.A.starts = W->starts, C.A.hdr = W->hdr, C.A.s1 = n, C.A.code = W->code;
+        const int rc = window_stage<REG_CODE, false>(C, W, nullptr, c1, true, st);
+        if (rc != SID_OK) return rc;
+    }
     if (W->regions) {   // the sites outside the region set: dropped in the workspace's codes
         RegArgs<sid_off_t> A{};
         A.text = base, A.len = c1, A.starts = W->starts, A.hdr = W->hdr, A.s1 = n, A.code = W->code;
         A.xm = sel_word(W->select), A.T = *W->regions;
         launch_region_mark<REG_CODE, false>(A, st);
     }
-    if (W->cx_n) {   // the context: the records outside the dilated selection, dropped likewise
+    if (W->cx_on) {   // the context: the records outside the dilated selection, dropped likewise
         CxArgs<sid_off_t> C{};
         C.A.text = base, C.A.len = c1, C.A.starts = W->starts, C.A.hdr = W->hdr, C.A.s1 = n, C.A.code = W->code;
         launch_context_mark<REG_CODE, false>(C, W, nullptr, st);
@@ -5133,7 +5618,7 @@ int sid_chunk_fmt_put(sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n
                             ? SID_OK : SID_EHIP;
     sid_fmt_put_kernel<<<(unsigned)nb, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->code, W->hom, W->het, ct,
                                                     W->boff, W->state, W->lb, out, sel_word(W->select));
-    if (W->cx_n) launch_context_edge(W, out, st);
+    if (W->cx_on) launch_context_edge(W, out, st);
     WCHECK(hipGetLastError());
     return SID_OK;
 }
@@ -5172,6 +5657,17 @@ int sid_chunk_local_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
         sid_local_fixlen_kernel<false><<<64, TB, 0, st>>>(base, c1, W->starts, W->hdr, W->counts, miss, W->lb, ctx->K,
                                                    ctx->d_lnt, ct, W->code, W->hom, W->het, W->bsum, W->lb,
                                                    sel_word(ctx->opts.select));
+    }
+    if (W->window) {   // the windowed summary: on the class words (or the counts) before a mark rewrites them
+        WinArgs<sid_off_t> C{};
+        RegArgs<sid_off_t>& A = C.A;
+        A.text = base, A.len = c1, A.starts = W->starts, A.hdr = W->hdr, A.s1 = n, A.cls = W->cls;
+        A.counts = W->counts, A.code = W->code, A.len1 = ctx->ws.len1, A.len2 = ctx->ws.len2;
+        const int rc = W->cls_ready ? window_stage<REG_DENSE, false>(C, W, ctx, c1, true, st)
+                                    : window_stage<REG_DENSE, true>(C, W, ctx, c1, true, st);
+        if (rc != SID_OK) return rc;
+    }
+    if (nb) {
         if (ctx->has_regions) {
             // the sites outside the region set: the skip word, and their groups' sums again.  Without class
             // words (the length kernel read the counts) the kernel writes them, for the writer
@@ -5186,7 +5682,7 @@ int sid_chunk_local_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
             W->cls_ready = true;
         }
     }
-    if (ctx->cx_n) {   // the context (no groups: the empty descriptor)
+    if (ctx->cx_on) {   // the context (no groups: the empty descriptor)
         CxArgs<sid_off_t> C{};
         RegArgs<sid_off_t>& A = C.A;
         A.text = base, A.len = c1, A.starts = W->starts, A.hdr = W->hdr, A.s1 = n, A.cls = W->cls;
@@ -5215,7 +5711,7 @@ int sid_chunk_local_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
         if (W->slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (slot_tile's exact range: a 4 GiB chunk has fewer)
         const SlotDiv cdiv = slot_div(W->slot_cap);
         const uint32_t xm = sel_word(ctx->opts.select);
-        if (ctx->has_regions || ctx->cx_n) {   // per group, by its record bytes (REG_LDS_MIN): the LDS assembly or the byte stores
+        if (ctx->has_regions || ctx->cx_on) {   // per group, by its record bytes (REG_LDS_MIN): the LDS assembly or the byte stores
             auto put = W->tile_quad ? sid_local_put_reg_kernel<true, false> : sid_local_put_reg_kernel<true, true>;
             put<<<(unsigned)nbs, FTB, 0, st>>>(base, c1, nullptr, W->hdr, W->slots, W->tcnt, W->slot_cap, cdiv, W->twv,
                                                tile_nwv(W->slot_cap), W->counts, W->cls, ctx->ws.str1, ctx->ws.str2,
@@ -5227,7 +5723,7 @@ int sid_chunk_local_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
                                                                     ctx->ws.str1, ctx->ws.str2, W->code, W->hom, W->het,
                                                                     ct, W->bsum, W->boff, W->state, W->lb, out, xm,
                                                                     REG_LDS_MIN);
-            if (ctx->cx_n) launch_context_edge(W, out, st);
+            if (ctx->cx_on) launch_context_edge(W, out, st);
             WCHECK(hipGetLastError());
             return SID_OK;
         }
@@ -5273,7 +5769,7 @@ int sid_chunk_local_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     if (nb == 0) return hipMemcpyAsync(W->lb + 4, W->state + 4, 8, hipMemcpyDeviceToDevice, st) == hipSuccess
                             ? SID_OK : SID_EHIP;
     const uint32_t* cw = W->cls_ready ? W->cls : nullptr;
-    if (ctx->has_regions || ctx->cx_n) {   // (the class words: the parse's, or the marking kernel's; the groups with a record)
+    if (ctx->has_regions || ctx->cx_on) {   // (the class words: the parse's, or the marking kernel's; the groups with a record)
         if (!cw) return SID_ESTATE;
         sid_local_put_reg_kernel<true><<<(unsigned)nb, FTB, 0, st>>>(
             base, c1, W->starts, W->hdr, n, nullptr, 0, SlotDiv{0, 0}, nullptr, 0, W->counts, cw, ctx->ws.str1,
@@ -5290,7 +5786,7 @@ int sid_chunk_local_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
                                           W->counts, cw, ctx->ws.str1, ctx->ws.str2, W->code, W->hom, W->het, ct,
                                           W->boff, W->state, W->lb, out);
     }
-    if (ctx->cx_n) launch_context_edge(W, out, st);
+    if (ctx->cx_on) launch_context_edge(W, out, st);
     WCHECK(hipGetLastError());
     return SID_OK;
 }
@@ -5357,7 +5853,7 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
     const uint64_t slots = ntp * cap;
     if (slots > W->site_cap || ntp > W->tile_cap || slots >= (1ull << 32)) return SID_EINVAL;
     if (ntp * tile_nwv(cap) > W->site_cap / 32 + 1) return SID_EINVAL;   // (never: cap >= 64)
-    if ((ctx->has_regions || ctx->cx_n) && slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (the marking kernels' slot_tile: its exact range, as the writer's)
+    if ((ctx->has_regions || ctx->cx_on || W->window) && slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (the marking kernels' slot_tile: its exact range, as the writer's)
     W->lens_ready = false;
     W->cls_ready = false;
     W->slot_cap = cap;
@@ -5368,7 +5864,12 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
     if (nb) WCHECK(hipMemsetAsync(W->bsum, 0, nb * 4, st));
     if (ntp == 0) {
         WCHECK(hipMemsetAsync(W->state + 4, 0xFF, sizeof(uint64_t), st));
-        if (ctx->cx_n) {   // (the empty descriptor)
+        if (W->window) {   // (no row)
+            WinArgs<sid_off_t> C{};
+            const int rc = window_stage<REG_TILE, false>(C, W, ctx, 0, false, st);
+            if (rc != SID_OK) return rc;
+        }
+        if (ctx->cx_on) {   // (the empty descriptor)
             CxArgs<sid_off_t> C{};
             launch_context_mark<REG_TILE, false>(C, W, ctx, st);
         }
@@ -5385,6 +5886,15 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
     auto serial = sel ? sid_tile_serial_kernel<true, true> : sid_tile_serial_kernel<true>;
     serial<<<TILE_SERIAL_GRID, TB, 0, st>>>(base, c1, W->fb, W->starts, W->lb, W->tcnt, ntp, cap, W->counts, W->hdr,
                                             (unsigned long long*)(W->state + 4), F);
+    if (W->window) {   // the windowed summary: on the class words before a mark rewrites them
+        WinArgs<sid_off_t> C{};
+        RegArgs<sid_off_t>& A = C.A;
+        A.text = base, A.len = c1, A.hdr = W->hdr, A.s1 = slots, A.tcnt = W->tcnt, A.cap = cap, A.cdiv = slot_div(cap);
+        A.twv = W->twv, A.nwv = tile_nwv(cap), A.cls = W->cls, A.code = W->code;
+        const int rc = quad ? window_stage<REG_TILE, false>(C, W, ctx, 0, false, st)
+                            : window_stage<REG_TILE, true>(C, W, ctx, 0, false, st);
+        if (rc != SID_OK) return rc;
+    }
     if (ctx->has_regions) {   // the slots outside the region set: the skip word, and their groups' sums again
         RegArgs<sid_off_t> A{};
         A.text = base, A.len = c1, A.hdr = W->hdr, A.s1 = slots, A.tcnt = W->tcnt, A.cap = cap, A.cdiv = slot_div(cap);
@@ -5394,7 +5904,7 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
         if (quad) launch_region_mark<REG_TILE, false>(A, st);
         else launch_region_mark<REG_TILE, true>(A, st);
     }
-    if (ctx->cx_n) {   // the context: the slots outside the dilated selection likewise
+    if (ctx->cx_on) {   // the context: the slots outside the dilated selection likewise
         CxArgs<sid_off_t> C{};
         RegArgs<sid_off_t>& A = C.A;
         A.text = base, A.len = c1, A.hdr = W->hdr, A.s1 = slots, A.tcnt = W->tcnt, A.cap = cap, A.cdiv = slot_div(cap);
@@ -5461,7 +5971,14 @@ int sid_chunk_lynch_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     if (n > W->site_cap) return SID_EINVAL;
     WCHECK(hipMemsetAsync(W->lb, 0, 8 * 8, st));   // [1] bytes, [2] range flag
     const uint64_t nb = (n + FTB - 1) / FTB;
-    if (ctx->cx_n) {   // the context: counts 0 likewise (no class or no site: the empty descriptor)
+    if (W->window) {   // the windowed summary: on the counts before a mark zeroes them
+        WinArgs<sid_off_t> C{};
+        C.A.text = base, C.A.len = c1, C.A.starts = W->starts, C.A.hdr = W->hdr, C.A.s1 = n, C.A.counts = W->counts;
+        C.V = V;
+        const int rc = window_stage<REG_LYNCH, false>(C, W, nullptr, c1, true, st);
+        if (rc != SID_OK) return rc;
+    }
+    if (ctx->cx_on) {   // the context: counts 0 likewise (no class or no site: the empty descriptor)
         CxArgs<sid_off_t> C{};
         RegArgs<sid_off_t>& A = C.A;
         A.text = base, A.len = c1, A.starts = W->starts, A.hdr = W->hdr, A.s1 = V.empty ? 0 : n, A.counts = W->counts;
@@ -5501,7 +6018,7 @@ int sid_chunk_lynch_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     else
         (ctx->opts.select != SID_SELECT_ALL ? sid_lynch_put_kernel<true> : sid_lynch_put_kernel<false>)
             <<<(unsigned)nb, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->counts, V, W->boff, W->state, W->lb, out);
-    if (ctx->cx_n) launch_context_edge(W, out, st);
+    if (ctx->cx_on) launch_context_edge(W, out, st);
     WCHECK(hipGetLastError());
     return SID_OK;
 }
