@@ -3026,6 +3026,17 @@ __global__ __launch_bounds__(FTB, SID_PUT_WAVES) void sid_local_put_reg_kernel(c
                                state, lb, out, xm);
 }
 
+// a compact word's Head from its wave's entry (tile_wave_store): the chrom from the entry, the position its
+// base plus the word's delta
+__device__ __forceinline__ Head entry_head(const ulonglong2 te, uint32_t w)
+{
+    Head h{0, 0, 0, 0};
+    h.clen = (uint32_t)(te.y >> 32) & 0xFFFu;
+    h.pos = (int32_t)((uint32_t)te.y + ((w >> 20) & (SID_CLS_DPOS - 1)));
+    h.c8 = te.x;
+    return h;
+}
+
 // The sparse -m local writer over the tile parse's slots, for a selection
 // that keeps few records (--only het).  A block walks SPB 512-slot groups; a
 // group without record bytes (its block sum) costs one load.  In the others
@@ -3035,7 +3046,77 @@ __global__ __launch_bounds__(FTB, SID_PUT_WAVES) void sid_local_put_reg_kernel(c
 // at the group's offset + its prefix (no LDS assembly: the records are too
 // few to fill 16-B stores).  The record of a slot is the one
 // sid_local_put_sel_kernel<true, WV> writes.
+// BAND (under a region set or a context): only the groups
+// sid_local_put_reg_kernel leaves, those with fewer than `hi` record bytes.
+// TAG: the out-of-line helpers of each kernel's own (record_put_tail).
 constexpr int SPB = 8;   // groups per block of the sparse writers
+template <bool WV, int TAG, bool BAND>
+__device__ __forceinline__ void local_put_sparse_body(const char* __restrict__ text, uint64_t len,
+                                                      const uint64_t* __restrict__ hdr, uint64_t n,
+                                                      const uint32_t* __restrict__ tcnt, uint32_t cap,
+                                                      SlotDiv cdiv, const ulonglong2* __restrict__ twv,
+                                                      uint32_t nwv, const uint32_t* __restrict__ cwords,
+                                                      const char* __restrict__ str1,
+                                                      const char* __restrict__ str2,
+                                                      const uint8_t* __restrict__ code,
+                                                      const double* __restrict__ hom,
+                                                      const double* __restrict__ het, CType ct,
+                                                      const uint32_t* __restrict__ bsum,
+                                                      const uint64_t* __restrict__ boff,
+                                                      const uint64_t* state, unsigned long long* lb,
+                                                      char* __restrict__ out, uint32_t xm, uint32_t hi)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) lb[4] = state[4];
+    const uint64_t nb = (n + FTB - 1) / FTB;
+    for (int it = 0; it < SPB; ++it) {
+        const uint64_t b = (uint64_t)blockIdx.x * SPB + it;
+        if (b >= nb) break;
+        const uint32_t bs = bsum[b];   // (block-uniform: one address)
+        if (bs == 0 || (BAND && bs >= hi)) continue;
+        const uint64_t i = b * FTB + threadIdx.x;
+        int l = 0;
+        Head h{0, 0, 0, 0};
+        uint4 ea = make_uint4(0, 0, 0, 0), eb = ea;
+        bool tab = false;
+        uint8_t c = 0;
+        if (i < n) {
+            const uint32_t w = cwords[i];
+            const uint32_t t = slot_tile((uint32_t)i, cdiv);
+            const uint32_t j = (uint32_t)i - __umul24(t, cap);
+            if (j < tcnt[t] && w != SID_CLS_SKIP) {
+                if (WV && cls_compact(w)) {
+                    h = entry_head(twv[__umul24(t, nwv) + (j >> 6)], w);
+                } else {
+                    Reader R{text, len};
+                    h = slot_head(R, *(const ulonglong2*)(hdr + 2 * i));
+                }
+                if (w != SID_CLS_MISS) {
+                    const uint32_t k = w & 0xFFFFFu;
+                    const uint4* e = (const uint4*)(k < SID_TAB_N ? str1 + (size_t)k * SID_STR_BYTES
+                                                                  : str2 + (size_t)(k - SID_TAB_N) * SID_STR_BYTES);
+                    ea = e[0];
+                    eb = e[1];
+                    tab = (ea.x & 0xFFu) != 0xFFu;
+                }
+                if (tab) {
+                    const uint32_t f = (w >> 28) & 3u, s2 = w >> 30;
+                    const bool het_l = (ea.x >> 8) & 1u;
+                    c = (uint8_t)(f | ((het_l ? s2 : f) << 2) | (het_l ? 0x80u : 0u));
+                    l = code_out(c, xm) ? 0 : local_rec_len(h, ea.x & 0xFFu);
+                } else {   // the fix-up's site
+                    c = code[i];
+                    l = code_out(c, xm) ? 0 : miss_len<TAG>(h, c, hom[i], het[i], ct);
+                }
+            }
+        }
+        uint32_t tot;
+        const uint32_t my = block_exscan<FTB>((uint32_t)l, &tot);
+        char* const dst = out + boff[b] + my;
+        if (l && tab) record_put_tail<TAG>(text, len, h, c, ea, eb, dst);
+        else if (l) miss_put<TAG>(text, len, h, c, hom[i], het[i], ct, dst);
+    }
+}
+
 template <bool WV>
 __global__ __launch_bounds__(FTB) void sid_local_put_sparse_kernel(const char* __restrict__ text, uint64_t len,
                                                                   const uint64_t* __restrict__ hdr, uint64_t n,
@@ -3052,64 +3133,11 @@ __global__ __launch_bounds__(FTB) void sid_local_put_sparse_kernel(const char* _
                                                                   const uint64_t* state, unsigned long long* lb,
                                                                   char* __restrict__ out, uint32_t xm)
 {
-    if (blockIdx.x == 0 && threadIdx.x == 0) lb[4] = state[4];
-    const uint64_t nb = (n + FTB - 1) / FTB;
-    for (int it = 0; it < SPB; ++it) {
-        const uint64_t b = (uint64_t)blockIdx.x * SPB + it;
-        if (b >= nb) break;
-        if (bsum[b] == 0) continue;   // (block-uniform: one address)
-        const uint64_t i = b * FTB + threadIdx.x;
-        int l = 0;
-        Head h{0, 0, 0, 0};
-        uint4 ea = make_uint4(0, 0, 0, 0), eb = ea;
-        bool tab = false;
-        uint8_t c = 0;
-        if (i < n) {
-            const uint32_t w = cwords[i];
-            const uint32_t t = slot_tile((uint32_t)i, cdiv);
-            const uint32_t j = (uint32_t)i - __umul24(t, cap);
-            if (j < tcnt[t] && w != SID_CLS_SKIP) {
-                if (WV && cls_compact(w)) {   // (the entry: tile_wave_store)
-                    const ulonglong2 te = twv[__umul24(t, nwv) + (j >> 6)];
-                    const uint32_t dp = (w >> 20) & (SID_CLS_DPOS - 1);
-                    h.clen = (uint32_t)(te.y >> 32) & 0xFFFu;
-                    h.pos = (int32_t)((uint32_t)te.y + dp);
-                    h.c8 = te.x;
-                    h.cb = 0;
-                } else {
-                    Reader R{text, len};
-                    h = slot_head(R, *(const ulonglong2*)(hdr + 2 * i));
-                }
-                if (w != SID_CLS_MISS) {
-                    const uint32_t k = w & 0xFFFFFu;
-                    const uint4* e = (const uint4*)(k < SID_TAB_N ? str1 + (size_t)k * SID_STR_BYTES
-                                                                  : str2 + (size_t)(k - SID_TAB_N) * SID_STR_BYTES);
-                    ea = e[0];
-                    eb = e[1];
-                    tab = (ea.x & 0xFFu) != 0xFFu;
-                }
-                if (tab) {
-                    const uint32_t f = (w >> 28) & 3u, s2 = w >> 30;
-                    const bool het_l = (ea.x >> 8) & 1u;
-                    c = (uint8_t)(f | ((het_l ? s2 : f) << 2) | (het_l ? 0x80u : 0u));
-                    l = code_out(c, xm) ? 0 : local_rec_len(h, ea.x & 0xFFu);
-                } else {   // the fix-up's site
-                    c = code[i];
-                    l = code_out(c, xm) ? 0 : miss_len<1>(h, c, hom[i], het[i], ct);
-                }
-            }
-        }
-        uint32_t tot;
-        const uint32_t my = block_exscan<FTB>((uint32_t)l, &tot);
-        char* const dst = out + boff[b] + my;
-        if (l && tab) record_put_tail<1>(text, len, h, c, ea, eb, dst);
-        else if (l) miss_put<1>(text, len, h, c, hom[i], het[i], ct, dst);
-    }
+    local_put_sparse_body<WV, 1, false>(text, len, hdr, n, tcnt, cap, cdiv, twv, nwv, cwords, str1, str2, code, hom, het,
+                                        ct, bsum, boff, state, lb, out, xm, 0u);
 }
 
-// The same writer under a region set, a copy of its own (the kernel above keeps
-// its code): only the groups sid_local_put_reg_kernel leaves, those with fewer
-// than `hi` record bytes, and out-of-line helpers of its own (TAG 2).
+// the same writer behind sid_local_put_reg_kernel (a region set, a context)
 template <bool WV>
 __global__ __launch_bounds__(FTB) void sid_local_put_reg_sparse_kernel(const char* __restrict__ text, uint64_t len,
                                                                   const uint64_t* __restrict__ hdr, uint64_t n,
@@ -3126,60 +3154,8 @@ __global__ __launch_bounds__(FTB) void sid_local_put_reg_sparse_kernel(const cha
                                                                   const uint64_t* state, unsigned long long* lb,
                                                                   char* __restrict__ out, uint32_t xm, uint32_t hi)
 {
-    if (blockIdx.x == 0 && threadIdx.x == 0) lb[4] = state[4];
-    const uint64_t nb = (n + FTB - 1) / FTB;
-    for (int it = 0; it < SPB; ++it) {
-        const uint64_t b = (uint64_t)blockIdx.x * SPB + it;
-        if (b >= nb) break;
-        const uint32_t bs = bsum[b];   // (block-uniform: one address)
-        if (bs == 0 || bs >= hi) continue;
-        const uint64_t i = b * FTB + threadIdx.x;
-        int l = 0;
-        Head h{0, 0, 0, 0};
-        uint4 ea = make_uint4(0, 0, 0, 0), eb = ea;
-        bool tab = false;
-        uint8_t c = 0;
-        if (i < n) {
-            const uint32_t w = cwords[i];
-            const uint32_t t = slot_tile((uint32_t)i, cdiv);
-            const uint32_t j = (uint32_t)i - __umul24(t, cap);
-            if (j < tcnt[t] && w != SID_CLS_SKIP) {
-                if (WV && cls_compact(w)) {   // (the entry: tile_wave_store)
-                    const ulonglong2 te = twv[__umul24(t, nwv) + (j >> 6)];
-                    const uint32_t dp = (w >> 20) & (SID_CLS_DPOS - 1);
-                    h.clen = (uint32_t)(te.y >> 32) & 0xFFFu;
-                    h.pos = (int32_t)((uint32_t)te.y + dp);
-                    h.c8 = te.x;
-                    h.cb = 0;
-                } else {
-                    Reader R{text, len};
-                    h = slot_head(R, *(const ulonglong2*)(hdr + 2 * i));
-                }
-                if (w != SID_CLS_MISS) {
-                    const uint32_t k = w & 0xFFFFFu;
-                    const uint4* e = (const uint4*)(k < SID_TAB_N ? str1 + (size_t)k * SID_STR_BYTES
-                                                                  : str2 + (size_t)(k - SID_TAB_N) * SID_STR_BYTES);
-                    ea = e[0];
-                    eb = e[1];
-                    tab = (ea.x & 0xFFu) != 0xFFu;
-                }
-                if (tab) {
-                    const uint32_t f = (w >> 28) & 3u, s2 = w >> 30;
-                    const bool het_l = (ea.x >> 8) & 1u;
-                    c = (uint8_t)(f | ((het_l ? s2 : f) << 2) | (het_l ? 0x80u : 0u));
-                    l = code_out(c, xm) ? 0 : local_rec_len(h, ea.x & 0xFFu);
-                } else {   // the fix-up's site
-                    c = code[i];
-                    l = code_out(c, xm) ? 0 : miss_len<2>(h, c, hom[i], het[i], ct);
-                }
-            }
-        }
-        uint32_t tot;
-        const uint32_t my = block_exscan<FTB>((uint32_t)l, &tot);
-        char* const dst = out + boff[b] + my;
-        if (l && tab) record_put_tail<2>(text, len, h, c, ea, eb, dst);
-        else if (l) miss_put<2>(text, len, h, c, hom[i], het[i], ct, dst);
-    }
+    local_put_sparse_body<WV, 2, true>(text, len, hdr, n, tcnt, cap, cdiv, twv, nwv, cwords, str1, str2, code, hom, het,
+                                       ct, bsum, boff, state, lb, out, xm, hi);
 }
 
 // ---- likelihood_ratio / bayes, fused with the class lookup: a site's
@@ -3598,9 +3574,14 @@ __device__ __forceinline__ bool reg_inside(Reader& R, const Head& h, bool site, 
     return idx < ie && T.start[idx] < h.pos;
 }
 
+// ------------------------------------------------------------ site view --
+// The sites of a chunk as the selection stages (the region mark, the context
+// flag and mark, the window flag and fill) see them: one argument struct per
+// layout, filled by the host's builders (tile_view, dense_view, dtext_view),
+// and one set of loaders over it.
 enum { REG_TILE = 0, REG_DENSE = 1, REG_LYNCH = 2, REG_CODE = 3 };
 template <class Off>
-struct RegArgs {
+struct SiteArgs {
     const char* text;
     uint64_t len;
     const Off* starts;            // (not the tile layout)
@@ -3618,61 +3599,117 @@ struct RegArgs {
     const double* het;
     CType ct;
     uint32_t xm;                  // sel_word: the selection by label
-    const uint8_t* len1;          // -m local: the tail lengths the length pass used
+    const uint8_t* len1;          // -m local: the tail lengths (the region stage: those the length pass used)
     const uint8_t* len2;
+    const char* str1;             // -m local: the class entries ([0] tail length, [1] het)
+    const char* str2;
     uint32_t* bsum;               // -m local: the groups' record bytes
-    sid_regtab T;
+    sid_lynch_fmt V;              // REG_LYNCH: the classes
+    sid_regtab T;                 // the region set (the region stage; the context, when a set selects)
 };
 
 // MODE REG_TILE: OPT = the lane shape (compact words and wave entries);
 // REG_DENSE: OPT = no class words yet (the length kernel read the counts:
-// long lines, or pass 2 of -R -m local on the kept parse), this kernel writes
-// them for the writer
-template <int MODE, bool OPT, class Off>
-__global__ __launch_bounds__(FTB) void sid_region_mark_kernel(const RegArgs<Off> A)
+// long lines, or pass 2 of -R -m local on the kept parse)
+//
+// The slot's site: its class word (-m local) and whether the slot holds a
+// site.  Where the stages differ:
+//   SV_FILTERED  REG_DENSE with OPT, the region stage: the word by A.len1 /
+//                A.len2 as they stand, which may be the filtered twins -- a
+//                class of another label is then SID_CLS_SKIP and no site.
+//                Without it (the context's ranks, the window's site counts:
+//                on the unfiltered tables) such a class stays a site with no
+//                record.
+//   SV_STORE     REG_DENSE with OPT: the word stored to A.cls[i], for the
+//                mark kernel and the writer (not the window stage, which runs
+//                in front of the marking stages without their stores)
+//   te           REG_TILE with OPT: the wave's entry loaded beside the word,
+//                not after it (one round trip, as the writer's), for sv_head
+enum { SV_FILTERED = 1, SV_STORE = 2 };
+template <int MODE, bool OPT, int FLAGS, class Off>
+__device__ __forceinline__ bool sv_site(const SiteArgs<Off>& A, uint64_t i, uint32_t* w, ulonglong2* te = nullptr)
 {
-    const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
-    Reader R{A.text, A.len};
-    bool site = i < A.s1;
-    Head h{0, 0, 0, 0};
-    uint32_t w = 0;
+    *w = 0;
+    if (i >= A.s1) return false;
     if (MODE == REG_TILE) {
-        if (site) {
-            w = A.cls[i];
+        *w = A.cls[i];
+        const uint32_t t = slot_tile((uint32_t)i, A.cdiv);
+        const uint32_t j = (uint32_t)i - __umul24(t, A.cap);
+        if (OPT && te) *te = A.twv[__umul24(t, A.nwv) + (j >> 6)];
+        return j < A.tcnt[t] && *w != SID_CLS_SKIP;
+    }
+    if (MODE == REG_DENSE) {
+        if (OPT) {
+            const LocalLen LL{A.len1, A.len2, nullptr, nullptr, nullptr, nullptr};
+            (void)local_site_word<(FLAGS & SV_FILTERED) != 0>(A.counts[i], A.len1, LL, w);
+            if (FLAGS & SV_STORE) A.cls[i] = *w;
+        } else {
+            *w = A.cls[i];
+        }
+        return *w != SID_CLS_SKIP;
+    }
+    return true;   // (REG_LYNCH, REG_CODE: every site)
+}
+
+// a site's chrom and position (te: the entry sv_site loaded, else loaded here, for a compact word only)
+template <int MODE, bool OPT, class Off>
+__device__ __forceinline__ Head sv_head(const SiteArgs<Off>& A, uint64_t i, uint32_t w, Reader& R,
+                                        const ulonglong2* te = nullptr)
+{
+    if (MODE == REG_TILE) {
+        if (OPT && cls_compact(w)) {
+            if (te) return entry_head(*te, w);
             const uint32_t t = slot_tile((uint32_t)i, A.cdiv);
             const uint32_t j = (uint32_t)i - __umul24(t, A.cap);
-            // (the wave's entry loaded beside the word, not after it: one round trip, as the writer's)
-            ulonglong2 te = make_ulonglong2(0, 0);
-            if (OPT) te = A.twv[__umul24(t, A.nwv) + (j >> 6)];
-            site = j < A.tcnt[t] && w != SID_CLS_SKIP;
-            if (site) {
-                if (OPT && cls_compact(w)) {   // (the entry: tile_wave_store)
-                    h.clen = (uint32_t)(te.y >> 32) & 0xFFFu;
-                    h.pos = (int32_t)((uint32_t)te.y + ((w >> 20) & (SID_CLS_DPOS - 1)));
-                    h.c8 = te.x;
-                } else {
-                    h = slot_head(R, *(const ulonglong2*)(A.hdr + 2 * i));
-                }
-            }
+            return entry_head(A.twv[__umul24(t, A.nwv) + (j >> 6)], w);
         }
-    } else if (MODE == REG_DENSE) {
-        if (site) {
-            if (OPT) {
-                const LocalLen LL{A.len1, A.len2, nullptr, nullptr, nullptr, nullptr};
-                (void)local_site_word<true>(A.counts[i], A.len1, LL, &w);
-                A.cls[i] = w;
-            } else {
-                w = A.cls[i];
-            }
-            site = w != SID_CLS_SKIP;
-            if (site) h = site_head(R, A.starts + i, A.hdr + 2 * i);
-        }
-    } else {
-        if (MODE == REG_CODE && site) site = !code_out(A.code[i], A.xm);   // (no record anyway)
-        if (site) h = site_head(R, A.starts + i, A.hdr ? A.hdr + 2 * i : nullptr);
+        return slot_head(R, *(const ulonglong2*)(A.hdr + 2 * i));
     }
-    const bool in = reg_inside(R, h, site, A.T);
-    const bool drop = site && !in;
+    return site_head(R, A.starts + i, A.hdr ? A.hdr + 2 * i : nullptr);
+}
+
+// -m local: the class entry's first two bytes (tail length, 0xFF: the fix-up's site; het)
+__device__ __forceinline__ uint32_t sv_entry(uint32_t w, const char* str1, const char* str2)
+{
+    if (w == SID_CLS_MISS) return 0xFFu;
+    const uint32_t k = w & 0xFFFFFu;
+    const char* e = k < SID_TAB_N ? str1 + (size_t)k * SID_STR_BYTES : str2 + (size_t)(k - SID_TAB_N) * SID_STR_BYTES;
+    return *(const uint16_t*)e;
+}
+
+// a site's label as its formatter will print it: rec = it has a record, het = the record's label
+template <int MODE, class Off>
+__device__ __forceinline__ void sv_label(const SiteArgs<Off>& A, uint64_t i, uint32_t w, bool* rec, bool* het)
+{
+    *rec = *het = false;
+    uint32_t c = 0;   // the call's code: REG_CODE, and -m local's fix-up sites
+    if (MODE == REG_TILE || MODE == REG_DENSE) {
+        const uint32_t e = sv_entry(w, A.str1, A.str2);
+        if ((e & 0xFFu) != 0xFFu) {
+            *rec = (e & 0xFFu) != 0;
+            *het = (e >> 8) & 1u;
+            return;
+        }
+    } else if (MODE == REG_LYNCH) {
+        const uint32_t idx = A.V.empty ? 0xFFFFFFFFu : lynch_class(A.counts[i], A.V);   // (empty: uniform, no class)
+        if (idx != 0xFFFFFFFFu) {
+            const char* t = A.V.lstr + (size_t)idx * SID_LSTR_BYTES;
+            *rec = t[0] != 0;
+            *het = t[9] == 'e';   // "het," / "hom,"
+        }
+        return;
+    }
+    c = A.code[i];
+    *rec = !(c & SID_CODE_DROPPED);
+    *het = (c & SID_CODE_HET) != 0;
+}
+
+// The marking stages' back end: a dropped site's marker, and for -m local its
+// group's record bytes again (every thread of the block calls it).  keep: the
+// site keeps a record, rec_len() bytes long.
+template <int MODE, class Off, class Len>
+__device__ __forceinline__ void sv_mark(const SiteArgs<Off>& A, uint64_t i, bool drop, bool keep, Len rec_len)
+{
     if (MODE == REG_LYNCH) {
         if (drop) A.counts[i] = 0;
         return;
@@ -3684,28 +3721,44 @@ __global__ __launch_bounds__(FTB) void sid_region_mark_kernel(const RegArgs<Off>
     if (!__syncthreads_or(drop)) return;   // nothing dropped: the group's sum stands
     // nothing kept (most groups of an exon-like set): a group without bytes, which both writers pass over
     // on its sum alone -- its words stay unmarked and unread (195 MB of stores a 50M-site step otherwise)
-    if (!__syncthreads_or(site && in)) {
+    if (!__syncthreads_or(keep)) {
         if (threadIdx.x == 0) A.bsum[blockIdx.x] = 0;
         return;
     }
     if (drop) A.cls[i] = SID_CLS_SKIP;
     int l = 0;
-    if (site && in) {
-        if (w == SID_CLS_MISS) {   // the fix-up's site
-            const uint8_t c = A.code[i];
-            l = code_out(c, A.xm) ? 0 : miss_len<2>(h, c, A.hom[i], A.het[i], A.ct);
-        } else {
-            const uint32_t k = w & 0xFFFFFu;
-            const uint32_t L = k < SID_TAB_N ? A.len1[k] : A.len2[k - SID_TAB_N];
-            l = L && L != 0xFFu ? local_rec_len(h, L) : 0;
-        }
-    }
+    if (keep) l = rec_len();
     const uint32_t tot = block_sum<FTB>((uint32_t)l);
     if (threadIdx.x == 0) A.bsum[blockIdx.x] = tot;
 }
 
+// ----------------------------------------------------------------- regions --
+// REG_DENSE with OPT: this kernel writes the class words, for the writer
 template <int MODE, bool OPT, class Off>
-static void launch_region_mark(const RegArgs<Off>& A, hipStream_t st)
+__global__ __launch_bounds__(FTB) void sid_region_mark_kernel(const SiteArgs<Off> A)
+{
+    const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
+    Reader R{A.text, A.len};
+    uint32_t w;
+    ulonglong2 te = make_ulonglong2(0, 0);
+    bool site = sv_site<MODE, OPT, SV_FILTERED | SV_STORE>(A, i, &w, &te);
+    if (MODE == REG_CODE && site) site = !code_out(A.code[i], A.xm);   // (no record anyway)
+    Head h{0, 0, 0, 0};
+    if (site) h = sv_head<MODE, OPT>(A, i, w, R, &te);
+    const bool in = reg_inside(R, h, site, A.T);
+    sv_mark<MODE>(A, i, site && !in, site && in, [&]() -> int {
+        if (w == SID_CLS_MISS) {   // the fix-up's site
+            const uint8_t c = A.code[i];
+            return code_out(c, A.xm) ? 0 : miss_len<2>(h, c, A.hom[i], A.het[i], A.ct);
+        }
+        const uint32_t k = w & 0xFFFFFu;
+        const uint32_t L = k < SID_TAB_N ? A.len1[k] : A.len2[k - SID_TAB_N];
+        return L && L != 0xFFu ? local_rec_len(h, L) : 0;
+    });
+}
+
+template <int MODE, bool OPT, class Off>
+static void launch_region_mark(const SiteArgs<Off>& A, hipStream_t st)
 {
     const uint64_t nb = (A.s1 - A.s0 + FTB - 1) / FTB;
     if (nb) sid_region_mark_kernel<MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(A);
@@ -3742,10 +3795,7 @@ constexpr uint32_t REG_LDS_MIN = 2048;
 // byte lengths off the chunk's first and last few KB of records.
 template <class Off>
 struct CxArgs {
-    RegArgs<Off> A;               // the region stage's view of the sites (A.T: the set, when reg)
-    const char* str1;             // -m local: the class entries ([0] tail length, [1] het)
-    const char* str2;
-    sid_lynch_fmt V;              // REG_LYNCH: the classes
+    SiteArgs<Off> A;              // the sites (A.T: the set, when reg)
     uint32_t sel;                 // SID_SELECT_*: the label selected (ALL: every label)
     uint32_t reg;                 // a region set selects too
     uint32_t N;
@@ -3758,97 +3808,22 @@ struct CxArgs {
     sid_cx_desc* desc;
 };
 
-// the slot's site as the region stage loads it: the class word (-m local) and whether the slot holds a site
-template <int MODE, bool OPT, class Off>
-__device__ __forceinline__ bool cx_site(const RegArgs<Off>& A, uint64_t i, uint32_t* w)
-{
-    *w = 0;
-    if (i >= A.s1) return false;
-    if (MODE == REG_TILE) {
-        *w = A.cls[i];
-        const uint32_t t = slot_tile((uint32_t)i, A.cdiv);
-        const uint32_t j = (uint32_t)i - __umul24(t, A.cap);
-        return j < A.tcnt[t] && *w != SID_CLS_SKIP;
-    }
-    if (MODE == REG_DENSE) {
-        if (OPT) {   // (no class words yet: written here, for the mark kernel and the writer)
-            const LocalLen LL{A.len1, A.len2, nullptr, nullptr, nullptr, nullptr};
-            (void)local_site_word<false>(A.counts[i], A.len1, LL, w);
-            A.cls[i] = *w;
-        } else {
-            *w = A.cls[i];
-        }
-        return *w != SID_CLS_SKIP;
-    }
-    return true;
-}
-
-template <int MODE, bool OPT, class Off>
-__device__ __forceinline__ Head cx_head(const RegArgs<Off>& A, uint64_t i, uint32_t w, Reader& R)
-{
-    if (MODE == REG_TILE) {
-        if (OPT && cls_compact(w)) {   // (the entry: tile_wave_store)
-            const uint32_t t = slot_tile((uint32_t)i, A.cdiv);
-            const uint32_t j = (uint32_t)i - __umul24(t, A.cap);
-            const ulonglong2 te = A.twv[__umul24(t, A.nwv) + (j >> 6)];
-            Head h{0, 0, 0, 0};
-            h.clen = (uint32_t)(te.y >> 32) & 0xFFFu;
-            h.pos = (int32_t)((uint32_t)te.y + ((w >> 20) & (SID_CLS_DPOS - 1)));
-            h.c8 = te.x;
-            return h;
-        }
-        return slot_head(R, *(const ulonglong2*)(A.hdr + 2 * i));
-    }
-    return site_head(R, A.starts + i, A.hdr ? A.hdr + 2 * i : nullptr);
-}
-
-// -m local: the class entry's first two bytes (tail length, 0xFF: the fix-up's site; het)
-__device__ __forceinline__ uint32_t cx_entry(uint32_t w, const char* str1, const char* str2)
-{
-    if (w == SID_CLS_MISS) return 0xFFu;
-    const uint32_t k = w & 0xFFFFFu;
-    const char* e = k < SID_TAB_N ? str1 + (size_t)k * SID_STR_BYTES : str2 + (size_t)(k - SID_TAB_N) * SID_STR_BYTES;
-    return *(const uint16_t*)e;
-}
-
+// (REG_DENSE with OPT: this kernel writes the class words, for the mark kernel and the writer)
 template <int MODE, bool OPT, class Off>
 __global__ __launch_bounds__(FTB) void sid_context_flag_kernel(const CxArgs<Off> C)
 {
-    const RegArgs<Off>& A = C.A;
+    const SiteArgs<Off>& A = C.A;
     __shared__ unsigned long long mr[FTB / 64], ms[FTB / 64];
     const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
     Reader R{A.text, A.len};
     uint32_t w;
-    const bool site = cx_site<MODE, OPT>(A, i, &w);
+    const bool site = sv_site<MODE, OPT, SV_STORE>(A, i, &w);
     bool rec = false, het = false;
-    if (site) {
-        if (MODE == REG_TILE || MODE == REG_DENSE) {
-            const uint32_t e = cx_entry(w, C.str1, C.str2);
-            if ((e & 0xFFu) == 0xFFu) {   // the fix-up's site: its code
-                const uint32_t c = A.code[i];
-                rec = !(c & SID_CODE_DROPPED);
-                het = (c & SID_CODE_HET) != 0;
-            } else {
-                rec = (e & 0xFFu) != 0;
-                het = (e >> 8) & 1u;
-            }
-        } else if (MODE == REG_LYNCH) {
-            const uint32_t idx = lynch_class(A.counts[i], C.V);
-            if (idx != 0xFFFFFFFFu) {
-                const char* t = C.V.lstr + (size_t)idx * SID_LSTR_BYTES;
-                rec = t[0] != 0;
-                het = t[9] == 'e';   // "het," / "hom,"
-            }
-        } else {
-            const uint32_t c = A.code[i];
-            rec = !(c & SID_CODE_DROPPED);
-            het = (c & SID_CODE_HET) != 0;
-        }
-    }
+    if (site) sv_label<MODE>(A, i, w, &rec, &het);
     bool sel = rec && (C.sel == SID_SELECT_ALL || het == (C.sel == SID_SELECT_HET));
     if (C.reg) {   // (uniform)
         Head h{0, 0, 0, 0};
-        if (sel) h = cx_head<MODE, OPT>(A, i, w, R);
+        if (sel) h = sv_head<MODE, OPT>(A, i, w, R);
         sel = reg_inside(R, h, sel, A.T);
     }
     const unsigned long long br = __ballot(rec), bs = __ballot(sel);
@@ -3947,7 +3922,7 @@ __global__ __launch_bounds__(CX_SCAN_TB) void sid_context_scan_kernel(const uint
 template <int MODE, bool OPT, class Off>
 __global__ __launch_bounds__(FTB) void sid_context_mark_kernel(const CxArgs<Off> C)
 {
-    const RegArgs<Off>& A = C.A;
+    const SiteArgs<Off>& A = C.A;
     __shared__ unsigned long long mr[FTB / 64], ms[FTB / 64];
     const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
     if (threadIdx.x < FTB / 64) {
@@ -4015,32 +3990,14 @@ __global__ __launch_bounds__(FTB) void sid_context_mark_kernel(const CxArgs<Off>
             keep = keep || rank < z || rank >= R - z;
         }
     }
-    const bool drop = rec && !keep;
-    if (MODE == REG_LYNCH) {
-        if (drop) A.counts[i] = 0;
-        return;
-    }
-    if (MODE == REG_CODE) {
-        if (drop) A.code[i] |= SID_CODE_DROPPED;
-        return;
-    }
-    if (!__syncthreads_or(drop)) return;   // nothing dropped: the group's sum stands
-    if (!__syncthreads_or(keep)) {         // nothing kept: a group without bytes (the writers pass over it)
-        if (threadIdx.x == 0) A.bsum[blockIdx.x] = 0;
-        return;
-    }
-    if (drop) A.cls[i] = SID_CLS_SKIP;
-    int l = 0;
-    if (keep) {
+    sv_mark<MODE>(A, i, rec && !keep, keep, [&]() -> int {
         Reader Rd{A.text, A.len};
         const uint32_t w = A.cls[i];
-        const Head h = cx_head<MODE, OPT>(A, i, w, Rd);
-        const uint32_t e = cx_entry(w, C.str1, C.str2);
-        if ((e & 0xFFu) == 0xFFu) l = miss_len<3>(h, A.code[i], A.hom[i], A.het[i], A.ct);
-        else l = local_rec_len(h, e & 0xFFu);
-    }
-    const uint32_t tot = block_sum<FTB>((uint32_t)l);
-    if (threadIdx.x == 0) A.bsum[blockIdx.x] = tot;
+        const Head h = sv_head<MODE, OPT>(A, i, w, Rd);
+        const uint32_t e = sv_entry(w, A.str1, A.str2);
+        if ((e & 0xFFu) == 0xFFu) return miss_len<3>(h, A.code[i], A.hom[i], A.het[i], A.ct);
+        return local_rec_len(h, e & 0xFFu);
+    });
 }
 
 // After the writer: the byte lengths of the chunk's forced records off its
@@ -4094,12 +4051,12 @@ __global__ __launch_bounds__(64) void sid_context_edge_kernel(const char* __rest
 
 // the stage for the groups of A's sites (none: the empty descriptor)
 template <int MODE, bool OPT, class Off>
-static void launch_context_mark(CxArgs<Off>& C, const sid_chunk_ws* W, const sid_ctx* ctx, hipStream_t st,
-                                bool force = true)
+static void launch_context_mark(const SiteArgs<Off>& A, const sid_chunk_ws* W, hipStream_t st, bool force = true)
 {
+    CxArgs<Off> C{};
+    C.A = A;
     C.sel = (uint32_t)W->cx_select, C.reg = W->cx_regions != nullptr, C.N = (uint32_t)W->cx_n, C.force = force;
     if (W->cx_regions) C.A.T = *W->cx_regions;
-    if (ctx) C.str1 = ctx->ws.str1, C.str2 = ctx->ws.str2;
     C.bits = W->cx_bits, C.sum = W->cx_sum, C.car = W->cx_car, C.hk = W->cx_hk, C.desc = W->cx_desc;
     const uint64_t nb = (C.A.s1 - C.A.s0 + FTB - 1) / FTB;
     if (nb) sid_context_flag_kernel<MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(C);
@@ -4147,10 +4104,7 @@ static_assert(sizeof(WinKey) == 32, "two keys a wave");
 
 template <class Off>
 struct WinArgs {
-    RegArgs<Off> A;               // the region stage's view of the sites
-    const char* str1;             // -m local: the class entries ([0] tail length, [1] het)
-    const char* str2;
-    sid_lynch_fmt V;              // REG_LYNCH: the classes
+    SiteArgs<Off> A;              // the sites
     int64_t W;
     unsigned long long* bits;     // per wave of slots: [0] sites [1] records [2] het records [3] heads
     WinKey* key;                  // per wave: [0] its first site's key, [1] its last site's
@@ -4187,35 +4141,10 @@ __device__ __forceinline__ int64_t win_index(int32_t pos, int64_t W)
     return -((-p + W - 1) / W);
 }
 
-// the slot's site as the marking stages load it (the unselected parse: no skip word is stored), without
-// their stores
 template <int MODE, bool OPT, class Off>
-__device__ __forceinline__ bool win_site(const RegArgs<Off>& A, uint64_t i, uint32_t* w)
+__device__ __forceinline__ WinKey win_key(const SiteArgs<Off>& A, uint64_t i, uint32_t w, Reader& R, int64_t W)
 {
-    *w = 0;
-    if (i >= A.s1) return false;
-    if (MODE == REG_TILE) {
-        *w = A.cls[i];
-        const uint32_t t = slot_tile((uint32_t)i, A.cdiv);
-        const uint32_t j = (uint32_t)i - __umul24(t, A.cap);
-        return j < A.tcnt[t] && *w != SID_CLS_SKIP;
-    }
-    if (MODE == REG_DENSE) {
-        if (OPT) {   // (no class words yet: from the counts)
-            const LocalLen LL{A.len1, A.len2, nullptr, nullptr, nullptr, nullptr};
-            (void)local_site_word<false>(A.counts[i], A.len1, LL, w);
-        } else {
-            *w = A.cls[i];
-        }
-        return *w != SID_CLS_SKIP;
-    }
-    return true;
-}
-
-template <int MODE, bool OPT, class Off>
-__device__ __forceinline__ WinKey win_key(const RegArgs<Off>& A, uint64_t i, uint32_t w, Reader& R, int64_t W)
-{
-    const Head h = cx_head<MODE, OPT>(A, i, w, R);
+    const Head h = sv_head<MODE, OPT>(A, i, w, R);
     WinKey k;
     k.c8 = reg_c8(R, h);
     k.wi = win_index(h.pos, W);
@@ -4228,38 +4157,17 @@ __device__ __forceinline__ WinKey win_key(const RegArgs<Off>& A, uint64_t i, uin
 template <int MODE, bool OPT, class Off>
 __global__ __launch_bounds__(FTB) void sid_window_flag_kernel(const WinArgs<Off> C)
 {
-    const RegArgs<Off>& A = C.A;
+    const SiteArgs<Off>& A = C.A;
     const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
     const uint64_t gw = ((uint64_t)blockIdx.x * FTB + threadIdx.x) >> 6;
     const uint32_t lane = threadIdx.x & 63u;
     Reader R{A.text, A.len};
     uint32_t w;
-    const bool site = win_site<MODE, OPT>(A, i, &w);
+    const bool site = sv_site<MODE, OPT, 0>(A, i, &w);   // (the unselected parse: no skip word is stored)
     bool rec = false, het = false;
     WinKey k{0, 0, 0, 0, 0};
     if (site) {
-        if (MODE == REG_TILE || MODE == REG_DENSE) {
-            const uint32_t e = cx_entry(w, C.str1, C.str2);
-            if ((e & 0xFFu) == 0xFFu) {   // the fix-up's site: its code
-                const uint32_t c = A.code[i];
-                rec = !(c & SID_CODE_DROPPED);
-                het = (c & SID_CODE_HET) != 0;
-            } else {
-                rec = (e & 0xFFu) != 0;
-                het = (e >> 8) & 1u;
-            }
-        } else if (MODE == REG_LYNCH) {
-            const uint32_t idx = C.V.empty ? 0xFFFFFFFFu : lynch_class(A.counts[i], C.V);
-            if (idx != 0xFFFFFFFFu) {
-                const char* t = C.V.lstr + (size_t)idx * SID_LSTR_BYTES;
-                rec = t[0] != 0;
-                het = t[9] == 'e';   // "het," / "hom,"
-            }
-        } else {
-            const uint32_t c = A.code[i];
-            rec = !(c & SID_CODE_DROPPED);
-            het = (c & SID_CODE_HET) != 0;
-        }
+        sv_label<MODE>(A, i, w, &rec, &het);
         k = win_key<MODE, OPT>(A, i, w, R, C.W);
     }
     const unsigned long long bs = __ballot(site);
@@ -4321,7 +4229,7 @@ __global__ __launch_bounds__(TB) void sid_window_link_kernel(const char* __restr
 template <int MODE, bool OPT, class Off>
 __global__ __launch_bounds__(FTB) void sid_window_fill_kernel(const WinArgs<Off> C)
 {
-    const RegArgs<Off>& A = C.A;
+    const SiteArgs<Off>& A = C.A;
     const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
     const uint64_t gw = ((uint64_t)blockIdx.x * FTB + threadIdx.x) >> 6;
     const uint32_t lane = threadIdx.x & 63u;
@@ -4339,7 +4247,7 @@ __global__ __launch_bounds__(FTB) void sid_window_fill_kernel(const WinArgs<Off>
         if (r < C.cap) {
             Reader R{A.text, A.len};
             uint32_t w;
-            (void)win_site<MODE, OPT>(A, i, &w);
+            (void)sv_site<MODE, OPT, 0>(A, i, &w);
             const WinKey k = win_key<MODE, OPT>(A, i, w, R, C.W);
             sid_win_row* row = C.rows + r;
             uint32_t name = 0;
@@ -4717,7 +4625,41 @@ struct sid_dtext {
     uint64_t tcap = 0;
 };
 
-#define TCHECK(x)                                                   \
+// The site view (SiteArgs) of each layout, every field the layout has; a stage
+// then sets only what is its own (the region stage: T, xm and the length
+// tables its length pass used; the Lynch stages: V).  ctx: the owner of -m
+// local's tables (null: the formatters that take no context).
+static SiteArgs<sid_off_t> dense_view(const sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n,
+                                      const sid_ctx* ctx = nullptr, const CType& ct = CType{})
+{
+    SiteArgs<sid_off_t> A{};
+    A.text = base, A.len = c1, A.starts = W->starts, A.hdr = W->hdr, A.s1 = n;
+    A.cls = W->cls, A.counts = W->counts, A.code = W->code, A.hom = W->hom, A.het = W->het, A.ct = ct;
+    A.bsum = W->bsum;
+    if (ctx) A.len1 = ctx->ws.len1, A.len2 = ctx->ws.len2, A.str1 = ctx->ws.str1, A.str2 = ctx->ws.str2;
+    return A;
+}
+
+// (the tile parse's slots: W->slots of them, `cap` a tile; no line starts)
+static SiteArgs<sid_off_t> tile_view(const sid_chunk_ws* W, const char* base, uint64_t c1, uint32_t cap,
+                                     const sid_ctx* ctx, const CType& ct)
+{
+    SiteArgs<sid_off_t> A = dense_view(W, base, c1, W->slots, ctx, ct);
+    A.starts = nullptr;
+    A.tcnt = W->tcnt, A.cap = cap, A.cdiv = slot_div(cap), A.twv = W->twv, A.nwv = tile_nwv(cap);
+    return A;
+}
+
+// (a resident text's sites [begin, end) with the call's codes)
+static SiteArgs<uint64_t> dtext_view(const sid_dtext* T, size_t begin, size_t end, uint8_t* code)
+{
+    SiteArgs<uint64_t> A{};
+    A.text = T->d_text, A.len = T->len, A.starts = T->d_starts, A.hdr = T->d_hdr, A.s0 = begin, A.s1 = end;
+    A.code = code;
+    return A;
+}
+
+#define TCHECK(x)                                                  \
     do {                                                            \
         hipError_t e_ = (x);                                        \
         if (e_ != hipSuccess) return sid_set_hip_error(e_);         \
@@ -4996,9 +4938,8 @@ extern "C" int sid_dtext_format(sid_ctx* ctx, const sid_dtext* T, size_t begin, 
     uint8_t* d_rcode = nullptr;
     if (rc == SID_OK && nb && ctx->has_regions && hip(hipMalloc(&d_rcode, end)) &&
         hip(hipMemcpyAsync(d_rcode + begin, d_code + begin, n, hipMemcpyDeviceToDevice, st))) {
-        RegArgs<uint64_t> A{};
-        A.text = T->d_text, A.len = T->len, A.starts = T->d_starts, A.hdr = T->d_hdr, A.s0 = begin, A.s1 = end;
-        A.code = d_rcode, A.xm = sel_word(ctx->opts.select), A.T = ctx->regtab;
+        SiteArgs<uint64_t> A = dtext_view(T, begin, end, d_rcode);
+        A.xm = sel_word(ctx->opts.select), A.T = ctx->regtab;
         launch_region_mark<REG_CODE, false>(A, st);
         hip(hipGetLastError());
         d_code = d_rcode;
@@ -5017,10 +4958,7 @@ extern "C" int sid_dtext_format(sid_ctx* ctx, const sid_dtext* T, size_t begin, 
             X.cx_bits = (unsigned long long*)d_cx, X.cx_sum = (uint4*)((char*)d_cx + o_sum);
             X.cx_car = (uint4*)((char*)d_cx + o_car), X.cx_hk = (uint8_t*)d_cx + o_hk;
             X.cx_desc = (sid_cx_desc*)((char*)d_cx + o_desc);
-            CxArgs<uint64_t> C{};
-            C.A.text = T->d_text, C.A.len = T->len, C.A.starts = T->d_starts, C.A.hdr = T->d_hdr, C.A.s0 = begin, C.A.s1 = end;
-            C.A.code = d_rcode;
-            launch_context_mark<REG_CODE, false>(C, &X, nullptr, st, false);
+            launch_context_mark<REG_CODE, false>(dtext_view(T, begin, end, d_rcode), &X, st, false);
             hip(hipGetLastError());
             d_code = d_rcode;
         }
@@ -5127,8 +5065,7 @@ extern "C" int sid_dtext_windows(sid_ctx* ctx, const sid_dtext* T, size_t begin,
         WinBufs B{(unsigned long long*)d_ws, (WinKey*)(d_ws + o_key), (uint32_t*)(d_ws + o_hcnt),
                   (uint64_t*)(d_ws + o_roff), (unsigned long long*)(d_ws + o_cnt), nullptr, 0, nullptr, 0};
         WinArgs<uint64_t> C{};
-        C.A.text = T->d_text, C.A.len = T->len, C.A.starts = T->d_starts, C.A.hdr = T->d_hdr, C.A.s0 = begin, C.A.s1 = end;
-        C.A.code = const_cast<uint8_t*>(d_code);
+        C.A = dtext_view(T, begin, end, const_cast<uint8_t*>(d_code));
         C.W = ctx->opts.window;
         launch_window_count<REG_CODE, false>(C, B, st);
         hip(hipGetLastError());
@@ -5319,11 +5256,11 @@ static int win_fit(sid_chunk_ws* W, int b, uint64_t rows, uint64_t names)
 // host round trip) the fill drops what does not fit and the caller, who reads the counts with the byte
 // count, runs the chunk again through the two-pass path.
 template <int MODE, bool OPT, class Off>
-static int window_stage(WinArgs<Off>& C, sid_chunk_ws* W, const sid_ctx* ctx, uint64_t text_bytes, bool size,
-                        hipStream_t st)
+static int window_stage(const SiteArgs<Off>& A, sid_chunk_ws* W, uint64_t text_bytes, bool size, hipStream_t st)
 {
+    WinArgs<Off> C{};
+    C.A = A;
     C.W = W->window;
-    if (ctx) C.str1 = ctx->ws.str1, C.str2 = ctx->ws.str2;
     const int b = (W->win_cur ^= 1);
     int rc = win_fit(W, b, W->win_want_rows, W->win_want_names);
     if (rc != SID_OK) return rc;
@@ -5585,23 +5522,18 @@ int sid_chunk_fmt_len(sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n
     if (n > W->site_cap) return SID_EINVAL;
     WCHECK(hipMemsetAsync(W->lb, 0, 8 * 8, st));
     const uint64_t nb = (n + FTB - 1) / FTB;
+    const SiteArgs<sid_off_t> S = dense_view(W, base, c1, n);
     if (W->window) {   // the windowed summary, on the codes as the call left them
-        WinArgs<sid_off_t> C{};
-        C.A.text = base, C.A.len = c1, C.A.starts = W->starts, C.A.hdr = W->hdr, C.A.s1 = n, C.A.code = W->code;
-        const int rc = window_stage<REG_CODE, false>(C, W, nullptr, c1, true, st);
+        const int rc = window_stage<REG_CODE, false>(S, W, c1, true, st);
         if (rc != SID_OK) return rc;
     }
     if (W->regions) {   // the sites outside the region set: dropped in the workspace's codes
-        RegArgs<sid_off_t> A{};
-        A.text = base, A.len = c1, A.starts = W->starts, A.hdr = W->hdr, A.s1 = n, A.code = W->code;
+        SiteArgs<sid_off_t> A = S;
         A.xm = sel_word(W->select), A.T = *W->regions;
         launch_region_mark<REG_CODE, false>(A, st);
     }
-    if (W->cx_on) {   // the context: the records outside the dilated selection, dropped likewise
-        CxArgs<sid_off_t> C{};
-        C.A.text = base, C.A.len = c1, C.A.starts = W->starts, C.A.hdr = W->hdr, C.A.s1 = n, C.A.code = W->code;
-        launch_context_mark<REG_CODE, false>(C, W, nullptr, st);
-    }
+    // the context: the records outside the dilated selection, dropped likewise
+    if (W->cx_on) launch_context_mark<REG_CODE, false>(S, W, st);
     if (nb) sid_fmt_blen_kernel<<<(unsigned)nb, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->code, W->hom,
                                                               W->het, ct, W->bsum, W->lb, sel_word(W->select));
     WCHECK(hipGetLastError());
@@ -5658,38 +5590,25 @@ int sid_chunk_local_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
                                                    ctx->d_lnt, ct, W->code, W->hom, W->het, W->bsum, W->lb,
                                                    sel_word(ctx->opts.select));
     }
+    const SiteArgs<sid_off_t> S = dense_view(W, base, c1, n, ctx, ct);
     if (W->window) {   // the windowed summary: on the class words (or the counts) before a mark rewrites them
-        WinArgs<sid_off_t> C{};
-        RegArgs<sid_off_t>& A = C.A;
-        A.text = base, A.len = c1, A.starts = W->starts, A.hdr = W->hdr, A.s1 = n, A.cls = W->cls;
-        A.counts = W->counts, A.code = W->code, A.len1 = ctx->ws.len1, A.len2 = ctx->ws.len2;
-        const int rc = W->cls_ready ? window_stage<REG_DENSE, false>(C, W, ctx, c1, true, st)
-                                    : window_stage<REG_DENSE, true>(C, W, ctx, c1, true, st);
+        const int rc = W->cls_ready ? window_stage<REG_DENSE, false>(S, W, c1, true, st)
+                                    : window_stage<REG_DENSE, true>(S, W, c1, true, st);
         if (rc != SID_OK) return rc;
     }
-    if (nb) {
-        if (ctx->has_regions) {
-            // the sites outside the region set: the skip word, and their groups' sums again.  Without class
-            // words (the length kernel read the counts) the kernel writes them, for the writer
-            RegArgs<sid_off_t> A{};
-            A.text = base, A.len = c1, A.starts = W->starts, A.hdr = W->hdr, A.s1 = n, A.cls = W->cls;
-            A.counts = W->counts, A.code = W->code, A.hom = W->hom, A.het = W->het, A.ct = ct;
-            A.xm = sel_word(ctx->opts.select);
-            A.len1 = local_sel(ctx) ? ctx->ws.len1f : ctx->ws.len1, A.len2 = local_sel(ctx) ? ctx->ws.len2f : ctx->ws.len2;
-            A.bsum = W->bsum, A.T = ctx->regtab;
-            if (W->cls_ready) launch_region_mark<REG_DENSE, false>(A, st);
-            else launch_region_mark<REG_DENSE, true>(A, st);
-            W->cls_ready = true;
-        }
+    if (nb && ctx->has_regions) {
+        // the sites outside the region set: the skip word, and their groups' sums again.  Without class
+        // words (the length kernel read the counts) the kernel writes them, for the writer
+        SiteArgs<sid_off_t> A = S;
+        A.xm = sel_word(ctx->opts.select), A.T = ctx->regtab;
+        if (local_sel(ctx)) A.len1 = ctx->ws.len1f, A.len2 = ctx->ws.len2f;   // (as the length pass)
+        if (W->cls_ready) launch_region_mark<REG_DENSE, false>(A, st);
+        else launch_region_mark<REG_DENSE, true>(A, st);
+        W->cls_ready = true;
     }
     if (ctx->cx_on) {   // the context (no groups: the empty descriptor)
-        CxArgs<sid_off_t> C{};
-        RegArgs<sid_off_t>& A = C.A;
-        A.text = base, A.len = c1, A.starts = W->starts, A.hdr = W->hdr, A.s1 = n, A.cls = W->cls;
-        A.counts = W->counts, A.code = W->code, A.hom = W->hom, A.het = W->het, A.ct = ct;
-        A.len1 = ctx->ws.len1, A.len2 = ctx->ws.len2, A.bsum = W->bsum;
-        if (W->cls_ready) launch_context_mark<REG_DENSE, false>(C, W, ctx, st);
-        else launch_context_mark<REG_DENSE, true>(C, W, ctx, st);
+        if (W->cls_ready) launch_context_mark<REG_DENSE, false>(S, W, st);
+        else launch_context_mark<REG_DENSE, true>(S, W, st);
         if (nb) W->cls_ready = true;
     }
     W->lens_ready = false;
@@ -5860,19 +5779,16 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
     W->slots = slots;
     W->tile_quad = quad;   // (the quad shape stores no compact words: the writer reads every header pair)
     const uint64_t nb = (slots + FTB - 1) / FTB;
+    const SiteArgs<sid_off_t> S = tile_view(W, base, c1, cap, ctx, ct);   // (the selection stages' view)
     WCHECK(hipMemsetAsync(W->lb, 0, 8 * 8, st));   // [0] fix-up sites [1] bytes [2] range [3] sites [5] max lines [6] [7]
     if (nb) WCHECK(hipMemsetAsync(W->bsum, 0, nb * 4, st));
     if (ntp == 0) {
         WCHECK(hipMemsetAsync(W->state + 4, 0xFF, sizeof(uint64_t), st));
         if (W->window) {   // (no row)
-            WinArgs<sid_off_t> C{};
-            const int rc = window_stage<REG_TILE, false>(C, W, ctx, 0, false, st);
+            const int rc = window_stage<REG_TILE, false>(S, W, 0, false, st);
             if (rc != SID_OK) return rc;
         }
-        if (ctx->cx_on) {   // (the empty descriptor)
-            CxArgs<sid_off_t> C{};
-            launch_context_mark<REG_TILE, false>(C, W, ctx, st);
-        }
+        if (ctx->cx_on) launch_context_mark<REG_TILE, false>(S, W, st);   // (the empty descriptor)
         return fmt_scan(W, nb, st);
     }
     uint32_t* miss = W->fb + 2 * W->site_cap;
@@ -5887,31 +5803,20 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
     serial<<<TILE_SERIAL_GRID, TB, 0, st>>>(base, c1, W->fb, W->starts, W->lb, W->tcnt, ntp, cap, W->counts, W->hdr,
                                             (unsigned long long*)(W->state + 4), F);
     if (W->window) {   // the windowed summary: on the class words before a mark rewrites them
-        WinArgs<sid_off_t> C{};
-        RegArgs<sid_off_t>& A = C.A;
-        A.text = base, A.len = c1, A.hdr = W->hdr, A.s1 = slots, A.tcnt = W->tcnt, A.cap = cap, A.cdiv = slot_div(cap);
-        A.twv = W->twv, A.nwv = tile_nwv(cap), A.cls = W->cls, A.code = W->code;
-        const int rc = quad ? window_stage<REG_TILE, false>(C, W, ctx, 0, false, st)
-                            : window_stage<REG_TILE, true>(C, W, ctx, 0, false, st);
+        const int rc = quad ? window_stage<REG_TILE, false>(S, W, 0, false, st)
+                            : window_stage<REG_TILE, true>(S, W, 0, false, st);
         if (rc != SID_OK) return rc;
     }
     if (ctx->has_regions) {   // the slots outside the region set: the skip word, and their groups' sums again
-        RegArgs<sid_off_t> A{};
-        A.text = base, A.len = c1, A.hdr = W->hdr, A.s1 = slots, A.tcnt = W->tcnt, A.cap = cap, A.cdiv = slot_div(cap);
-        A.twv = W->twv, A.nwv = tile_nwv(cap), A.cls = W->cls, A.code = W->code, A.hom = W->hom, A.het = W->het;
-        A.ct = ct, A.xm = sel_word(ctx->opts.select), A.len1 = LL.len1, A.len2 = LL.len2, A.bsum = W->bsum;
-        A.T = ctx->regtab;
+        SiteArgs<sid_off_t> A = S;
+        A.xm = sel_word(ctx->opts.select), A.T = ctx->regtab;
+        A.len1 = LL.len1, A.len2 = LL.len2;   // (as the parse)
         if (quad) launch_region_mark<REG_TILE, false>(A, st);
         else launch_region_mark<REG_TILE, true>(A, st);
     }
     if (ctx->cx_on) {   // the context: the slots outside the dilated selection likewise
-        CxArgs<sid_off_t> C{};
-        RegArgs<sid_off_t>& A = C.A;
-        A.text = base, A.len = c1, A.hdr = W->hdr, A.s1 = slots, A.tcnt = W->tcnt, A.cap = cap, A.cdiv = slot_div(cap);
-        A.twv = W->twv, A.nwv = tile_nwv(cap), A.cls = W->cls, A.code = W->code, A.hom = W->hom, A.het = W->het;
-        A.ct = ct, A.bsum = W->bsum;
-        if (quad) launch_context_mark<REG_TILE, false>(C, W, ctx, st);
-        else launch_context_mark<REG_TILE, true>(C, W, ctx, st);
+        if (quad) launch_context_mark<REG_TILE, false>(S, W, st);
+        else launch_context_mark<REG_TILE, true>(S, W, st);
     }
     WCHECK(hipGetLastError());
     W->cls_ready = true;
@@ -5971,26 +5876,22 @@ int sid_chunk_lynch_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     if (n > W->site_cap) return SID_EINVAL;
     WCHECK(hipMemsetAsync(W->lb, 0, 8 * 8, st));   // [1] bytes, [2] range flag
     const uint64_t nb = (n + FTB - 1) / FTB;
+    SiteArgs<sid_off_t> S = dense_view(W, base, c1, n);
+    S.V = V;
     if (W->window) {   // the windowed summary: on the counts before a mark zeroes them
-        WinArgs<sid_off_t> C{};
-        C.A.text = base, C.A.len = c1, C.A.starts = W->starts, C.A.hdr = W->hdr, C.A.s1 = n, C.A.counts = W->counts;
-        C.V = V;
-        const int rc = window_stage<REG_LYNCH, false>(C, W, nullptr, c1, true, st);
+        const int rc = window_stage<REG_LYNCH, false>(S, W, c1, true, st);
         if (rc != SID_OK) return rc;
     }
     if (ctx->cx_on) {   // the context: counts 0 likewise (no class or no site: the empty descriptor)
-        CxArgs<sid_off_t> C{};
-        RegArgs<sid_off_t>& A = C.A;
-        A.text = base, A.len = c1, A.starts = W->starts, A.hdr = W->hdr, A.s1 = V.empty ? 0 : n, A.counts = W->counts;
-        C.V = V;
-        launch_context_mark<REG_LYNCH, false>(C, W, nullptr, st);
+        SiteArgs<sid_off_t> A = S;
+        if (V.empty) A.s1 = 0;
+        launch_context_mark<REG_LYNCH, false>(A, W, st);
     }
     if (nb && V.empty) {   // no class: every site dropped (and no length table)
         WCHECK(hipMemsetAsync(W->bsum, 0, nb * 4, st));
     } else if (nb) {
         if (ctx->has_regions) {   // the sites outside the region set: counts 0, which no class holds
-            RegArgs<sid_off_t> A{};
-            A.text = base, A.len = c1, A.starts = W->starts, A.hdr = W->hdr, A.s1 = n, A.counts = W->counts;
+            SiteArgs<sid_off_t> A = S;
             A.T = ctx->regtab;
             launch_region_mark<REG_LYNCH, false>(A, st);
         }

@@ -56,6 +56,8 @@ PERIOD, LEN_LO, LEN_HI, SET_SEED = 12_000, 200, 400, 1234
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--parent", default=None, help="a built checkout of the parent commit (none: this tree only)")
+    p.add_argument("--parent-all", action="store_true",
+                   help="the parent runs every selection this tree runs (a parent that has them all)")
     p.add_argument("--sites", type=int, default=50_000_000)
     p.add_argument("--steps", type=int, default=8)
     p.add_argument("--warmup", type=int, default=2)
@@ -263,7 +265,7 @@ def main():
                 check = name == "this" and rnd == 0 and not a.no_check
                 cmd = [sys.executable, os.path.abspath(__file__), "--worker", tree, "--config", config, "--sites",
                        str(a.sites), "--steps", str(a.steps), "--warmup", str(a.warmup), "--sets",
-                       "none,sparse,whole" if name == "this" else "none"] + (["--check"] if check else [])
+                       "none,sparse,whole" if name == "this" or a.parent_all else "none"] + (["--check"] if check else [])
                 env = dict(os.environ)
                 env.pop("SID_LIB_PATH", None)   # each tree loads its own build/libsid.so
                 p = subprocess.run(cmd, capture_output=True, text=True, timeout=a.step_timeout, env=env)
