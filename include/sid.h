@@ -79,6 +79,24 @@
  *     fails has no rows.  Any other W: SID_EINVAL from sid_create and
  *     sid_engine_create.  Host path: sid_windows_host, on the codes before any
  *     mark.
+ *   - Variants (sid_opts.variants = 1; --variants): the records whose genotype
+ *     is not the reference's.  For the site of a record, R is the single byte
+ *     of its line's third token (the reference base, pileup.cpp:26-30),
+ *     upper-cased as pileup.cpp:79 does (toupper, ASCII).  The record is a
+ *     variant when (1) R is one of A, C, G, T, (2) the site has at least one
+ *     counted base (a non-zero count in its profile_t) and (3) its gt field is
+ *     not RR.  (2) is not decoration: -m local prints "hom,TT,1,1,p_value" for
+ *     a site without a counted base -- depth 0, only '*', only '.' / ',' on an
+ *     N reference -- whatever its reference.  The same formatters then emit only
+ *     the variants, byte for byte and in U's order.  With a selection by label
+ *     and / or region a record is emitted when all of them hold; with
+ *     --context N, S is the set all of them keep; the window rows never change.
+ *     Header, stderr, exit status, the calls, the -R prior, the Lynch estimate
+ *     and Benjamini-Hochberg see every site and are unchanged; bytes_out stays
+ *     exact in every sink mode, and the result does not depend on chunk size,
+ *     device count, lanes, budgets, source kind or tile shape.  Any other
+ *     value: SID_EINVAL from sid_create and sid_engine_create.  Host
+ *     formatting: sid_variants_mark, before sid_context_mark.
  *   - Counts layout: profile_t (pileup.hpp:7) = 4 x uint16 {A,C,G,T} per site,
  *     array of structures, 8 bytes per site.
  */
@@ -141,6 +159,13 @@ typedef struct {
                                     emitted, by label; sid_create and
                                     sid_engine_create return SID_EINVAL for any
                                     other value                                    */
+    int variants;                /* --variants (default 0): 1 = only the records
+                                    whose genotype is not homozygous reference are
+                                    emitted (Conventions); any other value:
+                                    SID_EINVAL.  It takes the four bytes that were
+                                    padding in front of the pointer below: the
+                                    structure's size and every other field's
+                                    offset are as before, `window` stays last      */
     const struct sid_regions* regions; /* --regions (default NULL = every site): the
                                     records emitted, by (chrom, pos); see
                                     sid_regions_* below                            */
@@ -200,6 +225,11 @@ int sid_regions_contains(const sid_regions* r, const char* chrom, size_t chrom_l
 void sid_regions_free(sid_regions* r);
 int sid_regions_mark(const sid_regions* r, const struct sid_sites* s, size_t begin, size_t end,
                      uint8_t* code /* host */);
+/* The variants on the host path (Conventions): sets SID_CODE_DROPPED on the
+ * host codes code[begin, end) of the sites that are no variant -- the analogue
+ * of sid_regions_mark, before sid_context_mark.  SID_EINVAL for a range outside
+ * the sites or a NULL pointer. */
+int sid_variants_mark(const struct sid_sites* s, size_t begin, size_t end, uint8_t* code /* host */);
 
 /* -------------------------------------------------------------- windows --
  * The rows of the windowed summary (Conventions).  chrom is not NUL-terminated.
@@ -338,6 +368,9 @@ void sid_sites_free(sid_sites* s);
 size_t sid_sites_count(const sid_sites* s);
 const uint16_t* sid_sites_counts(const sid_sites* s);   /* host, n x 4          */
 const int32_t* sid_sites_positions(const sid_sites* s); /* host, n              */
+/* The reference base of every site: the byte of its line's third token, as it
+ * stands in the text (not upper-cased). */
+const uint8_t* sid_sites_refs(const sid_sites* s);      /* host, n              */
 /* Chromosome runs: segment k covers sites [start_k, start_{k+1}). */
 size_t sid_sites_chrom_segments(const sid_sites* s);
 const char* sid_sites_chrom_name(const sid_sites* s, size_t k, uint64_t* start);
@@ -502,9 +535,9 @@ typedef struct {
     uint64_t chunks;
     uint64_t bytes_in;           /* input text bytes                                 */
     uint64_t bytes_out;          /* CSV bytes written (header excluded; with a
-                                    selection by label or region: the selected
-                                    records', with a context theirs too; exact in
-                                    every sink mode)                                */
+                                    selection by label, region or variant: the
+                                    selected records', with a context theirs too;
+                                    exact in every sink mode)                                */
     uint64_t chunks_held;        /* formatted in the first pass                      */
     uint64_t chunks_retained;    /* text kept in HBM for the second pass             */
     uint64_t chunks_reloaded;    /* text read from the source a second time          */

@@ -49,7 +49,7 @@ class Opts(C.Structure):
     """sid_opts = GlobalOptions (sid.cpp:11-17)."""
     _fields_ = [("method", C.c_int), ("estimate_prior", C.c_int), ("snp_prior", C.c_double),
                 ("significance_level", C.c_double), ("site_error_threshold", C.c_double), ("select", C.c_int),
-                ("regions", C.c_void_p), ("context", C.c_int)]
+                ("variants", C.c_int), ("regions", C.c_void_p), ("context", C.c_int)]
     # sid_opts.window, the int behind `context`: the structure's last four bytes (its size is a multiple
     # of the 8-byte alignment of its doubles and pointer, so they belong to it).  The field list above
     # ends at `context`, as its users have it; `window` reads and writes those bytes
@@ -134,6 +134,7 @@ SIGNATURES = [
     ("sid_regions_contains", _I, [_P, C.c_char_p, _SZ, C.c_int32]),
     ("sid_regions_free", None, [_P]),
     ("sid_regions_mark", _I, [_P, _P, _SZ, _SZ, _P]),
+    ("sid_variants_mark", _I, [_P, _SZ, _SZ, _P]),
     ("sid_device_count", _I, [C.POINTER(C.c_int)]),
     ("sid_create", _I, [_I, C.POINTER(Opts), C.POINTER(_P)]),
     ("sid_destroy", _I, [_P]),
@@ -160,6 +161,7 @@ SIGNATURES = [
     ("sid_sites_count", _SZ, [_P]),
     ("sid_sites_counts", _P, [_P]),
     ("sid_sites_positions", _P, [_P]),
+    ("sid_sites_refs", _P, [_P]),
     ("sid_sites_chrom_segments", _SZ, [_P]),
     ("sid_sites_chrom_name", C.c_char_p, [_P, _SZ, C.POINTER(C.c_uint64)]),
     ("sid_format_csv", _I, [_P, _SZ, _SZ, _P, _P, _P, C.c_char_p, _P, _SZ, C.POINTER(C.c_size_t)]),
@@ -304,7 +306,7 @@ class Regions:
 
 
 def make_opts(method="local", estimate_prior=False, snp_prior=-1.0, significance_level=0.05,
-              site_error_threshold=0.1, select="all", regions=None, context=0, window=0) -> Opts:
+              site_error_threshold=0.1, select="all", regions=None, context=0, window=0, variants=0) -> Opts:
     o = Opts()
     lib().sid_opts_default(C.byref(o))
     o.method = METHODS[method] if isinstance(method, str) else int(method)
@@ -324,6 +326,8 @@ def make_opts(method="local", estimate_prior=False, snp_prior=-1.0, significance
     o.context = int(context)
     # (0 = off, 1 .. 2^31-1: a negative value is SID_EINVAL there too)
     o.window = int(window)
+    # (0 or 1, True / False: another value is SID_EINVAL there too)
+    o.variants = int(variants)
     return o
 
 
@@ -401,6 +405,7 @@ class Sites:
     positions: np.ndarray       # (n,) int32
     chroms: list                # [(start_site, name)]
     handle: object = None       # sid_sites* kept for format_csv
+    refs: np.ndarray = None     # (n,) uint8: the reference base of every site, the byte of its third column
 
     def __len__(self):
         return len(self.positions)
@@ -431,7 +436,9 @@ def parse_text(text: bytes, threads: int = 0) -> Sites:
         start = C.c_uint64(0)
         name = L.sid_sites_chrom_name(h, k, C.byref(start))
         chroms.append((start.value, name))
-    return Sites(counts, pos, chroms, h)
+    refs = np.ctypeslib.as_array(C.cast(L.sid_sites_refs(h), C.POINTER(C.c_uint8)),
+                                 shape=(n,)).copy() if n else np.zeros(0, np.uint8)
+    return Sites(counts, pos, chroms, h, refs)
 
 
 def format_csv(sites: Sites, code: np.ndarray, hom: np.ndarray, het: np.ndarray,
@@ -484,6 +491,20 @@ def regions_mark(sites: Sites, code: np.ndarray, regions) -> np.ndarray:
         raise SidError(1, "regions_mark: one code per site")
     check(lib().sid_regions_mark(regions._handle() if regions is not None else None, sites.handle, 0, out.size,
                                  _ptr(out)), "sid_regions_mark")
+    return out
+
+
+def variants_mark(sites: Sites, code: np.ndarray, begin: int = 0, end: int = None) -> np.ndarray:
+    """sid_variants_mark on a copy of the codes: the sites of [begin, end) whose
+    record is no variant -- a reference base that is none of A, C, G, T, no
+    counted base, or a genotype that is the reference's twice -- get
+    SID_CODE_DROPPED, so format_csv skips them.  After select_mark /
+    regions_mark or before them (they commute), before context_mark."""
+    out = np.array(code, np.uint8, copy=True)
+    if out.size != len(sites):
+        raise SidError(1, "variants_mark: one code per site")
+    check(lib().sid_variants_mark(sites.handle, int(begin), out.size if end is None else int(end), _ptr(out)),
+          "sid_variants_mark")
     return out
 
 

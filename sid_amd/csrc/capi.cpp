@@ -65,6 +65,7 @@ extern "C" void sid_opts_default(sid_opts* o)
     o->regions = nullptr;
     o->context = 0;
     o->window = 0;
+    o->variants = 0;
 }
 
 // GSL 2.7.1 specfunc/gamma.c lngamma_lanczos (x >= 0.5, away from 1 and 2,
@@ -134,6 +135,7 @@ extern "C" int sid_create(int device, const sid_opts* opts, sid_ctx** out)
     if (opts && (opts->select < SID_SELECT_ALL || opts->select > SID_SELECT_HOM)) return SID_EINVAL;
     if (opts && (opts->context < 0 || opts->context > SID_CONTEXT_MAX)) return SID_EINVAL;
     if (opts && opts->window < 0) return SID_EINVAL;
+    if (opts && opts->variants != 0 && opts->variants != 1) return SID_EINVAL;
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) return sid_set_hip_error(e);
     sid_ctx* c = new sid_ctx();
@@ -141,7 +143,7 @@ extern "C" int sid_create(int device, const sid_opts* opts, sid_ctx** out)
     if (opts) c->opts = *opts; else sid_opts_default(&c->opts);
     // a context around a selection: the unselected tables, tails and parse, and the marking stage selects
     // (without a selection the context changes nothing)
-    const bool cx = c->opts.context > 0 && (c->opts.select != SID_SELECT_ALL || c->opts.regions);
+    const bool cx = c->opts.context > 0 && (c->opts.select != SID_SELECT_ALL || c->opts.regions || c->opts.variants);
     // a selection by label under --windows goes the same way with N = 0: the window stage needs every
     // site's label, which the selecting parse and the filtered tables do not keep
     if (cx || (c->opts.window > 0 && c->opts.select != SID_SELECT_ALL)) {
@@ -150,6 +152,9 @@ extern "C" int sid_create(int device, const sid_opts* opts, sid_ctx** out)
         c->cx_select = c->opts.select;
         c->opts.select = SID_SELECT_ALL;
     }
+    // the variants: a marking stage of their own, or one more test of the context's
+    c->has_variants = c->opts.variants && !c->cx_on;
+    c->cx_variants = c->opts.variants && c->cx_on;
     sid_build_local_k(c->opts, &c->K);
     // SID_TABLE_TAIL=0: the second-level class table off, its sites through
     // the fix-up (tests/test_local_gpu.py covers both)

@@ -12,7 +12,18 @@
 // reference's flags): --devices N, --threads N, --stats, --host-parse,
 // --chunk-bytes N, --hold-bytes N, --retain-bytes N, --host-hold N,
 // --only het|hom|all, --regions FILE, --bgzf, --context N, --windows W,
-// --windows-out FILE.
+// --windows-out FILE, --variants.
+//
+// --variants (no argument) writes the header and only the records whose
+// genotype is not homozygous reference (sid_opts.variants, sid.h Conventions):
+// the reference base is the line's third column, upper-cased; a record stays
+// when that is one of A, C, G, T, the site has a counted base and its gt field
+// is not that base twice -- the het sites `--only het` finds and the
+// homozygous non-reference sites it misses, chosen before the records are
+// formatted.  Everything else, stderr included, is as without it; with --only
+// and / or --regions all must hold, --context N counts from what they all
+// keep, and the --windows rows do not change.  With --host-parse:
+// sid_variants_mark.  Not listed by -h, whose text stays the reference's.
 //
 // --windows W --windows-out FILE (W in 1 .. 2147483647): beside the records,
 // the windowed summary of the run (sid_opts.window, sid.h Conventions) as CSV
@@ -290,6 +301,7 @@ int main(int argc, char** argv)
                                          {"context", required_argument, nullptr, 12},
                                          {"windows", required_argument, nullptr, 13},
                                          {"windows-out", required_argument, nullptr, 14},
+                                         {"variants", no_argument, nullptr, 15},
                                          {nullptr, 0, nullptr, 0}};
     int flag;
     while ((flag = getopt_long(argc, argv, "E:Rhm:p:r:", LONG, nullptr)) != -1) {
@@ -387,6 +399,7 @@ int main(int argc, char** argv)
             break;
         }
         case 14: windows_out = optarg; break;
+        case 15: opt.o.variants = 1; break;
         default: std::exit(EXIT_FAILURE);
         }
     }
@@ -792,9 +805,11 @@ int main(int argc, char** argv)
         if (windows_out) CHECK(sid_windows_host(sites, 0, n, h_code, opt.o.window, &wrows, &nwrows), "windows");
         window_rows = nwrows;
         std::vector<uint8_t> code_all;   // --context: the codes before the selections marked them
-        if (opt.o.context > 0 && (opt.o.select != SID_SELECT_ALL || regions)) code_all.assign(h_code, h_code + n);
+        if (opt.o.context > 0 && (opt.o.select != SID_SELECT_ALL || regions || opt.o.variants))
+            code_all.assign(h_code, h_code + n);
         CHECK(sid_select_mark(h_code, n, opt.o.select), "select");   // --only: the other labels' sites get no record
         CHECK(sid_regions_mark(regions, sites, 0, n, h_code), "regions");   // --regions: nor the sites outside
+        if (opt.o.variants) CHECK(sid_variants_mark(sites, 0, n, h_code), "variants");   // --variants: nor the others
         if (!code_all.empty()) CHECK(sid_context_mark(code_all.data(), h_code, n, opt.o.context), "context");
         const size_t BLOCK = 1u << 18;
         const size_t nblocks = (n + BLOCK - 1) / BLOCK;

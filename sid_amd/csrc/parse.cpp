@@ -132,6 +132,7 @@ struct Err {
 struct Part {
     std::vector<uint16_t> counts;
     std::vector<int32_t> pos;
+    std::vector<uint8_t> ref;          // the reference base: token 2's byte
     std::vector<uint64_t> seg_start;   // local site index
     std::vector<std::string> seg_name;
     Err err;
@@ -142,6 +143,7 @@ void parse_range(const char* base, const char* b, const char* e, Part& P)
 {
     P.counts.reserve((size_t)(e - b) / 40 * 4 + 16);
     P.pos.reserve((size_t)(e - b) / 40 + 4);
+    P.ref.reserve((size_t)(e - b) / 40 + 4);
     const char* p = b;
     size_t nsites = 0;
     const char* last_name = nullptr;
@@ -185,6 +187,7 @@ void parse_range(const char* base, const char* b, const char* e, Part& P)
             last_len = nlen;
         }
         P.pos.push_back(atoi_like(tb[1], te[1]));
+        P.ref.push_back((uint8_t)*tb[2]);
         uint16_t c[4];
         read_bases(tb[4], te[4], *tb[2], c);
         P.counts.insert(P.counts.end(), c, c + 4);
@@ -246,12 +249,14 @@ extern "C" int sid_parse_text(const char* text, size_t len, int nthreads, sid_si
     }
     S->counts.resize(total * 4);
     S->pos.resize(total);
+    S->ref.resize(total);
     std::vector<std::thread> cp;
     for (int t = 0; t < T; ++t)
         cp.emplace_back([&, t] {
             if (parts[t].pos.empty()) return;   // (memcpy from a null pointer is undefined, even of 0 bytes)
             std::memcpy(S->counts.data() + 4 * off[t], parts[t].counts.data(), parts[t].counts.size() * 2);
             std::memcpy(S->pos.data() + off[t], parts[t].pos.data(), parts[t].pos.size() * 4);
+            std::memcpy(S->ref.data() + off[t], parts[t].ref.data(), parts[t].ref.size());
         });
     for (auto& x : cp) x.join();
     for (int t = 0; t < T; ++t) {
@@ -269,6 +274,26 @@ extern "C" void sid_sites_free(sid_sites* s) { delete s; }
 extern "C" size_t sid_sites_count(const sid_sites* s) { return s ? s->pos.size() : 0; }
 extern "C" const uint16_t* sid_sites_counts(const sid_sites* s) { return s ? s->counts.data() : nullptr; }
 extern "C" const int32_t* sid_sites_positions(const sid_sites* s) { return s ? s->pos.data() : nullptr; }
+extern "C" const uint8_t* sid_sites_refs(const sid_sites* s) { return s ? s->ref.data() : nullptr; }
+
+// The variants on the host path (sid.h Conventions): a site stays when its
+// reference base is one of A, C, G, T (either case), one of its counts is not
+// 0 and its genotype is not the reference's twice.
+extern "C" int sid_variants_mark(const sid_sites* s, size_t begin, size_t end, uint8_t* code)
+{
+    if (!s || begin > end || end > s->pos.size() || s->ref.size() != s->pos.size()) return SID_EINVAL;
+    if (!code && end != begin) return SID_EINVAL;
+    for (size_t i = begin; i < end; ++i) {
+        const uint8_t k = BASE_CLASS.t[s->ref[i]];   // (either case: toupper)
+        const uint16_t* c = s->counts.data() + 4 * i;
+        const bool counted = (c[0] | c[1] | c[2] | c[3]) != 0;
+        const uint8_t r = (uint8_t)(k - 1);          // 0 .. 3 = A, C, G, T when k is a base
+        const bool rr = (code[i] & 3u) == r && ((code[i] >> 2) & 3u) == r;
+        if (k < C_A || k > C_T || !counted || rr) code[i] |= SID_CODE_DROPPED;
+    }
+    return SID_OK;
+}
+
 extern "C" size_t sid_sites_chrom_segments(const sid_sites* s) { return s ? s->seg_name.size() : 0; }
 extern "C" const char* sid_sites_chrom_name(const sid_sites* s, size_t k, uint64_t* start)
 {

@@ -2039,7 +2039,8 @@ void compute(sid_engine* e, Dev& d, int pass)
                 d.tile_over(maxl, quad);
             } else {
                 const uint64_t m2 = (m + 1) & ~(uint64_t)1, m4 = (m + 3) & ~(uint64_t)3;
-                const uint64_t pre_bytes = 4 * m4 + 24 * m2;
+                // (sid_opts.variants: the sites' reference bytes behind the header pairs, 1 B a site)
+                const uint64_t pre_bytes = 4 * m4 + 24 * m2 + (W.refb ? m : 0);
                 uint64_t pc = 0;
                 char* pre = m && d.retain_used.load() + pre_bytes <= d.retain_budget
                                 ? d.pool.get(pre_bytes, &pc, d.s_comp) : nullptr;
@@ -2050,7 +2051,8 @@ void compute(sid_engine* e, Dev& d, int pass)
                         r.pre_cap = pc;
                         d.retain_used += pc;
                         counts = (uint64_t*)(pre + 4 * m4);
-                        rc = sid_chunk_tile_compact(&W, (sid_off_t*)pre, counts, counts + m2, d.s_comp);
+                        rc = sid_chunk_tile_compact(&W, (sid_off_t*)pre, counts, counts + m2,
+                                                    W.refb ? (uint8_t*)(counts + 3 * m2) : nullptr, d.s_comp);
                         if (rc != SID_OK) return (void)fail(e, rc);
                     }
                     W.slot_cap = 0;
@@ -2079,21 +2081,24 @@ void compute(sid_engine* e, Dev& d, int pass)
             sid_chunk_ws& W;
             sid_off_t* starts;
             uint64_t *counts, *hdr;
+            uint8_t* refb;
             bool on = false;
             ~View()
             {
-                if (on) W.starts = starts, W.counts = counts, W.hdr = hdr;
+                if (on) W.starts = starts, W.counts = counts, W.hdr = hdr, W.refb = refb;
             }
-        } view{W, W.starts, W.counts, W.hdr};
+        } view{W, W.starts, W.counts, W.hdr, W.refb};
         // the kept parse's layout: starts (4 B), counts (8 B), header pairs
         // (16 B), each at a 16-B aligned offset (the lookup reads counts as
-        // 16-B site pairs)
+        // 16-B site pairs), then with sid_opts.variants the reference bytes
+        // (1 B; the workspace has an array of them exactly then)
         auto use_pre = [&](char* pre, uint64_t m) {
-            view.starts = W.starts, view.counts = W.counts, view.hdr = W.hdr, view.on = true;
+            view.starts = W.starts, view.counts = W.counts, view.hdr = W.hdr, view.refb = W.refb, view.on = true;
             const uint64_t m2 = (m + 1) & ~(uint64_t)1, m4 = (m + 3) & ~(uint64_t)3;
             W.starts = (sid_off_t*)pre;
             W.counts = (uint64_t*)(pre + 4 * m4);
             W.hdr = W.counts + m2;
+            if (W.refb) W.refb = (uint8_t*)(W.hdr + 2 * m2);
         };
         if (pass == 2 && r.pre) {
             n = r.parsed;
@@ -2121,7 +2126,7 @@ void compute(sid_engine* e, Dev& d, int pass)
             // pass 2 (which then skips index and parse) while the retain
             // budget allows: 28 B a site, cheaper than indexing and parsing
             // the text again
-            const uint64_t pre_bytes = 4 * ((n + 3) & ~(uint64_t)3) + 24 * ((n + 1) & ~(uint64_t)1);
+            const uint64_t pre_bytes = 4 * ((n + 3) & ~(uint64_t)3) + 24 * ((n + 1) & ~(uint64_t)1) + (W.refb ? n : 0);
             if (pass == 1 && e->lynch && n && !qmode && d.retain_used.load() + pre_bytes <= d.retain_budget) {
                 uint64_t pc = 0;
                 char* pre = d.pool.get(pre_bytes, &pc, d.s_comp);

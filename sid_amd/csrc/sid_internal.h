@@ -131,6 +131,11 @@ struct sid_ctx {
     int cx_n = 0;
     int cx_select = SID_SELECT_ALL;
     bool cx_regions = false;   // regtab holds the set
+    // the variants (sid_opts.variants): has_variants, the marking stage of their own (sid_variant_mark_kernel)
+    // behind the region stage; cx_variants, under a context's route, the marking stage's third test.  Either
+    // way the parse keeps every site's reference byte (sid_chunk_ws::refb)
+    bool has_variants = false;
+    bool cx_variants = false;
     // the route's switch: a context in effect, or (cx_n = 0) a selection by label under sid_opts.window, whose
     // stage reads every site's label in front of the marking stage
     bool cx_on = false;
@@ -218,6 +223,14 @@ struct sid_chunk_ws {
     bool cx_on = false;
     int cx_select = 0;
     const sid_regtab* cx_regions = nullptr;
+    // likewise the owner's variants (sid_ctx::has_variants, cx_variants), and with either the sites' reference
+    // bytes, in the layout the chunk is in (per slot for the tile layout, per site in file order otherwise):
+    // bits 0-2 the reference base's class (0 .. 3 = A, C, G, T either case, 4 = anything else), bit 3 = the
+    // site has no counted base.  The tile parse and its general routine store them (REF instantiations);
+    // behind the two-pass parse, which has line offsets, sid_ref_fill_kernel reads them off the resident text
+    bool variants = false;
+    bool cx_variants = false;
+    uint8_t* refb = nullptr;
     unsigned long long* cx_bits = nullptr;
     uint4* cx_sum = nullptr;
     uint4* cx_car = nullptr;
@@ -300,7 +313,9 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
 // arrays (line offsets, counts, header pairs: the two-pass parse's layout).
 int sid_chunk_tile_counts(sid_chunk_ws* W, const char* base, uint64_t c0, uint64_t c1, uint32_t cap, bool quad,
                           hipStream_t st);
-int sid_chunk_tile_compact(sid_chunk_ws* W, sid_off_t* starts, uint64_t* counts, uint64_t* hdr, hipStream_t st);
+// (refb: the reference bytes likewise, when the workspace keeps them; else null)
+int sid_chunk_tile_compact(sid_chunk_ws* W, sid_off_t* starts, uint64_t* counts, uint64_t* hdr, uint8_t* refb,
+                           hipStream_t st);
 // likelihood_ratio / bayes fused with the class lookup (sid_lynch_fmt_view)
 int sid_chunk_lynch_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n, hipStream_t st);
 int sid_chunk_lynch_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n, char* out,

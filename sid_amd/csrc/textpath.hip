@@ -1900,10 +1900,37 @@ struct LaneSlot {
     uint32_t pl = 0;           // the position's digits
     bool elig = false;         // the words are the wave's to store
 };
-template <bool LOCAL, bool SEL, class Ld>
+// A site's reference byte (sid_chunk_ws::refb) from the class '.' / ',' stand
+// for (kd: K_A .. K_T, else anything) and its counts
+__device__ __forceinline__ uint8_t ref_byte(uint32_t kd, uint64_t c)
+{
+    return (uint8_t)((kd >= K_A && kd <= K_T ? kd - K_A : 4u) | (c == 0 ? 8u : 0u));
+}
+
+// The same off the resident text, for a line the parse has accepted (its third
+// token is one byte): tokens on ' ' / '\t' runs as parse_line_serial's
+__device__ __noinline__ uint8_t ref_byte_text(const char* __restrict__ text, uint64_t len, uint64_t s0, uint64_t c)
+{
+    Reader R{text, len};
+    uint64_t q = s0;
+    for (int t = 0; t < 2; ++t) {
+        while (q < len && is_sep(R.at(q))) ++q;
+        while (q < len) {
+            const uint32_t b = R.at(q);
+            if (is_sep(b) || b == '\n' || b == 0) break;
+            ++q;
+        }
+    }
+    while (q < len && is_sep(R.at(q))) ++q;
+    return ref_byte(q < len ? base_class(R.at(q)) : 0u, c);
+}
+
+// REF (sid_opts.variants): the line's reference byte into refb[g]
+template <bool LOCAL, bool SEL, bool REF, class Ld>
 __device__ __forceinline__ int tile_line(const char* __restrict__ text, const char* tl, Ld ld, uint64_t g0, uint32_t r0,
                                          uint64_t g, uint32_t len_t, uint64_t c1, const uint8_t* cls,
-                                         const uint32_t* rbl, const TileOut& O, const LocalLen& LL, LaneSlot& ws)
+                                         const uint32_t* rbl, const TileOut& O, const LocalLen& LL, LaneSlot& ws,
+                                         uint8_t* refb)
 {
     int l = 0;
     const uint64_t s0 = g0 + r0;
@@ -1920,6 +1947,7 @@ __device__ __forceinline__ int tile_line(const char* __restrict__ text, const ch
                                           (uint32_t)(low48 >> fw) & 0xFFFFu);
     }
     if (ok) {
+        if (REF) refb[g] = ref_byte(kd, c);
         const bool hv = (h[0] >> 63) != 0;
         const uint32_t clen = (uint32_t)(h[0] >> 32) & 0xFFFu;
         if (!hv || clen > 8) h[1] = (uint32_t)s0;   // the writer reads the chrom, or tokenises, from the line
@@ -2045,10 +2073,12 @@ __device__ __forceinline__ uint32_t quad_head(const char* tl, uint64_t g0, uint3
 // counted by the quad; the lead lane lists the line for the general routine
 // when they need it, else stores its counts (the Lynch paths'), or, for
 // -m local, keeps them in LDS for quad_tail (bit 31 of the line's word: counted)
-template <bool LOCAL, class Ld>
+// REF: the line's reference byte (kd from the header's word, the counts here;
+// -m local: by quad_tail, with the counts it reads back)
+template <bool LOCAL, bool REF, class Ld>
 __device__ __forceinline__ void quad_bases(const char* tl, Ld ld, uint64_t g0, uint32_t r0, uint32_t* meta,
                                            uint64_t* cnt_l, uint64_t g, uint32_t len_t, bool lead,
-                                           const uint32_t* rbl, const TileOut& O)
+                                           const uint32_t* rbl, const TileOut& O, uint8_t* refb)
 {
     const uint32_t mt = *meta;
     if (!(mt & 1u)) return;   // (the whole quad: the general routine's line)
@@ -2062,6 +2092,7 @@ __device__ __forceinline__ void quad_bases(const char* tl, Ld ld, uint64_t g0, u
         O.fbo[k] = (uint32_t)(g0 + r0);
     } else if (!LOCAL) {
         ST_MID(O.counts + g, c);
+        if (REF) refb[g] = ref_byte(kd, c);
     } else {
         *cnt_l = c;
         *meta = mt | (1u << 31);
@@ -2071,11 +2102,12 @@ __device__ __forceinline__ void quad_bases(const char* tl, Ld ld, uint64_t g0, u
 // -m local's call of a counted quad-shape line, a lane per line as the
 // header: the class word, the record's length (returned; 0 for a fix-up site
 // or a line not counted here)
-template <bool SEL>
+template <bool SEL, bool REF>
 __device__ __forceinline__ int quad_tail(const char* __restrict__ text, uint64_t s0, uint32_t mt, uint64_t c, uint64_t g,
-                                         uint64_t c1, const TileOut& O, const LocalLen& LL)
+                                         uint64_t c1, const TileOut& O, const LocalLen& LL, uint8_t* refb)
 {
     if (!(mt >> 31)) return 0;
+    if (REF) refb[g] = ref_byte((mt >> 7) & 7u, c);
     int l;
     if ((mt >> 10) & 1u) {
         const int L = local_site_tail<true, SEL>(c, g, LL.len1, LL);
@@ -2108,9 +2140,12 @@ __device__ uint32_t put_stamp[TP_STAMP_N][4];
 // SEL (LOCAL only): a selection by label -- LL's tail-length tables are the
 // filtered twins, a class of another label stores SID_CLS_SKIP and adds no
 // bytes (local_site_word); the instantiations without it are unchanged.
-template <bool QUAD, bool LOCAL, bool SEL = false>
+// REF (sid_opts.variants): every parsed line's reference byte into refb, per
+// slot (the last argument, which the instantiations without it never load).
+template <bool QUAD, bool LOCAL, bool SEL = false, bool REF = false>
 __global__ __launch_bounds__(TB) void sid_tile_parse_kernel(const char* __restrict__ text, uint64_t tile_base,
-                                                            uint64_t c0, uint64_t c1, TileOut O, LocalLen LL)
+                                                            uint64_t c0, uint64_t c1, TileOut O, LocalLen LL,
+                                                            uint8_t* __restrict__ refb)
 {
     constexpr uint32_t ROWS = QUAD ? TP_ROWS_QUAD : TP_ROWS, TP_TILE = ROWS * TILE;
     constexpr uint32_t LPR = QUAD ? TB / 4 : TB;   // lines per round of the block
@@ -2330,14 +2365,15 @@ __global__ __launch_bounds__(TB) void sid_tile_parse_kernel(const char* __restri
             for (uint32_t j0 = 0; j0 < cnt; j0 += LPR) {   // block-uniform trip count
                 const uint32_t j = j0 + (tid >> 2);
                 if (j < cnt)
-                    quad_bases<LOCAL>(tl, ld, g0, ls[j], qmeta + j, qcnt + (LOCAL ? j : 0), g_tile + j, len_t,
-                                      (tid & 3u) == 0, rbl, O);
+                    quad_bases<LOCAL, REF>(tl, ld, g0, ls[j], qmeta + j, qcnt + (LOCAL ? j : 0), g_tile + j, len_t,
+                                           (tid & 3u) == 0, rbl, O, refb);
             }
             if constexpr (LOCAL) {
                 __syncthreads();
                 __builtin_amdgcn_s_setprio(2);
                 int l = 0;
-                if (tid < cnt) l = quad_tail<SEL>(text, g0 + ls[tid], qmeta[tid], qcnt[tid], g_tile + tid, c1, O, LL);
+                if (tid < cnt)
+                    l = quad_tail<SEL, REF>(text, g0 + ls[tid], qmeta[tid], qcnt[tid], g_tile + tid, c1, O, LL, refb);
                 bsum_add(tid & ~63u, tid, l);
             }
         } else {
@@ -2346,7 +2382,8 @@ __global__ __launch_bounds__(TB) void sid_tile_parse_kernel(const char* __restri
                 int l = 0;
                 LaneSlot ws;
                 if (j < cnt)
-                    l = tile_line<LOCAL, SEL>(text, tl, ld, g0, ls[j], g_tile + j, len_t, c1, cls, rbl, O, LL, ws);
+                    l = tile_line<LOCAL, SEL, REF>(text, tl, ld, g0, ls[j], g_tile + j, len_t, c1, cls, rbl, O, LL, ws,
+                                                   refb);
                 if constexpr (LOCAL) {
                     tile_wave_store(ws, g_tile + j, O.twv + t * O.nwv + ((j0 + (tid & ~63u)) >> 6), O, LL);
                     bsum_add(j0 + (tid & ~63u), j, l);
@@ -2407,14 +2444,16 @@ __device__ __forceinline__ void fix_site(uint64_t i, const Head& hd, uint64_t c,
 // record length, a fix-up where no class table covers it, and the fix-ups
 // the tile parse listed (LL.miss) -- the work of two more launches a chunk
 // (a record-length kernel over the leftovers, then the fix-up kernel)
-template <bool LOCAL, bool SEL = false>
+// REF (sid_opts.variants): the leftover lines' reference bytes into refb
+template <bool LOCAL, bool SEL = false, bool REF = false>
 __global__ __launch_bounds__(TB) void sid_tile_serial_kernel(const char* __restrict__ text, uint64_t len,
                                                              const uint32_t* __restrict__ fb,
                                                              const uint32_t* __restrict__ fbo,
                                                              unsigned long long* lb, const uint32_t* __restrict__ tcnt,
                                                              uint64_t ntiles, uint32_t cap,
                                                              uint64_t* __restrict__ counts, uint64_t* __restrict__ hdr,
-                                                             unsigned long long* __restrict__ err, LocalFix F)
+                                                             unsigned long long* __restrict__ err, LocalFix F,
+                                                             uint8_t* __restrict__ refb)
 {
     __shared__ uint8_t cls[256];
     __shared__ uint32_t red[2][TB / 64];
@@ -2465,6 +2504,7 @@ __global__ __launch_bounds__(TB) void sid_tile_serial_kernel(const char* __restr
         counts[g] = c;
         hdr[2 * g] = 0;
         hdr[2 * g + 1] = s0;
+        if constexpr (REF) refb[g] = ref_byte_text(text, len, s0, c);
         if constexpr (LOCAL) {
             Reader R{text, len};
             const Head hd = slot_head(R, make_ulonglong2(0, s0));
@@ -2508,6 +2548,8 @@ constexpr uint64_t SID_SLOTS_MAX = 1ull << 28;
 // j goes to toff[tile] + j (toff: the tiles' exclusive prefix of their
 // counts); the line offset where the header pair keeps it (a chrom over 8
 // bytes, no valid pair), else 0 (unread)
+// REF (sid_opts.variants): the slots' reference bytes likewise
+template <bool REF>
 __global__ __launch_bounds__(TB) void sid_tile_compact_kernel(const uint32_t* __restrict__ tcnt,
                                                               const uint64_t* __restrict__ toff, uint64_t slots,
                                                               uint32_t cap, SlotDiv cdiv,
@@ -2515,7 +2557,9 @@ __global__ __launch_bounds__(TB) void sid_tile_compact_kernel(const uint32_t* __
                                                               const uint64_t* __restrict__ hdr,
                                                               sid_off_t* __restrict__ d_starts,
                                                               uint64_t* __restrict__ d_counts,
-                                                              uint64_t* __restrict__ d_hdr)
+                                                              uint64_t* __restrict__ d_hdr,
+                                                              const uint8_t* __restrict__ refb,
+                                                              uint8_t* __restrict__ d_refb)
 {
     for (uint64_t g = (uint64_t)blockIdx.x * TB + threadIdx.x; g < slots; g += (uint64_t)gridDim.x * TB) {
         const uint32_t t = slot_tile((uint32_t)g, cdiv);
@@ -2527,6 +2571,7 @@ __global__ __launch_bounds__(TB) void sid_tile_compact_kernel(const uint32_t* __
         d_counts[i] = counts[g];
         *(ulonglong2*)(d_hdr + 2 * i) = hw;
         d_starts[i] = keep ? 0u : (sid_off_t)hw.y;
+        if (REF) d_refb[i] = refb[g];
     }
 }
 
@@ -3606,6 +3651,7 @@ struct SiteArgs {
     uint32_t* bsum;               // -m local: the groups' record bytes
     sid_lynch_fmt V;              // REG_LYNCH: the classes
     sid_regtab T;                 // the region set (the region stage; the context, when a set selects)
+    const uint8_t* refb;          // the reference bytes (sid_chunk_ws::refb; the variant stage, the context's test)
 };
 
 // MODE REG_TILE: OPT = the lane shape (compact words and wave entries);
@@ -3704,6 +3750,34 @@ __device__ __forceinline__ void sv_label(const SiteArgs<Off>& A, uint64_t i, uin
     *het = (c & SID_CODE_HET) != 0;
 }
 
+// Whether a site's record is a variant (sid.h Conventions), for a site that
+// has one: its reference base one of A, C, G, T, a counted base (both in the
+// site's reference byte), and a genotype that is not the reference's twice.  A
+// het record names two different bases, so it is one whenever the byte allows
+// it; a hom record takes one compare of its base.  The genotype per mode:
+//   REG_TILE / REG_DENSE  the class word's major base (bits 28-29) and the
+//                         entry's het byte; a fix-up site: its code
+//   REG_LYNCH             the class's tail, "hom,XX," / "het,XY," from byte 8
+//   REG_CODE              the code's bits 0-3 and bit 7
+template <int MODE, class Off>
+__device__ __forceinline__ bool sv_variant(const SiteArgs<Off>& A, uint64_t i, uint32_t w)
+{
+    const uint32_t r = A.refb[i];
+    if (r > 3u) return false;   // (bit 3: no counted base; class 4: no base)
+    if (MODE == REG_TILE || MODE == REG_DENSE) {
+        const uint32_t e = sv_entry(w, A.str1, A.str2);
+        if ((e & 0xFFu) != 0xFFu) return ((e >> 8) & 1u) || (w >> 28 & 3u) != r;
+    } else if (MODE == REG_LYNCH) {
+        const uint32_t idx = A.V.empty ? 0xFFFFFFFFu : lynch_class(A.counts[i], A.V);
+        if (idx == 0xFFFFFFFFu) return false;   // (no record)
+        const char* t = A.V.lstr + (size_t)idx * SID_LSTR_BYTES;
+        const uint32_t ch = (0x54474341u >> (8u * r)) & 0xFFu;   // "ACGT"[r]
+        return (uint32_t)(uint8_t)t[12] != ch || (uint32_t)(uint8_t)t[13] != ch;
+    }
+    const uint32_t c = A.code[i];
+    return (c & 3u) != r || ((c >> 2) & 3u) != r;
+}
+
 // The marking stages' back end: a dropped site's marker, and for -m local its
 // group's record bytes again (every thread of the block calls it).  keep: the
 // site keeps a record, rec_len() bytes long.
@@ -3770,6 +3844,81 @@ static void launch_region_mark(const SiteArgs<Off>& A, hipStream_t st)
 // stores (an exon-like set leaves most groups empty or with a few records).
 constexpr uint32_t REG_LDS_MIN = 2048;
 
+// ---------------------------------------------------------------- variants --
+// The variants (sid_opts.variants; sid_ctx::has_variants): the records whose
+// genotype is the reference's twice, whose reference is no base or whose site
+// has no counted base get the region stage's markers, behind that stage and
+// the window's, so the region writers and the unselected Lynch / code writers
+// follow unchanged.  The reference bytes (SiteArgs::refb) are the parse's: the
+// tile parse stores them per slot, and where a layout has line offsets
+// sid_ref_fill_kernel reads them off the resident text behind the parse.
+// -m local: a group without record bytes -- nothing parsed into it, or nothing
+// of it inside the region set, whose stage then leaves its words unmarked --
+// has nothing to keep and is passed over on its sum, as the writers pass it.
+// (REG_DENSE with OPT: this kernel writes the class words, for the writer)
+template <int MODE, bool OPT, class Off>
+__global__ __launch_bounds__(FTB) void sid_variant_mark_kernel(const SiteArgs<Off> A)
+{
+    if ((MODE == REG_TILE || MODE == REG_DENSE) && A.bsum[blockIdx.x] == 0) return;   // (block-uniform)
+    const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
+    uint32_t w;
+    bool site = sv_site<MODE, OPT, SV_FILTERED | SV_STORE>(A, i, &w);
+    if (MODE == REG_CODE && site) site = !code_out(A.code[i], A.xm);   // (no record anyway)
+    const bool var = site && sv_variant<MODE>(A, i, w);
+    sv_mark<MODE>(A, i, site && !var, var, [&]() -> int {
+        Reader R{A.text, A.len};
+        const Head h = sv_head<MODE, OPT>(A, i, w, R);
+        if (w == SID_CLS_MISS) {   // the fix-up's site
+            const uint8_t c = A.code[i];
+            return code_out(c, A.xm) ? 0 : miss_len<4>(h, c, A.hom[i], A.het[i], A.ct);
+        }
+        const uint32_t k = w & 0xFFFFFu;
+        const uint32_t L = k < SID_TAB_N ? A.len1[k] : A.len2[k - SID_TAB_N];
+        return L && L != 0xFFu ? local_rec_len(h, L) : 0;
+    });
+}
+
+template <int MODE, bool OPT, class Off>
+static void launch_variant_mark(const SiteArgs<Off>& A, hipStream_t st)
+{
+    const uint64_t nb = (A.s1 - A.s0 + FTB - 1) / FTB;
+    if (nb) sid_variant_mark_kernel<MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(A);
+}
+
+// The reference bytes of sites [s0, s1) of a layout with line offsets, off the
+// resident text (the two-pass parse's sites, a resident shard's): the class of
+// the line's third token, and "no counted base" from the site's counts -- or,
+// where the parse left class words instead (cls; sid_parse_len_kernel writes
+// the counts of the fix-up's sites alone), from the word: only the profile
+// without a count has the table's entry 0 .. 31 (nf = 0: sid_tab_slot).
+template <class Off>
+__global__ __launch_bounds__(TB) void sid_ref_fill_kernel(const char* __restrict__ text, uint64_t len,
+                                                          const Off* __restrict__ starts, uint64_t s0, uint64_t s1,
+                                                          const uint64_t* __restrict__ counts,
+                                                          const uint32_t* __restrict__ cls, uint8_t* __restrict__ refb)
+{
+    for (uint64_t i = s0 + (uint64_t)blockIdx.x * TB + threadIdx.x; i < s1; i += (uint64_t)gridDim.x * TB) {
+        uint64_t c = 1;
+        if (cls) {
+            const uint32_t w = cls[i];
+            if (w == SID_CLS_MISS) c = counts[i];
+            else if (w != SID_CLS_SKIP) c = (w & 0xFFFFFu) >= (uint32_t)(SID_TAB_NS * SID_TAB_NR);
+        } else {
+            c = counts[i];
+        }
+        refb[i] = ref_byte_text(text, len, (uint64_t)starts[i], c);
+    }
+}
+
+template <class Off>
+static void launch_ref_fill(const char* text, uint64_t len, const Off* starts, uint64_t s0, uint64_t s1,
+                            const uint64_t* counts, const uint32_t* cls, uint8_t* refb, hipStream_t st)
+{
+    if (s1 <= s0) return;
+    const unsigned grid = (unsigned)std::min<uint64_t>((s1 - s0 + TB - 1) / TB, 16384);
+    sid_ref_fill_kernel<Off><<<grid, TB, 0, st>>>(text, len, starts, s0, s1, counts, cls, refb);
+}
+
 // ---------------------------------------------------------------- context --
 // The context (sid_opts.context = N with a selection; sid_ctx::cx_n): every
 // selected record with the N records before and after it, in record rank --
@@ -3798,6 +3947,7 @@ struct CxArgs {
     SiteArgs<Off> A;              // the sites (A.T: the set, when reg)
     uint32_t sel;                 // SID_SELECT_*: the label selected (ALL: every label)
     uint32_t reg;                 // a region set selects too
+    uint32_t var;                 // ... and the variant test (A.refb)
     uint32_t N;
     uint32_t force;               // the chunk's edge records are forced (not for a whole text at once)
     unsigned long long* bits;     // per wave of slots: [0] records, [1] selected
@@ -3821,6 +3971,7 @@ __global__ __launch_bounds__(FTB) void sid_context_flag_kernel(const CxArgs<Off>
     bool rec = false, het = false;
     if (site) sv_label<MODE>(A, i, w, &rec, &het);
     bool sel = rec && (C.sel == SID_SELECT_ALL || het == (C.sel == SID_SELECT_HET));
+    if (C.var) sel = sel && sv_variant<MODE>(A, i, w);   // (uniform)
     if (C.reg) {   // (uniform)
         Head h{0, 0, 0, 0};
         if (sel) h = sv_head<MODE, OPT>(A, i, w, R);
@@ -4056,6 +4207,7 @@ static void launch_context_mark(const SiteArgs<Off>& A, const sid_chunk_ws* W, h
     CxArgs<Off> C{};
     C.A = A;
     C.sel = (uint32_t)W->cx_select, C.reg = W->cx_regions != nullptr, C.N = (uint32_t)W->cx_n, C.force = force;
+    C.var = W->cx_variants;
     if (W->cx_regions) C.A.T = *W->cx_regions;
     C.bits = W->cx_bits, C.sum = W->cx_sum, C.car = W->cx_car, C.hk = W->cx_hk, C.desc = W->cx_desc;
     const uint64_t nb = (C.A.s1 - C.A.s0 + FTB - 1) / FTB;
@@ -4623,6 +4775,8 @@ struct sid_dtext {
     uint32_t* d_tcnt = nullptr;
     uint64_t* d_toff = nullptr;
     uint64_t tcap = 0;
+    uint8_t* d_refb = nullptr;     // the sites' reference bytes (sid_chunk_ws::refb), made for a context with
+                                   // sid_opts.variants: by the parse, or by the first sid_dtext_format that asks
 };
 
 // The site view (SiteArgs) of each layout, every field the layout has; a stage
@@ -4636,6 +4790,7 @@ static SiteArgs<sid_off_t> dense_view(const sid_chunk_ws* W, const char* base, u
     A.text = base, A.len = c1, A.starts = W->starts, A.hdr = W->hdr, A.s1 = n;
     A.cls = W->cls, A.counts = W->counts, A.code = W->code, A.hom = W->hom, A.het = W->het, A.ct = ct;
     A.bsum = W->bsum;
+    A.refb = W->refb;
     if (ctx) A.len1 = ctx->ws.len1, A.len2 = ctx->ws.len2, A.str1 = ctx->ws.str1, A.str2 = ctx->ws.str2;
     return A;
 }
@@ -4656,6 +4811,7 @@ static SiteArgs<uint64_t> dtext_view(const sid_dtext* T, size_t begin, size_t en
     SiteArgs<uint64_t> A{};
     A.text = T->d_text, A.len = T->len, A.starts = T->d_starts, A.hdr = T->d_hdr, A.s0 = begin, A.s1 = end;
     A.code = code;
+    A.refb = T->d_refb;
     return A;
 }
 
@@ -4672,9 +4828,19 @@ extern "C" int sid_dtext_free(sid_dtext* t)
     for (void* p : {(void*)t->d_hdr, (void*)t->d_fb})
         if (p) (void)hipFree(p);
     for (void* p : {(void*)t->d_text, (void*)t->d_starts, (void*)t->d_counts, (void*)t->d_state, (void*)t->d_err,
-                    (void*)t->d_tcnt, (void*)t->d_toff})
+                    (void*)t->d_tcnt, (void*)t->d_toff, (void*)t->d_refb})
         if (p) (void)hipFree(p);
     delete t;
+    return SID_OK;
+}
+
+// the shard's reference bytes (once): off the resident text by its line offsets
+static int dtext_refs(sid_dtext* T, hipStream_t st)
+{
+    if (T->d_refb || T->nsites == 0) return SID_OK;
+    TCHECK(hipMalloc(&T->d_refb, T->nsites));
+    launch_ref_fill<uint64_t>(T->d_text, T->len, T->d_starts, 0, T->nsites, T->d_counts, nullptr, T->d_refb, st);
+    TCHECK(hipGetLastError());
     return SID_OK;
 }
 
@@ -4769,6 +4935,10 @@ extern "C" int sid_dtext_parse(sid_ctx* ctx, const char* text, size_t len, size_
     }
     const double w1 = wall();
     rc = dtext_index_parse(T, st, err_offset);
+    if (rc == SID_OK && (ctx->has_variants || ctx->cx_variants)) {   // the reference bytes, for sid_dtext_format
+        rc = dtext_refs(T, st);
+        if (rc == SID_OK && hipStreamSynchronize(st) != hipSuccess) rc = SID_EHIP;
+    }
     if (text_timing())
         std::fprintf(stderr, "{\"dtext_parse\": {\"bytes\": %llu, \"upload_s\": %.6f, \"index_parse_s\": %.6f}}\n",
                      (unsigned long long)len, w1 - w0, wall() - w1);
@@ -4847,6 +5017,10 @@ extern "C" int sid_dtext_parse_fd(sid_ctx* ctx, int fd, uint64_t offset, uint64_
         }
     const double w1 = wall();
     rc = dtext_index_parse(T, st, err_offset);
+    if (rc == SID_OK && (ctx->has_variants || ctx->cx_variants)) {   // the reference bytes, for sid_dtext_format
+        rc = dtext_refs(T, st);
+        if (rc == SID_OK && hipStreamSynchronize(st) != hipSuccess) rc = SID_EHIP;
+    }
     if (text_timing())
         std::fprintf(stderr,
                      "{\"dtext_parse_fd\": {\"bytes\": %llu, \"readers\": %d, \"upload_s\": %.6f, \"index_parse_s\": %.6f}}\n",
@@ -4941,6 +5115,20 @@ extern "C" int sid_dtext_format(sid_ctx* ctx, const sid_dtext* T, size_t begin, 
         SiteArgs<uint64_t> A = dtext_view(T, begin, end, d_rcode);
         A.xm = sel_word(ctx->opts.select), A.T = ctx->regtab;
         launch_region_mark<REG_CODE, false>(A, st);
+        hip(hipGetLastError());
+        d_code = d_rcode;
+    }
+    // the variants: the shard's reference bytes (made here when its parse had another context), and the
+    // records that are none dropped likewise, behind the region stage
+    if (rc == SID_OK && nb && (ctx->has_variants || ctx->cx_variants) && !T->d_refb) {
+        const int r2 = dtext_refs(const_cast<sid_dtext*>(T), st);
+        if (r2 != SID_OK) rc = r2;
+    }
+    if (rc == SID_OK && nb && ctx->has_variants && (d_rcode || hip(hipMalloc(&d_rcode, end))) &&
+        (d_code == d_rcode || hip(hipMemcpyAsync(d_rcode + begin, d_code + begin, n, hipMemcpyDeviceToDevice, st)))) {
+        SiteArgs<uint64_t> A = dtext_view(T, begin, end, d_rcode);
+        A.xm = sel_word(ctx->opts.select);
+        launch_variant_mark<REG_CODE, false>(A, st);
         hip(hipGetLastError());
         d_code = d_rcode;
     }
@@ -5328,8 +5516,9 @@ int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites)
         for (void* p : {(void*)W->starts, (void*)W->counts, (void*)W->code, (void*)W->hom, (void*)W->het,
                         (void*)W->bsum, (void*)W->boff, (void*)W->hdr, (void*)W->fb, (void*)W->lb, (void*)W->cls,
                         (void*)W->twv, (void*)W->cx_bits, (void*)W->cx_sum, (void*)W->cx_car, (void*)W->win_bits,
-                        W->win_key, (void*)W->win_hcnt, (void*)W->win_roff})
+                        W->win_key, (void*)W->win_hcnt, (void*)W->win_roff, (void*)W->refb})
             if (p) (void)hipFree(p);
+        W->refb = nullptr;
         W->win_bits = nullptr, W->win_key = nullptr, W->win_hcnt = nullptr, W->win_roff = nullptr;
         W->cx_bits = nullptr;
         W->cx_sum = W->cx_car = nullptr;
@@ -5348,6 +5537,7 @@ int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites)
         WCHECK(hipMalloc(&W->starts, m * sizeof(sid_off_t)));
         WCHECK(hipMalloc(&W->counts, m * 8));
         WCHECK(hipMalloc(&W->cls, m * 4));
+        if (W->variants || W->cx_variants) WCHECK(hipMalloc(&W->refb, m));   // the sites' reference bytes
         WCHECK(hipMalloc(&W->hdr, m * 16));
         WCHECK(hipMalloc(&W->twv, (m / 32 + 1) * 16));   // the tile parse's wave entries (tile_nwv)
         WCHECK(hipMalloc(&W->fb, m * 12));   // three site lists (sid_chunk_ws::fb)
@@ -5383,7 +5573,7 @@ void sid_chunk_release(sid_chunk_ws* W)
                     (void*)W->cx_bits, (void*)W->cx_sum, (void*)W->cx_car, (void*)W->cx_hk, (void*)W->cx_desc,
                     (void*)W->win_bits, W->win_key, (void*)W->win_hcnt, (void*)W->win_roff, (void*)W->win_cnt[0],
                     (void*)W->win_cnt[1], (void*)W->win_rows[0], (void*)W->win_rows[1], (void*)W->win_names[0],
-                    (void*)W->win_names[1]})
+                    (void*)W->win_names[1], (void*)W->refb})
         if (p) (void)hipFree(p);
     for (void* p : {(void*)W->win_h, (void*)W->win_eager[0], (void*)W->win_eager[1]})
         if (p) (void)hipHostFree(p);
@@ -5393,8 +5583,10 @@ void sid_chunk_release(sid_chunk_ws* W)
     const bool cx_on = W->cx_on;
     const sid_regtab* cx_regions = W->cx_regions;
     const int window = W->window;
+    const bool variants = W->variants, cx_variants = W->cx_variants;
     *W = sid_chunk_ws{};
     W->window = window;
+    W->variants = variants, W->cx_variants = cx_variants;
     W->select = select;
     W->regions = regions;
     W->cx_n = cx_n, W->cx_select = cx_select, W->cx_regions = cx_regions;
@@ -5410,6 +5602,8 @@ void sid_chunk_bind_context(sid_chunk_ws* W, const sid_ctx* ctx)
     W->window = ctx->opts.window;
     W->cx_select = ctx->cx_select;
     W->cx_regions = ctx->cx_regions ? &ctx->regtab : nullptr;
+    W->variants = ctx->has_variants;
+    W->cx_variants = ctx->cx_variants;
 }
 
 // blocks of the strided index kernels (count kernel, index stage per 50M
@@ -5485,6 +5679,8 @@ int sid_chunk_parse(sid_chunk_ws* W, const char* base, uint64_t c0, uint64_t c1,
         launch_parse(base, c1, W->starts, W->state + 1, n, W->counts, W->hdr, W->fb,
                      (unsigned long long*)(W->state + 6), (unsigned long long*)(W->state + 4), qmode, st);
     }
+    // the variants: the reference bytes off the text, by the line offsets this layout has
+    if (W->refb) launch_ref_fill<sid_off_t>(base, c1, W->starts, 0, n, W->counts, lens ? W->cls : nullptr, W->refb, st);
     WCHECK(hipGetLastError());
     return SID_OK;
 }
@@ -5520,6 +5716,7 @@ int sid_chunk_fmt_len(sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n
     CType ct;
     if (chunk_ctype(conf_type, &ct)) return SID_EINVAL;
     if (n > W->site_cap) return SID_EINVAL;
+    if ((W->variants || W->cx_variants) && n && !W->refb) return SID_ESTATE;
     WCHECK(hipMemsetAsync(W->lb, 0, 8 * 8, st));
     const uint64_t nb = (n + FTB - 1) / FTB;
     const SiteArgs<sid_off_t> S = dense_view(W, base, c1, n);
@@ -5531,6 +5728,11 @@ int sid_chunk_fmt_len(sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n
         SiteArgs<sid_off_t> A = S;
         A.xm = sel_word(W->select), A.T = *W->regions;
         launch_region_mark<REG_CODE, false>(A, st);
+    }
+    if (W->variants) {   // the records that are no variant likewise
+        SiteArgs<sid_off_t> A = S;
+        A.xm = sel_word(W->select);
+        launch_variant_mark<REG_CODE, false>(A, st);
     }
     // the context: the records outside the dilated selection, dropped likewise
     if (W->cx_on) launch_context_mark<REG_CODE, false>(S, W, st);
@@ -5575,6 +5777,7 @@ int sid_chunk_local_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     CType ct;
     if (local_ctype(ctx, conf_type, &ct)) return SID_EINVAL;
     if (n > W->site_cap || n >= (1ull << 32)) return SID_EINVAL;
+    if ((ctx->has_variants || ctx->cx_variants) && n && !W->refb) return SID_ESTATE;   // (a workspace not bound)
     // the fix-up's sites in the third list of W->fb
     uint32_t* miss = W->fb + 2 * W->site_cap;
     const uint64_t nb = (n + FTB - 1) / FTB;
@@ -5606,6 +5809,14 @@ int sid_chunk_local_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
         else launch_region_mark<REG_DENSE, true>(A, st);
         W->cls_ready = true;
     }
+    if (nb && ctx->has_variants) {   // the records that are no variant likewise
+        SiteArgs<sid_off_t> A = S;
+        A.xm = sel_word(ctx->opts.select);
+        if (local_sel(ctx)) A.len1 = ctx->ws.len1f, A.len2 = ctx->ws.len2f;   // (as the length pass)
+        if (W->cls_ready) launch_variant_mark<REG_DENSE, false>(A, st);
+        else launch_variant_mark<REG_DENSE, true>(A, st);
+        W->cls_ready = true;
+    }
     if (ctx->cx_on) {   // the context (no groups: the empty descriptor)
         if (W->cls_ready) launch_context_mark<REG_DENSE, false>(S, W, st);
         else launch_context_mark<REG_DENSE, true>(S, W, st);
@@ -5630,7 +5841,7 @@ int sid_chunk_local_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
         if (W->slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (slot_tile's exact range: a 4 GiB chunk has fewer)
         const SlotDiv cdiv = slot_div(W->slot_cap);
         const uint32_t xm = sel_word(ctx->opts.select);
-        if (ctx->has_regions || ctx->cx_on) {   // per group, by its record bytes (REG_LDS_MIN): the LDS assembly or the byte stores
+        if (ctx->has_regions || ctx->has_variants || ctx->cx_on) {   // per group, by its record bytes (REG_LDS_MIN): the LDS assembly or the byte stores
             auto put = W->tile_quad ? sid_local_put_reg_kernel<true, false> : sid_local_put_reg_kernel<true, true>;
             put<<<(unsigned)nbs, FTB, 0, st>>>(base, c1, nullptr, W->hdr, W->slots, W->tcnt, W->slot_cap, cdiv, W->twv,
                                                tile_nwv(W->slot_cap), W->counts, W->cls, ctx->ws.str1, ctx->ws.str2,
@@ -5688,7 +5899,7 @@ int sid_chunk_local_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     if (nb == 0) return hipMemcpyAsync(W->lb + 4, W->state + 4, 8, hipMemcpyDeviceToDevice, st) == hipSuccess
                             ? SID_OK : SID_EHIP;
     const uint32_t* cw = W->cls_ready ? W->cls : nullptr;
-    if (ctx->has_regions || ctx->cx_on) {   // (the class words: the parse's, or the marking kernel's; the groups with a record)
+    if (ctx->has_regions || ctx->has_variants || ctx->cx_on) {   // (the class words: the parse's, or the marking kernel's; the groups with a record)
         if (!cw) return SID_ESTATE;
         sid_local_put_reg_kernel<true><<<(unsigned)nb, FTB, 0, st>>>(
             base, c1, W->starts, W->hdr, n, nullptr, 0, SlotDiv{0, 0}, nullptr, 0, W->counts, cw, ctx->ws.str1,
@@ -5716,15 +5927,15 @@ static uint64_t tile_count(uint64_t c0, uint64_t c1, bool quad)
     return c1 > c0 ? (c1 - t0 + tp_tile(quad) - 1) / tp_tile(quad) : 0;
 }
 
-template <bool LOCAL, bool SEL = false>
+template <bool LOCAL, bool SEL = false, bool REF = false>
 static void launch_tile_parse(bool quad, const char* base, uint64_t c0, uint64_t c1, uint64_t ntp, const TileOut& O,
-                              const LocalLen& LL, hipStream_t st)
+                              const LocalLen& LL, uint8_t* refb, hipStream_t st)
 {
     const uint64_t tb = c0 & ~(uint64_t)15;
     if (quad)
-        sid_tile_parse_kernel<true, LOCAL, SEL><<<(unsigned)ntp, TB, 0, st>>>(base, tb, c0, c1, O, LL);
+        sid_tile_parse_kernel<true, LOCAL, SEL, REF><<<(unsigned)ntp, TB, 0, st>>>(base, tb, c0, c1, O, LL, refb);
     else
-        sid_tile_parse_kernel<false, LOCAL, SEL><<<(unsigned)ntp, TB, 0, st>>>(base, tb, c0, c1, O, LL);
+        sid_tile_parse_kernel<false, LOCAL, SEL, REF><<<(unsigned)ntp, TB, 0, st>>>(base, tb, c0, c1, O, LL, refb);
 #ifdef SID_TP_STAMP
     {
         const uint64_t m = std::min<uint64_t>(ntp, TP_STAMP_N);
@@ -5772,7 +5983,8 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
     const uint64_t slots = ntp * cap;
     if (slots > W->site_cap || ntp > W->tile_cap || slots >= (1ull << 32)) return SID_EINVAL;
     if (ntp * tile_nwv(cap) > W->site_cap / 32 + 1) return SID_EINVAL;   // (never: cap >= 64)
-    if ((ctx->has_regions || ctx->cx_on || W->window) && slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (the marking kernels' slot_tile: its exact range, as the writer's)
+    if ((ctx->has_variants || ctx->cx_variants) && slots && !W->refb) return SID_ESTATE;   // (a workspace not bound)
+    if ((ctx->has_regions || ctx->has_variants || ctx->cx_on || W->window) && slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (the marking kernels' slot_tile: its exact range, as the writer's)
     W->lens_ready = false;
     W->cls_ready = false;
     W->slot_cap = cap;
@@ -5796,12 +6008,16 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
     const LocalLen LL{sel ? ctx->ws.len1f : ctx->ws.len1, sel ? ctx->ws.len2f : ctx->ws.len2, W->bsum, miss, W->lb,
                       W->cls};
     const TileOut O{cap, W->tcnt, W->hdr, W->counts, W->fb, W->starts, W->lb, W->state, W->twv, tile_nwv(cap)};
-    if (sel) launch_tile_parse<true, true>(quad, base, c0, c1, ntp, O, LL, st);
-    else launch_tile_parse<true>(quad, base, c0, c1, ntp, O, LL, st);
+    const bool ref = W->refb != nullptr;   // (the variants: the slots' reference bytes out of the parse)
+    if (sel) ref ? launch_tile_parse<true, true, true>(quad, base, c0, c1, ntp, O, LL, W->refb, st)
+                 : launch_tile_parse<true, true>(quad, base, c0, c1, ntp, O, LL, nullptr, st);
+    else ref ? launch_tile_parse<true, false, true>(quad, base, c0, c1, ntp, O, LL, W->refb, st)
+             : launch_tile_parse<true>(quad, base, c0, c1, ntp, O, LL, nullptr, st);
     const LocalFix F{LL, ctx->K, ctx->d_lnt, ct, W->code, W->hom, W->het, sel_word(ctx->opts.select)};
-    auto serial = sel ? sid_tile_serial_kernel<true, true> : sid_tile_serial_kernel<true>;
+    auto serial = sel ? (ref ? sid_tile_serial_kernel<true, true, true> : sid_tile_serial_kernel<true, true>)
+                      : (ref ? sid_tile_serial_kernel<true, false, true> : sid_tile_serial_kernel<true>);
     serial<<<TILE_SERIAL_GRID, TB, 0, st>>>(base, c1, W->fb, W->starts, W->lb, W->tcnt, ntp, cap, W->counts, W->hdr,
-                                            (unsigned long long*)(W->state + 4), F);
+                                            (unsigned long long*)(W->state + 4), F, W->refb);
     if (W->window) {   // the windowed summary: on the class words before a mark rewrites them
         const int rc = quad ? window_stage<REG_TILE, false>(S, W, 0, false, st)
                             : window_stage<REG_TILE, true>(S, W, 0, false, st);
@@ -5813,6 +6029,13 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
         A.len1 = LL.len1, A.len2 = LL.len2;   // (as the parse)
         if (quad) launch_region_mark<REG_TILE, false>(A, st);
         else launch_region_mark<REG_TILE, true>(A, st);
+    }
+    if (ctx->has_variants) {   // the slots whose record is no variant likewise
+        SiteArgs<sid_off_t> A = S;
+        A.xm = sel_word(ctx->opts.select);
+        A.len1 = LL.len1, A.len2 = LL.len2;   // (as the parse)
+        if (quad) launch_variant_mark<REG_TILE, false>(A, st);
+        else launch_variant_mark<REG_TILE, true>(A, st);
     }
     if (ctx->cx_on) {   // the context: the slots outside the dilated selection likewise
         if (quad) launch_context_mark<REG_TILE, false>(S, W, st);
@@ -5845,10 +6068,12 @@ int sid_chunk_tile_counts(sid_chunk_ws* W, const char* base, uint64_t c0, uint64
     }
     const LocalLen LL{};
     const TileOut O{cap, W->tcnt, W->hdr, W->counts, W->fb, W->starts, W->lb, W->state, nullptr, 0};
-    launch_tile_parse<false>(quad, base, c0, c1, ntp, O, LL, st);
-    sid_tile_serial_kernel<false><<<TILE_SERIAL_GRID, TB, 0, st>>>(base, c1, W->fb, W->starts, W->lb, W->tcnt, ntp,
-                                                      cap, W->counts, W->hdr,
-                                                      (unsigned long long*)(W->state + 4), LocalFix{});
+    // (the variants: the slots' reference bytes too, for sid_chunk_tile_compact)
+    if (W->refb) launch_tile_parse<false, false, true>(quad, base, c0, c1, ntp, O, LL, W->refb, st);
+    else launch_tile_parse<false>(quad, base, c0, c1, ntp, O, LL, nullptr, st);
+    (W->refb ? sid_tile_serial_kernel<false, false, true> : sid_tile_serial_kernel<false>)
+        <<<TILE_SERIAL_GRID, TB, 0, st>>>(base, c1, W->fb, W->starts, W->lb, W->tcnt, ntp, cap, W->counts, W->hdr,
+                                          (unsigned long long*)(W->state + 4), LocalFix{}, W->refb);
     // the tiles' first sites in file order (state[0]: the chunk's sites; over the cap: void)
     launch_scan(W->tcnt, ntp, W->toff, W->state, nullptr,
                 (uint64_t*)((char*)W->tcnt + ((ntp * 4 + 7) & ~(size_t)7)), st);
@@ -5856,14 +6081,17 @@ int sid_chunk_tile_counts(sid_chunk_ws* W, const char* base, uint64_t c0, uint64
     return SID_OK;
 }
 
-int sid_chunk_tile_compact(sid_chunk_ws* W, sid_off_t* starts, uint64_t* counts, uint64_t* hdr, hipStream_t st)
+int sid_chunk_tile_compact(sid_chunk_ws* W, sid_off_t* starts, uint64_t* counts, uint64_t* hdr, uint8_t* refb,
+                           hipStream_t st)
 {
     if (!W->slot_cap) return SID_ESTATE;
+    if (refb && !W->refb) return SID_ESTATE;
     if (W->slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (slot_tile's exact range: a 4 GiB chunk has fewer)
     const SlotDiv cdiv = slot_div(W->slot_cap);
     const unsigned grid = (unsigned)std::min<uint64_t>(std::max<uint64_t>((W->slots + TB - 1) / TB, 1), 8192);
-    sid_tile_compact_kernel<<<grid, TB, 0, st>>>(W->tcnt, W->toff, W->slots, W->slot_cap, cdiv, W->counts, W->hdr,
-                                                 starts, counts, hdr);
+    (refb ? sid_tile_compact_kernel<true> : sid_tile_compact_kernel<false>)
+        <<<grid, TB, 0, st>>>(W->tcnt, W->toff, W->slots, W->slot_cap, cdiv, W->counts, W->hdr, starts, counts, hdr,
+                              W->refb, refb);
     W->slot_cap = 0;   // the dense layout again
     WCHECK(hipGetLastError());
     return SID_OK;
@@ -5874,6 +6102,7 @@ int sid_chunk_lynch_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     sid_lynch_fmt V;
     if (sid_lynch_fmt_view(ctx, &V) != SID_OK) return SID_ESTATE;
     if (n > W->site_cap) return SID_EINVAL;
+    if ((ctx->has_variants || ctx->cx_variants) && n && !W->refb) return SID_ESTATE;   // (a workspace not bound)
     WCHECK(hipMemsetAsync(W->lb, 0, 8 * 8, st));   // [1] bytes, [2] range flag
     const uint64_t nb = (n + FTB - 1) / FTB;
     SiteArgs<sid_off_t> S = dense_view(W, base, c1, n);
@@ -5895,6 +6124,7 @@ int sid_chunk_lynch_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
             A.T = ctx->regtab;
             launch_region_mark<REG_LYNCH, false>(A, st);
         }
+        if (ctx->has_variants) launch_variant_mark<REG_LYNCH, false>(S, st);   // the records that are no variant likewise
         (ctx->opts.select == SID_SELECT_HET ? sid_lynch_len_kernel<true> : sid_lynch_len_kernel<false>)
             <<<(unsigned)((nb + LPB - 1) / LPB), FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->counts, V, W->bsum);
     }
