@@ -97,6 +97,29 @@
  *     device count, lanes, budgets, source kind or tile shape.  Any other
  *     value: SID_EINVAL from sid_create and sid_engine_create.  Host
  *     formatting: sid_variants_mark, before sid_context_mark.
+ *   - Depth bounds (sid_set_depth / sid_engine_set_depth; --min-depth N,
+ *     --max-depth N): the records of the sites whose coverage lies in a range.
+ *     A site's depth is A + C + G + T of its profile_t as the parser stores it
+ *     -- what sid_sites_counts / sid_dtext_counts report, the coverage
+ *     call.cpp:66-70 compares with 4 -- not the pileup's fourth column: '*',
+ *     'N', and '.' / ',' on a reference that is no base do not count.  The
+ *     bounds are min (default 0) and max (default 0 = no upper bound); a record
+ *     is emitted when min <= depth and (max == 0 or depth <= max).  Valid:
+ *     0 <= min <= 262140 (4 x 65535), and max == 0 or min <= max <= 262140;
+ *     anything else is SID_EINVAL.  min == 0 and max == 0 is the option switched
+ *     off: every byte and every kernel as without it.  The same formatters
+ *     then emit only those records, byte for byte and in U's order.  With a
+ *     selection by label, region and / or variant a record is emitted when all
+ *     of them hold; with --context N, S is the set all of them keep; the
+ *     window rows never change.  Header, stderr, exit status, the calls, the -R
+ *     prior, the Lynch estimate and Benjamini-Hochberg see every site and are
+ *     unchanged; bytes_out stays exact in every sink mode, and the result does
+ *     not depend on chunk size, device count, lanes, budgets, source kind or
+ *     tile shape.  The Lynch methods print no record below coverage 4, so
+ *     min <= 4 changes nothing there.  The bounds are no field of sid_opts
+ *     (whose layout stands): they are set on a context or an engine.  Host
+ *     formatting: sid_depth_mark, after the marks by label, region and variant
+ *     and before sid_context_mark.
  *   - Counts layout: profile_t (pileup.hpp:7) = 4 x uint16 {A,C,G,T} per site,
  *     array of structures, 8 bytes per site.
  */
@@ -230,6 +253,13 @@ int sid_regions_mark(const sid_regions* r, const struct sid_sites* s, size_t beg
  * of sid_regions_mark, before sid_context_mark.  SID_EINVAL for a range outside
  * the sites or a NULL pointer. */
 int sid_variants_mark(const struct sid_sites* s, size_t begin, size_t end, uint8_t* code /* host */);
+/* The depth bounds on the host path (Conventions): sets SID_CODE_DROPPED on the
+ * host codes code[begin, end) of the sites whose depth is below min or, with
+ * max != 0, above max -- after the marks by label, region and variant, before
+ * sid_context_mark.  SID_EINVAL for bounds outside the Conventions', a range
+ * outside the sites or a NULL pointer. */
+#define SID_DEPTH_MAX 262140
+int sid_depth_mark(const struct sid_sites* s, size_t begin, size_t end, int min, int max, uint8_t* code /* host */);
 
 /* -------------------------------------------------------------- windows --
  * The rows of the windowed summary (Conventions).  chrom is not NUL-terminated.
@@ -264,6 +294,10 @@ int sid_create(int device, const sid_opts* opts, sid_ctx** out);
 int sid_destroy(sid_ctx* ctx);
 /* Replaces snp_prior after the -R estimate (call.cpp:223-234). */
 int sid_set_prior(sid_ctx* ctx, double snp_prior);
+/* The depth bounds (Conventions) of every formatter call made on the context
+ * after it (sid_dtext_format and the chunk formatters behind it); (0, 0)
+ * switches them off again.  SID_EINVAL for bounds outside the Conventions'. */
+int sid_set_depth(sid_ctx* ctx, int min, int max);
 
 /* ------------------------------------------------------- -m local (a5-a8) --
  * Per-site replacement of callSiteMLError's per-profile loop + per-site gather
@@ -535,8 +569,8 @@ typedef struct {
     uint64_t chunks;
     uint64_t bytes_in;           /* input text bytes                                 */
     uint64_t bytes_out;          /* CSV bytes written (header excluded; with a
-                                    selection by label, region or variant: the
-                                    selected records', with a context theirs too;
+                                    selection by label, region, variant or depth:
+                                    the selected records', with a context theirs too;
                                     exact in every sink mode)                                */
     uint64_t chunks_held;        /* formatted in the first pass                      */
     uint64_t chunks_retained;    /* text kept in HBM for the second pass             */
@@ -579,6 +613,12 @@ int sid_engine_create(const sid_opts* opts, const sid_engine_cfg* cfg, sid_engin
 int sid_engine_destroy(sid_engine* e);
 int sid_engine_devices(const sid_engine* e);
 sid_ctx* sid_engine_context(sid_engine* e, int i);
+/* sid_set_depth on every pipeline's context.  Allowed after sid_engine_create
+ * and again once a run has ended (the emit returned, or the ingest failed);
+ * between a successful sid_engine_ingest and its emit: SID_ESTATE (-m local
+ * formats during the ingest).  The bounds hold for every later run until they
+ * are set again. */
+int sid_engine_set_depth(sid_engine* e, int min, int max);
 /* Host placement of pipeline i (a multi-GPU node: each GPU's uploader,
  * compute and drain threads run on the CPUs local to its PCI device, and its
  * pinned host buffers are allocated from them, so their pages sit on the

@@ -135,6 +135,9 @@ SIGNATURES = [
     ("sid_regions_free", None, [_P]),
     ("sid_regions_mark", _I, [_P, _P, _SZ, _SZ, _P]),
     ("sid_variants_mark", _I, [_P, _SZ, _SZ, _P]),
+    ("sid_depth_mark", _I, [_P, _SZ, _SZ, _I, _I, _P]),
+    ("sid_set_depth", _I, [_P, _I, _I]),
+    ("sid_engine_set_depth", _I, [_P, _I, _I]),
     ("sid_device_count", _I, [C.POINTER(C.c_int)]),
     ("sid_create", _I, [_I, C.POINTER(Opts), C.POINTER(_P)]),
     ("sid_destroy", _I, [_P]),
@@ -508,6 +511,21 @@ def variants_mark(sites: Sites, code: np.ndarray, begin: int = 0, end: int = Non
     return out
 
 
+def depth_mark(sites: Sites, code: np.ndarray, min_depth: int, max_depth: int, begin: int = 0,
+               end: int = None) -> np.ndarray:
+    """sid_depth_mark on a copy of the codes: the sites of [begin, end) whose
+    depth -- the sum of their four counts -- is below min_depth or, with
+    max_depth != 0, above max_depth get SID_CODE_DROPPED, so format_csv skips
+    them.  After select_mark / regions_mark / variants_mark, before
+    context_mark."""
+    out = np.array(code, np.uint8, copy=True)
+    if out.size != len(sites):
+        raise SidError(1, "depth_mark: one code per site")
+    check(lib().sid_depth_mark(sites.handle, int(begin), out.size if end is None else int(end), int(min_depth),
+                               int(max_depth), _ptr(out)), "sid_depth_mark")
+    return out
+
+
 def format_double(v: float) -> str:
     buf = C.create_string_buffer(48)
     k = lib().sid_format_double(float(v), buf, 48)
@@ -697,13 +715,15 @@ def crc32(data: bytes, crc: int = 0) -> int:
 class Context:
     """One sid_ctx (one device, one host thread)."""
 
-    def __init__(self, device: int = 0, **opts):
+    def __init__(self, device: int = 0, min_depth: int = 0, max_depth: int = 0, **opts):
         self.opts = make_opts(**opts)
         self.device = device
         h = C.c_void_p()
         check(lib().sid_create(device, C.byref(self.opts), C.byref(h)), "sid_create")
         self.opts.regions = None   # (the context holds its own copy of the set)
         self.h = h
+        if min_depth or max_depth:   # (the depth bounds are no field of sid_opts)
+            self.set_depth(min_depth, max_depth)
 
     @classmethod
     def wrap(cls, handle, device: int = 0):
@@ -725,6 +745,10 @@ class Context:
 
     def set_prior(self, prior: float):
         check(lib().sid_set_prior(self.h, float(prior)), "sid_set_prior")
+
+    def set_depth(self, min_depth: int, max_depth: int):
+        """The depth bounds of every formatter call from now on (0, 0: none)."""
+        check(lib().sid_set_depth(self.h, int(min_depth), int(max_depth)), "sid_set_depth")
 
     # raw device-pointer entry points -------------------------------------
     def call_local(self, counts_ptr, n, code_ptr, hom_ptr, het_ptr, stream=None):
@@ -801,7 +825,7 @@ class Engine:
 
     def __init__(self, method="local", devices=1, first_device=0, chunk_bytes=0, slots=0, hold_bytes=0,
                  retain_bytes=0, host_threads=0, verbose=False, device_sink=False, lanes=0, host_hold_bytes=0,
-                 **opts):
+                 min_depth=0, max_depth=0, **opts):
         self.opts = make_opts(method=method, **opts)
         cfg = EngineCfg()
         lib().sid_engine_cfg_default(C.byref(cfg))
@@ -815,6 +839,8 @@ class Engine:
         self.opts.regions = None   # (every pipeline's context holds its own copy of the set)
         self.h = h
         self._keep = None
+        if min_depth or max_depth:   # (the depth bounds are no field of sid_opts)
+            self.set_depth(min_depth, max_depth)
 
     def close(self):
         if getattr(self, "h", None):
@@ -829,6 +855,11 @@ class Engine:
 
     def context(self, i=0):
         return lib().sid_engine_context(self.h, i)
+
+    def set_depth(self, min_depth: int, max_depth: int):
+        """The depth bounds of every run from now on (0, 0: none); SID_ESTATE
+        between an ingest and its emit."""
+        check(lib().sid_engine_set_depth(self.h, int(min_depth), int(max_depth)), "sid_engine_set_depth")
 
     def placement(self, i=0) -> dict:
         """Pipeline i's host placement: its GPU's NUMA node, the CPUs its

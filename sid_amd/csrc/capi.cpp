@@ -155,6 +155,7 @@ extern "C" int sid_create(int device, const sid_opts* opts, sid_ctx** out)
     // the variants: a marking stage of their own, or one more test of the context's
     c->has_variants = c->opts.variants && !c->cx_on;
     c->cx_variants = c->opts.variants && c->cx_on;
+    c->cx_base = c->cx_on;   // (sid_set_depth: the bounds alone may select under a context)
     sid_build_local_k(c->opts, &c->K);
     // SID_TABLE_TAIL=0: the second-level class table off, its sites through
     // the fix-up (tests/test_local_gpu.py covers both)
@@ -247,6 +248,25 @@ extern "C" int sid_set_prior(sid_ctx* c, double snp_prior)
     (void)hipSetDevice(c->device);
     hipError_t e = sid_build_table(c);
     return e == hipSuccess ? SID_OK : sid_set_hip_error(e);
+}
+
+// The depth bounds (sid.h Conventions): a marking stage of their own, or one
+// more test of the context's.  With sid_opts.context and no other selection the
+// bounds are the selection: they switch the context's route on, and off again.
+extern "C" int sid_set_depth(sid_ctx* c, int min, int max)
+{
+    if (!c) return SID_EINVAL;
+    if (min < 0 || min > SID_DEPTH_MAX || (max != 0 && (max < min || max > SID_DEPTH_MAX))) return SID_EINVAL;
+    c->depth_min = min;
+    c->depth_max = max;
+    const bool on = min != 0 || max != 0;
+    if (!c->cx_base) {
+        c->cx_on = on && c->opts.context > 0;
+        c->cx_n = c->cx_on ? c->opts.context : 0;
+    }
+    c->has_depth = on && !c->cx_on;
+    c->cx_depth = on && c->cx_on;
+    return SID_OK;
 }
 
 extern "C" int sid_call_local(sid_ctx* c, const uint16_t* counts, size_t n, uint8_t* code,

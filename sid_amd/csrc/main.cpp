@@ -12,7 +12,21 @@
 // reference's flags): --devices N, --threads N, --stats, --host-parse,
 // --chunk-bytes N, --hold-bytes N, --retain-bytes N, --host-hold N,
 // --only het|hom|all, --regions FILE, --bgzf, --context N, --windows W,
-// --windows-out FILE, --variants.
+// --windows-out FILE, --variants, --min-depth N, --max-depth N.
+//
+// --min-depth N / --max-depth N (decimal, 0 .. 262140; given twice, the last
+// wins) write the header and only the records of the sites whose depth -- A +
+// C + G + T of the parsed profile, not the pileup's fourth column (sid.h
+// Conventions) -- is at least the one and, when --max-depth is not 0, at most
+// the other, chosen before the records are formatted (sid_engine_set_depth).
+// 0 and 0 is the run without them.  Everything else, stderr included, is as
+// without them; with --only, --regions and / or --variants all must hold,
+// --context N counts from what they all keep, and the --windows rows do not
+// change.  An argument that is no such number: "sid: --min-depth: expected
+// 0..262140, got ARG" (likewise --max-depth); a minimum above a maximum that is
+// not 0: "sid: --min-depth above --max-depth"; each on stderr with exit status
+// 1 and nothing on stdout.  With --host-parse: sid_depth_mark.  Not listed by
+// -h, whose text stays the reference's.
 //
 // --variants (no argument) writes the header and only the records whose
 // genotype is not homozygous reference (sid_opts.variants, sid.h Conventions):
@@ -287,6 +301,7 @@ int main(int argc, char** argv)
     sid_regions* regions = nullptr;   // --regions (kept for the run: --host-parse marks with it)
     std::atexit(free_regions);   // (the ways out that do not go through finish)
     const char* windows_out = nullptr;   // --windows-out
+    int min_depth = 0, max_depth = 0;    // --min-depth, --max-depth
     static const struct option LONG[] = {{"devices", required_argument, nullptr, 1},
                                          {"threads", required_argument, nullptr, 2},
                                          {"stats", no_argument, nullptr, 3},
@@ -302,6 +317,8 @@ int main(int argc, char** argv)
                                          {"windows", required_argument, nullptr, 13},
                                          {"windows-out", required_argument, nullptr, 14},
                                          {"variants", no_argument, nullptr, 15},
+                                         {"min-depth", required_argument, nullptr, 16},
+                                         {"max-depth", required_argument, nullptr, 17},
                                          {nullptr, 0, nullptr, 0}};
     int flag;
     while ((flag = getopt_long(argc, argv, "E:Rhm:p:r:", LONG, nullptr)) != -1) {
@@ -400,9 +417,31 @@ int main(int argc, char** argv)
         }
         case 14: windows_out = optarg; break;
         case 15: opt.o.variants = 1; break;
+        case 16:
+        case 17: {
+            int v = 0;
+            bool good = *optarg != 0 && std::strlen(optarg) <= 6;
+            for (const char* c = optarg; good && *c; ++c) {
+                good = *c >= '0' && *c <= '9';
+                v = v * 10 + (*c - '0');
+            }
+            if (!good || v > SID_DEPTH_MAX) {
+                std::fflush(stdout);
+                std::fprintf(stderr, "sid: --%s-depth: expected 0..262140, got %s\n", flag == 16 ? "min" : "max", optarg);
+                std::exit(EXIT_FAILURE);
+            }
+            (flag == 16 ? min_depth : max_depth) = v;   // (given twice: the last wins)
+            break;
+        }
         default: std::exit(EXIT_FAILURE);
         }
     }
+    if (max_depth != 0 && min_depth > max_depth) {
+        std::fflush(stdout);
+        std::fputs("sid: --min-depth above --max-depth\n", stderr);
+        std::exit(EXIT_FAILURE);
+    }
+    const bool depth_on = min_depth != 0 || max_depth != 0;
     if ((opt.o.window > 0) != (windows_out != nullptr)) {
         std::fflush(stdout);
         std::fputs("sid: --windows and --windows-out go together\n", stderr);
@@ -463,7 +502,8 @@ int main(int argc, char** argv)
         cfg.host_hold_bytes = opt.host_hold;
         cfg.host_threads = T;
         cfg.verbose = 1;
-        return sid_engine_create(&opt.o, &cfg, &eng);
+        const int rc = sid_engine_create(&opt.o, &cfg, &eng);
+        return rc == SID_OK && depth_on ? sid_engine_set_depth(eng, min_depth, max_depth) : rc;
     };
     int dev_rc = SID_OK, eng_rc = SID_OK;
     double t0 = 0, tc = 0;
@@ -522,6 +562,7 @@ int main(int argc, char** argv)
         sid_opts o = opt.o;
         o.window = 0;   // (this path's rows come from the host codes: sid_windows_host)
         CHECK(sid_create(d % ndev, &o, &s.ctx), "context");
+        if (depth_on) CHECK(sid_set_depth(s.ctx, min_depth, max_depth), "depth");
         HCHECK(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking), "stream");
     };
     auto alloc_out = [&](Shard& s) {
@@ -805,11 +846,12 @@ int main(int argc, char** argv)
         if (windows_out) CHECK(sid_windows_host(sites, 0, n, h_code, opt.o.window, &wrows, &nwrows), "windows");
         window_rows = nwrows;
         std::vector<uint8_t> code_all;   // --context: the codes before the selections marked them
-        if (opt.o.context > 0 && (opt.o.select != SID_SELECT_ALL || regions || opt.o.variants))
+        if (opt.o.context > 0 && (opt.o.select != SID_SELECT_ALL || regions || opt.o.variants || depth_on))
             code_all.assign(h_code, h_code + n);
         CHECK(sid_select_mark(h_code, n, opt.o.select), "select");   // --only: the other labels' sites get no record
         CHECK(sid_regions_mark(regions, sites, 0, n, h_code), "regions");   // --regions: nor the sites outside
         if (opt.o.variants) CHECK(sid_variants_mark(sites, 0, n, h_code), "variants");   // --variants: nor the others
+        if (depth_on) CHECK(sid_depth_mark(sites, 0, n, min_depth, max_depth, h_code), "depth");   // the depth bounds: nor those outside
         if (!code_all.empty()) CHECK(sid_context_mark(code_all.data(), h_code, n, opt.o.context), "context");
         const size_t BLOCK = 1u << 18;
         const size_t nblocks = (n + BLOCK - 1) / BLOCK;

@@ -294,6 +294,21 @@ extern "C" int sid_variants_mark(const sid_sites* s, size_t begin, size_t end, u
     return SID_OK;
 }
 
+// The depth bounds on the host path (sid.h Conventions): a site stays when the
+// sum of its four counts is at least min and, with max != 0, at most max.
+extern "C" int sid_depth_mark(const sid_sites* s, size_t begin, size_t end, int min, int max, uint8_t* code)
+{
+    if (min < 0 || min > SID_DEPTH_MAX || (max != 0 && (max < min || max > SID_DEPTH_MAX))) return SID_EINVAL;
+    if (!s || begin > end || end > s->pos.size() || s->counts.size() != 4 * s->pos.size()) return SID_EINVAL;
+    if (!code && end != begin) return SID_EINVAL;
+    for (size_t i = begin; i < end; ++i) {
+        const uint16_t* c = s->counts.data() + 4 * i;
+        const uint32_t d = (uint32_t)c[0] + c[1] + c[2] + c[3];
+        if (d < (uint32_t)min || (max != 0 && d > (uint32_t)max)) code[i] |= SID_CODE_DROPPED;
+    }
+    return SID_OK;
+}
+
 extern "C" size_t sid_sites_chrom_segments(const sid_sites* s) { return s ? s->seg_name.size() : 0; }
 extern "C" const char* sid_sites_chrom_name(const sid_sites* s, size_t k, uint64_t* start)
 {

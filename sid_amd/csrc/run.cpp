@@ -1062,6 +1062,25 @@ extern "C" sid_ctx* sid_engine_context(sid_engine* e, int i)
     return e->devs[i]->ctx;
 }
 
+// The depth bounds of every pipeline's context, and of its workspace (the
+// formatters that take no context); the context's route follows where the
+// bounds alone select under sid_opts.context.  Not between an ingest and its
+// emit: -m local's records are formatted by then, the others' are not.
+extern "C" int sid_engine_set_depth(sid_engine* e, int min, int max)
+{
+    if (!e) return SID_EINVAL;
+    if (min < 0 || min > SID_DEPTH_MAX || (max != 0 && (max < min || max > SID_DEPTH_MAX))) return SID_EINVAL;
+    if (e->ingested) return SID_ESTATE;
+    for (auto& d : e->devs) {
+        const int rc = sid_set_depth(d->ctx, min, max);
+        if (rc != SID_OK) return rc;
+        sid_chunk_bind_context(&d->ws, d->ctx);
+    }
+    e->cx_n = e->devs[0]->ctx->cx_n;
+    e->cx_on = e->devs[0]->ctx->cx_on;
+    return SID_OK;
+}
+
 extern "C" int sid_engine_placement(const sid_engine* e, int i, sid_placement* out)
 {
     if (!e || !out || i < 0 || i >= (int)e->devs.size()) return SID_EINVAL;

@@ -136,6 +136,15 @@ struct sid_ctx {
     // way the parse keeps every site's reference byte (sid_chunk_ws::refb)
     bool has_variants = false;
     bool cx_variants = false;
+    // the depth bounds (sid_set_depth; 0, 0 = off): has_depth, the marking stage of their own
+    // (sid_depth_mark_kernel) beside the variant stage; cx_depth, under a context's route, one more test of
+    // the marking stage's.  No per-site state: a site's depth is in its class word or its counts (sv_depth).
+    // cx_base: the route's switch as sid_create left it -- with a context but no other selection the bounds
+    // switch the route on and off themselves
+    int depth_min = 0, depth_max = 0;
+    bool has_depth = false;
+    bool cx_depth = false;
+    bool cx_base = false;
     // the route's switch: a context in effect, or (cx_n = 0) a selection by label under sid_opts.window, whose
     // stage reads every site's label in front of the marking stage
     bool cx_on = false;
@@ -231,6 +240,10 @@ struct sid_chunk_ws {
     bool variants = false;
     bool cx_variants = false;
     uint8_t* refb = nullptr;
+    // likewise the owner's depth bounds (sid_ctx::has_depth, cx_depth, depth_min, depth_max)
+    bool depth = false;
+    bool cx_depth = false;
+    uint32_t depth_min = 0, depth_max = 0;
     unsigned long long* cx_bits = nullptr;
     uint4* cx_sum = nullptr;
     uint4* cx_car = nullptr;

@@ -3652,6 +3652,7 @@ struct SiteArgs {
     sid_lynch_fmt V;              // REG_LYNCH: the classes
     sid_regtab T;                 // the region set (the region stage; the context, when a set selects)
     const uint8_t* refb;          // the reference bytes (sid_chunk_ws::refb; the variant stage, the context's test)
+    uint32_t dmin, dmax;          // the depth bounds (the depth stage, the context's test; dmax 0: no upper bound)
 };
 
 // MODE REG_TILE: OPT = the lane shape (compact words and wave entries);
@@ -3778,6 +3779,41 @@ __device__ __forceinline__ bool sv_variant(const SiteArgs<Off>& A, uint64_t i, u
     return (c & 3u) != r || ((c >> 2) & 3u) != r;
 }
 
+// A site's depth, A + C + G + T of its profile_t (sid.h Conventions), without a
+// per-site array of its own:
+//   REG_TILE, REG_DENSE  the class word names the table entry of (nf, ns, r2),
+//                        and depth = nf + ns + r2: local_entry inverted (the
+//                        LDS table's swizzle, sid_tab_slot, is an XOR with
+//                        nf's low bits; the second table is linear).  A fix-up
+//                        site (SID_CLS_MISS) has no entry, but every parse
+//                        stores its counts for the fix-up.  REG_DENSE with OPT
+//                        has every site's counts and no words yet
+//   REG_LYNCH, REG_CODE  the counts
+template <int MODE, bool OPT, class Off>
+__device__ __forceinline__ uint32_t sv_depth(const SiteArgs<Off>& A, uint64_t i, uint32_t w)
+{
+    if ((MODE == REG_TILE || (MODE == REG_DENSE && !OPT)) && w != SID_CLS_MISS) {
+        const uint32_t k = w & 0xFFFFFu;
+        if (k < SID_TAB_N) {
+            const uint32_t nf = k / (SID_TAB_NS * SID_TAB_NR);
+            const uint32_t x = (k ^ nf) & (SID_TAB_NS * SID_TAB_NR - 1);   // ns * SID_TAB_NR + r2
+            return nf + x / SID_TAB_NR + x % SID_TAB_NR;
+        }
+        const uint32_t q = k - SID_TAB_N;   // (nf * SID_TAB2_NS + ns) * SID_TAB2_NR + r2
+        return q / (SID_TAB2_NS * SID_TAB2_NR) + q / SID_TAB2_NR % SID_TAB2_NS + q % SID_TAB2_NR;
+    }
+    const uint64_t c = A.counts[i];
+    return (uint32_t)(c & 0xFFFFu) + (uint32_t)(c >> 16 & 0xFFFFu) + (uint32_t)(c >> 32 & 0xFFFFu) + (uint32_t)(c >> 48);
+}
+
+// ... and whether it lies within the bounds
+template <int MODE, bool OPT, class Off>
+__device__ __forceinline__ bool sv_depth_in(const SiteArgs<Off>& A, uint64_t i, uint32_t w)
+{
+    const uint32_t d = sv_depth<MODE, OPT>(A, i, w);
+    return d >= A.dmin && (A.dmax == 0 || d <= A.dmax);
+}
+
 // The marking stages' back end: a dropped site's marker, and for -m local its
 // group's record bytes again (every thread of the block calls it).  keep: the
 // site keeps a record, rec_len() bytes long.
@@ -3878,13 +3914,6 @@ __global__ __launch_bounds__(FTB) void sid_variant_mark_kernel(const SiteArgs<Of
     });
 }
 
-template <int MODE, bool OPT, class Off>
-static void launch_variant_mark(const SiteArgs<Off>& A, hipStream_t st)
-{
-    const uint64_t nb = (A.s1 - A.s0 + FTB - 1) / FTB;
-    if (nb) sid_variant_mark_kernel<MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(A);
-}
-
 // The reference bytes of sites [s0, s1) of a layout with line offsets, off the
 // resident text (the two-pass parse's sites, a resident shard's): the class of
 // the line's third token, and "no counted base" from the site's counts -- or,
@@ -3919,6 +3948,66 @@ static void launch_ref_fill(const char* text, uint64_t len, const Off* starts, u
     sid_ref_fill_kernel<Off><<<grid, TB, 0, st>>>(text, len, starts, s0, s1, counts, cls, refb);
 }
 
+// ------------------------------------------------------------------- depth --
+// The depth bounds (sid_set_depth; sid_ctx::has_depth): the records of the
+// sites whose depth (sv_depth) lies outside them get the region stage's
+// markers, beside the variant stage and as that stage does it -- behind the
+// region and window stages, a -m local group without record bytes passed over
+// on its sum.  VAR: the variant test in the same pass, when both options are
+// given (one read of the words and one set of marks instead of two).
+// (REG_DENSE with OPT: this kernel writes the class words, for the writer)
+template <int MODE, bool OPT, bool VAR, class Off>
+__global__ __launch_bounds__(FTB) void sid_depth_mark_kernel(const SiteArgs<Off> A)
+{
+    if ((MODE == REG_TILE || MODE == REG_DENSE) && A.bsum[blockIdx.x] == 0) return;   // (block-uniform)
+    const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
+    uint32_t w;
+    bool site = sv_site<MODE, OPT, SV_FILTERED | SV_STORE>(A, i, &w);
+    if (MODE == REG_CODE && site) site = !code_out(A.code[i], A.xm);   // (no record anyway)
+    bool in = site && sv_depth_in<MODE, OPT>(A, i, w);
+    if (VAR) in = in && sv_variant<MODE>(A, i, w);
+    sv_mark<MODE>(A, i, site && !in, in, [&]() -> int {
+        Reader R{A.text, A.len};
+        const Head h = sv_head<MODE, OPT>(A, i, w, R);
+        if (w == SID_CLS_MISS) {   // the fix-up's site
+            const uint8_t c = A.code[i];
+            return code_out(c, A.xm) ? 0 : miss_len<4>(h, c, A.hom[i], A.het[i], A.ct);
+        }
+        const uint32_t k = w & 0xFFFFFu;
+        const uint32_t L = k < SID_TAB_N ? A.len1[k] : A.len2[k - SID_TAB_N];
+        return L && L != 0xFFu ? local_rec_len(h, L) : 0;
+    });
+}
+
+// SID_DEPTH_SPLIT=1 (a measurement switch): with sid_opts.variants
+// the variant stage's kernel and this stage's one after the other instead
+static bool depth_split()
+{
+    static const bool on = [] {
+        const char* g = std::getenv("SID_DEPTH_SPLIT");
+        return g && std::atoi(g) != 0;
+    }();
+    return on;
+}
+
+// the variant stage (var), the depth stage (dep) or both over the sites of A
+// (dmin, dmax: the bounds)
+template <int MODE, bool OPT, class Off>
+static void launch_select_mark(SiteArgs<Off> A, bool var, bool dep, uint32_t dmin, uint32_t dmax, hipStream_t st)
+{
+    const uint64_t nb = (A.s1 - A.s0 + FTB - 1) / FTB;
+    if (!nb) return;
+    A.dmin = dmin, A.dmax = dmax;
+    if (var && (!dep || depth_split())) {
+        sid_variant_mark_kernel<MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(A);
+        // (REG_DENSE with OPT: the words, and the variant stage's markers in them, are stored now)
+        if (dep) launch_select_mark<MODE, MODE == REG_DENSE ? false : OPT>(A, false, true, dmin, dmax, st);
+        return;
+    }
+    if (var) sid_depth_mark_kernel<MODE, OPT, true, Off><<<(unsigned)nb, FTB, 0, st>>>(A);
+    else sid_depth_mark_kernel<MODE, OPT, false, Off><<<(unsigned)nb, FTB, 0, st>>>(A);
+}
+
 // ---------------------------------------------------------------- context --
 // The context (sid_opts.context = N with a selection; sid_ctx::cx_n): every
 // selected record with the N records before and after it, in record rank --
@@ -3948,6 +4037,7 @@ struct CxArgs {
     uint32_t sel;                 // SID_SELECT_*: the label selected (ALL: every label)
     uint32_t reg;                 // a region set selects too
     uint32_t var;                 // ... and the variant test (A.refb)
+    uint32_t dep;                 // ... and the depth bounds (A.dmin, A.dmax)
     uint32_t N;
     uint32_t force;               // the chunk's edge records are forced (not for a whole text at once)
     unsigned long long* bits;     // per wave of slots: [0] records, [1] selected
@@ -3972,6 +4062,7 @@ __global__ __launch_bounds__(FTB) void sid_context_flag_kernel(const CxArgs<Off>
     if (site) sv_label<MODE>(A, i, w, &rec, &het);
     bool sel = rec && (C.sel == SID_SELECT_ALL || het == (C.sel == SID_SELECT_HET));
     if (C.var) sel = sel && sv_variant<MODE>(A, i, w);   // (uniform)
+    if (C.dep) sel = sel && sv_depth_in<MODE, OPT>(A, i, w);   // (uniform)
     if (C.reg) {   // (uniform)
         Head h{0, 0, 0, 0};
         if (sel) h = sv_head<MODE, OPT>(A, i, w, R);
@@ -4208,6 +4299,7 @@ static void launch_context_mark(const SiteArgs<Off>& A, const sid_chunk_ws* W, h
     C.A = A;
     C.sel = (uint32_t)W->cx_select, C.reg = W->cx_regions != nullptr, C.N = (uint32_t)W->cx_n, C.force = force;
     C.var = W->cx_variants;
+    C.dep = W->cx_depth, C.A.dmin = W->depth_min, C.A.dmax = W->depth_max;
     if (W->cx_regions) C.A.T = *W->cx_regions;
     C.bits = W->cx_bits, C.sum = W->cx_sum, C.car = W->cx_car, C.hk = W->cx_hk, C.desc = W->cx_desc;
     const uint64_t nb = (C.A.s1 - C.A.s0 + FTB - 1) / FTB;
@@ -4812,6 +4904,7 @@ static SiteArgs<uint64_t> dtext_view(const sid_dtext* T, size_t begin, size_t en
     A.text = T->d_text, A.len = T->len, A.starts = T->d_starts, A.hdr = T->d_hdr, A.s0 = begin, A.s1 = end;
     A.code = code;
     A.refb = T->d_refb;
+    A.counts = T->d_counts;   // (the depth stage reads them)
     return A;
 }
 
@@ -5124,11 +5217,13 @@ extern "C" int sid_dtext_format(sid_ctx* ctx, const sid_dtext* T, size_t begin, 
         const int r2 = dtext_refs(const_cast<sid_dtext*>(T), st);
         if (r2 != SID_OK) rc = r2;
     }
-    if (rc == SID_OK && nb && ctx->has_variants && (d_rcode || hip(hipMalloc(&d_rcode, end))) &&
+    // (the depth bounds: the records outside them, in the same place)
+    if (rc == SID_OK && nb && (ctx->has_variants || ctx->has_depth) && (d_rcode || hip(hipMalloc(&d_rcode, end))) &&
         (d_code == d_rcode || hip(hipMemcpyAsync(d_rcode + begin, d_code + begin, n, hipMemcpyDeviceToDevice, st)))) {
         SiteArgs<uint64_t> A = dtext_view(T, begin, end, d_rcode);
         A.xm = sel_word(ctx->opts.select);
-        launch_variant_mark<REG_CODE, false>(A, st);
+        launch_select_mark<REG_CODE, false>(A, ctx->has_variants, ctx->has_depth, (uint32_t)ctx->depth_min,
+                                            (uint32_t)ctx->depth_max, st);
         hip(hipGetLastError());
         d_code = d_rcode;
     }
@@ -5562,6 +5657,12 @@ int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites)
         }
         W->site_cap = m;
     }
+    if (W->cx_on && !W->cx_bits && W->site_cap) {   // the route switched on behind the growth (sid_set_depth)
+        const uint64_t ng = (W->site_cap + FTB - 1) / FTB + 1;
+        WCHECK(hipMalloc(&W->cx_bits, ng * (FTB / 64) * 16));
+        WCHECK(hipMalloc(&W->cx_sum, ng * sizeof(uint4)));
+        WCHECK(hipMalloc(&W->cx_car, ng * sizeof(uint4)));
+    }
     return SID_OK;
 }
 
@@ -5584,7 +5685,10 @@ void sid_chunk_release(sid_chunk_ws* W)
     const sid_regtab* cx_regions = W->cx_regions;
     const int window = W->window;
     const bool variants = W->variants, cx_variants = W->cx_variants;
+    const bool depth = W->depth, cx_depth = W->cx_depth;
+    const uint32_t depth_min = W->depth_min, depth_max = W->depth_max;
     *W = sid_chunk_ws{};
+    W->depth = depth, W->cx_depth = cx_depth, W->depth_min = depth_min, W->depth_max = depth_max;
     W->window = window;
     W->variants = variants, W->cx_variants = cx_variants;
     W->select = select;
@@ -5604,6 +5708,9 @@ void sid_chunk_bind_context(sid_chunk_ws* W, const sid_ctx* ctx)
     W->cx_regions = ctx->cx_regions ? &ctx->regtab : nullptr;
     W->variants = ctx->has_variants;
     W->cx_variants = ctx->cx_variants;
+    W->depth = ctx->has_depth;
+    W->cx_depth = ctx->cx_depth;
+    W->depth_min = (uint32_t)ctx->depth_min, W->depth_max = (uint32_t)ctx->depth_max;
 }
 
 // blocks of the strided index kernels (count kernel, index stage per 50M
@@ -5729,10 +5836,10 @@ int sid_chunk_fmt_len(sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n
         A.xm = sel_word(W->select), A.T = *W->regions;
         launch_region_mark<REG_CODE, false>(A, st);
     }
-    if (W->variants) {   // the records that are no variant likewise
+    if (W->variants || W->depth) {   // the records that are no variant, or outside the depth bounds, likewise
         SiteArgs<sid_off_t> A = S;
         A.xm = sel_word(W->select);
-        launch_variant_mark<REG_CODE, false>(A, st);
+        launch_select_mark<REG_CODE, false>(A, W->variants, W->depth, W->depth_min, W->depth_max, st);
     }
     // the context: the records outside the dilated selection, dropped likewise
     if (W->cx_on) launch_context_mark<REG_CODE, false>(S, W, st);
@@ -5809,12 +5916,13 @@ int sid_chunk_local_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
         else launch_region_mark<REG_DENSE, true>(A, st);
         W->cls_ready = true;
     }
-    if (nb && ctx->has_variants) {   // the records that are no variant likewise
+    if (nb && (ctx->has_variants || ctx->has_depth)) {   // the records that are no variant, or outside the depth bounds, likewise
         SiteArgs<sid_off_t> A = S;
         A.xm = sel_word(ctx->opts.select);
         if (local_sel(ctx)) A.len1 = ctx->ws.len1f, A.len2 = ctx->ws.len2f;   // (as the length pass)
-        if (W->cls_ready) launch_variant_mark<REG_DENSE, false>(A, st);
-        else launch_variant_mark<REG_DENSE, true>(A, st);
+        const uint32_t dmin = (uint32_t)ctx->depth_min, dmax = (uint32_t)ctx->depth_max;
+        if (W->cls_ready) launch_select_mark<REG_DENSE, false>(A, ctx->has_variants, ctx->has_depth, dmin, dmax, st);
+        else launch_select_mark<REG_DENSE, true>(A, ctx->has_variants, ctx->has_depth, dmin, dmax, st);
         W->cls_ready = true;
     }
     if (ctx->cx_on) {   // the context (no groups: the empty descriptor)
@@ -5841,7 +5949,7 @@ int sid_chunk_local_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
         if (W->slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (slot_tile's exact range: a 4 GiB chunk has fewer)
         const SlotDiv cdiv = slot_div(W->slot_cap);
         const uint32_t xm = sel_word(ctx->opts.select);
-        if (ctx->has_regions || ctx->has_variants || ctx->cx_on) {   // per group, by its record bytes (REG_LDS_MIN): the LDS assembly or the byte stores
+        if (ctx->has_regions || ctx->has_variants || ctx->has_depth || ctx->cx_on) {   // per group, by its record bytes (REG_LDS_MIN): the LDS assembly or the byte stores
             auto put = W->tile_quad ? sid_local_put_reg_kernel<true, false> : sid_local_put_reg_kernel<true, true>;
             put<<<(unsigned)nbs, FTB, 0, st>>>(base, c1, nullptr, W->hdr, W->slots, W->tcnt, W->slot_cap, cdiv, W->twv,
                                                tile_nwv(W->slot_cap), W->counts, W->cls, ctx->ws.str1, ctx->ws.str2,
@@ -5899,7 +6007,7 @@ int sid_chunk_local_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     if (nb == 0) return hipMemcpyAsync(W->lb + 4, W->state + 4, 8, hipMemcpyDeviceToDevice, st) == hipSuccess
                             ? SID_OK : SID_EHIP;
     const uint32_t* cw = W->cls_ready ? W->cls : nullptr;
-    if (ctx->has_regions || ctx->has_variants || ctx->cx_on) {   // (the class words: the parse's, or the marking kernel's; the groups with a record)
+    if (ctx->has_regions || ctx->has_variants || ctx->has_depth || ctx->cx_on) {   // (the class words: the parse's, or the marking kernel's; the groups with a record)
         if (!cw) return SID_ESTATE;
         sid_local_put_reg_kernel<true><<<(unsigned)nb, FTB, 0, st>>>(
             base, c1, W->starts, W->hdr, n, nullptr, 0, SlotDiv{0, 0}, nullptr, 0, W->counts, cw, ctx->ws.str1,
@@ -5984,7 +6092,7 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
     if (slots > W->site_cap || ntp > W->tile_cap || slots >= (1ull << 32)) return SID_EINVAL;
     if (ntp * tile_nwv(cap) > W->site_cap / 32 + 1) return SID_EINVAL;   // (never: cap >= 64)
     if ((ctx->has_variants || ctx->cx_variants) && slots && !W->refb) return SID_ESTATE;   // (a workspace not bound)
-    if ((ctx->has_regions || ctx->has_variants || ctx->cx_on || W->window) && slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (the marking kernels' slot_tile: its exact range, as the writer's)
+    if ((ctx->has_regions || ctx->has_variants || ctx->has_depth || ctx->cx_on || W->window) && slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (the marking kernels' slot_tile: its exact range, as the writer's)
     W->lens_ready = false;
     W->cls_ready = false;
     W->slot_cap = cap;
@@ -6030,12 +6138,13 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
         if (quad) launch_region_mark<REG_TILE, false>(A, st);
         else launch_region_mark<REG_TILE, true>(A, st);
     }
-    if (ctx->has_variants) {   // the slots whose record is no variant likewise
+    if (ctx->has_variants || ctx->has_depth) {   // the slots whose record is no variant, or outside the depth bounds, likewise
         SiteArgs<sid_off_t> A = S;
         A.xm = sel_word(ctx->opts.select);
         A.len1 = LL.len1, A.len2 = LL.len2;   // (as the parse)
-        if (quad) launch_variant_mark<REG_TILE, false>(A, st);
-        else launch_variant_mark<REG_TILE, true>(A, st);
+        const uint32_t dmin = (uint32_t)ctx->depth_min, dmax = (uint32_t)ctx->depth_max;
+        if (quad) launch_select_mark<REG_TILE, false>(A, ctx->has_variants, ctx->has_depth, dmin, dmax, st);
+        else launch_select_mark<REG_TILE, true>(A, ctx->has_variants, ctx->has_depth, dmin, dmax, st);
     }
     if (ctx->cx_on) {   // the context: the slots outside the dilated selection likewise
         if (quad) launch_context_mark<REG_TILE, false>(S, W, st);
@@ -6124,7 +6233,10 @@ int sid_chunk_lynch_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
             A.T = ctx->regtab;
             launch_region_mark<REG_LYNCH, false>(A, st);
         }
-        if (ctx->has_variants) launch_variant_mark<REG_LYNCH, false>(S, st);   // the records that are no variant likewise
+        // the records that are no variant, or outside the depth bounds, likewise
+        if (ctx->has_variants || ctx->has_depth)
+            launch_select_mark<REG_LYNCH, false>(S, ctx->has_variants, ctx->has_depth, (uint32_t)ctx->depth_min,
+                                                 (uint32_t)ctx->depth_max, st);
         (ctx->opts.select == SID_SELECT_HET ? sid_lynch_len_kernel<true> : sid_lynch_len_kernel<false>)
             <<<(unsigned)((nb + LPB - 1) / LPB), FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->counts, V, W->bsum);
     }
