@@ -120,6 +120,36 @@
  *     (whose layout stands): they are set on a context or an engine.  Host
  *     formatting: sid_depth_mark, after the marks by label, region and variant
  *     and before sid_context_mark.
+ *   - VCF (sid_set_format / sid_engine_set_format with SID_FORMAT_VCF; --vcf):
+ *     what a record is, not which records exist.  The same formatters print a
+ *     VCF line for exactly the sites that print a CSV record under the same
+ *     options, in the same order -- the selections by label, region, variant
+ *     and depth and the context decide which records exist, the format then
+ *     applies to those -- and a line is a pure function of that CSV record, the
+ *     site's reference byte and its depth.  Ten columns, tab-separated, '\n':
+ *         CHROM POS . REF ALT . . DP=<d>;HOM=<hom_conf>;HET=<het_conf> GT <g>
+ *     CHROM, POS: the bytes the CSV record prints; the position is the atoi
+ *     integer, so it may be 0 or negative -- parity with the CSV wins over VCF
+ *     validity.  REF: the single byte of the line's third token, upper-cased as
+ *     pileup.cpp:79 does, when that is one of A, C, G, T; else N.  DP: the depth
+ *     of the paragraph above (A + C + G + T of the profile_t), in decimal.  With
+ *     DP = 0 (no counted base: the "hom,TT" placeholder of -m local) ALT is "."
+ *     and <g> is "./.".  Otherwise, X and Y being the two bytes of the CSV's gt
+ *     field: ALT is the distinct bytes among X, Y that differ from REF, X's
+ *     first, joined by ','; none: ".".  Allele 0 is REF, the ALT alleles are 1
+ *     and 2, and <g> is the allele numbers of X and Y, the smaller first, joined
+ *     by '/': 0/0, 0/1, 1/1 or 1/2.  With REF N every counted base is an ALT.
+ *     HOM, HET: the %g bytes of the CSV's hom_conf and het_conf fields, byte for
+ *     byte (nan, -nan, inf as printed there).  The header (sid_vcf_header)
+ *     replaces the CSV's header line; it has no ##contig lines, a pileup does
+ *     not hold the chrom lengths.  stderr, the exit status, "nothing is written
+ *     before the whole input has parsed", a failing run's empty output, the
+ *     calls, the estimate, Benjamini-Hochberg and the window rows are
+ *     unchanged; bytes_out stays exact in every sink mode, and the result does
+ *     not depend on chunk size, device count, lanes, budgets, source kind or
+ *     tile shape.  The format is no field of sid_opts (whose layout stands).
+ *     Host formatting: sid_format_vcf in place of sid_format_csv, after the
+ *     same marks.
  *   - Counts layout: profile_t (pileup.hpp:7) = 4 x uint16 {A,C,G,T} per site,
  *     array of structures, 8 bytes per site.
  */
@@ -298,6 +328,11 @@ int sid_set_prior(sid_ctx* ctx, double snp_prior);
  * after it (sid_dtext_format and the chunk formatters behind it); (0, 0)
  * switches them off again.  SID_EINVAL for bounds outside the Conventions'. */
 int sid_set_depth(sid_ctx* ctx, int min, int max);
+/* The record format (Conventions, "VCF") of every formatter call made on the
+ * context after it (sid_dtext_format and the chunk formatters behind it).
+ * SID_EINVAL for any other value. */
+enum { SID_FORMAT_CSV = 0, SID_FORMAT_VCF = 1 };
+int sid_set_format(sid_ctx* ctx, int format);
 
 /* ------------------------------------------------------- -m local (a5-a8) --
  * Per-site replacement of callSiteMLError's per-profile loop + per-site gather
@@ -418,6 +453,20 @@ const char* sid_sites_chrom_name(const sid_sites* s, size_t k, uint64_t* start);
 int sid_format_csv(const sid_sites* s, size_t begin, size_t end, const uint8_t* code,
                    const double* hom_conf, const double* het_conf, const char* conf_type,
                    char* buf, size_t cap, size_t* len);
+/* The same records as VCF lines (Conventions, "VCF"): a line for exactly the
+ * sites sid_format_csv prints a record for (code bit 6 set: skipped), REF from
+ * sid_sites_refs and DP from the counts.  Sized as sid_format_csv: SID_ENOMEM
+ * and a sufficient *len when cap is too small.  SID_EINVAL for a NULL pointer,
+ * a range outside the sites, or sites that carry no reference bytes. */
+int sid_format_vcf(const sid_sites* s, size_t begin, size_t end, const uint8_t* code,
+                   const double* hom_conf, const double* het_conf, char* buf, size_t cap, size_t* len);
+/* The VCF header of a run with these options, in place of the CSV's header
+ * line: "##fileformat=VCFv4.2", "##source=" + sid_version(), an ##INFO line
+ * each for DP (Integer), HOM and HET (Float), "##sidConfType=p_value" or
+ * "probability" (the CSV's seventh column: probability for SID_METHOD_BAYES),
+ * the ##FORMAT line of GT and the "#CHROM ... SAMPLE" line.  No NUL is
+ * written.  Sized as sid_format_csv; SID_EINVAL for a NULL opts or len. */
+int sid_vcf_header(const sid_opts* opts, char* buf, size_t cap, size_t* len);
 /* %g formatting of one double exactly as std::ostream does (precision 6). */
 int sid_format_double(double v, char* buf, size_t cap);
 
@@ -619,6 +668,12 @@ sid_ctx* sid_engine_context(sid_engine* e, int i);
  * formats during the ingest).  The bounds hold for every later run until they
  * are set again. */
 int sid_engine_set_depth(sid_engine* e, int min, int max);
+/* sid_set_format on every pipeline's context, under the same state rules:
+ * SID_EINVAL for a value that is no SID_FORMAT_*, SID_ESTATE between a
+ * successful sid_engine_ingest and its emit.  The format holds for every later
+ * run until it is set again; the caller passes sid_vcf_header's text as the
+ * emit's header.  bytes_out counts the VCF lines' bytes. */
+int sid_engine_set_format(sid_engine* e, int format);
 /* Host placement of pipeline i (a multi-GPU node: each GPU's uploader,
  * compute and drain threads run on the CPUs local to its PCI device, and its
  * pinned host buffers are allocated from them, so their pages sit on the

@@ -138,6 +138,10 @@ SIGNATURES = [
     ("sid_depth_mark", _I, [_P, _SZ, _SZ, _I, _I, _P]),
     ("sid_set_depth", _I, [_P, _I, _I]),
     ("sid_engine_set_depth", _I, [_P, _I, _I]),
+    ("sid_set_format", _I, [_P, _I]),
+    ("sid_engine_set_format", _I, [_P, _I]),
+    ("sid_format_vcf", _I, [_P, _SZ, _SZ, _P, _P, _P, _P, _SZ, C.POINTER(C.c_size_t)]),
+    ("sid_vcf_header", _I, [C.POINTER(Opts), _P, _SZ, C.POINTER(C.c_size_t)]),
     ("sid_device_count", _I, [C.POINTER(C.c_int)]),
     ("sid_create", _I, [_I, C.POINTER(Opts), C.POINTER(_P)]),
     ("sid_destroy", _I, [_P]),
@@ -242,6 +246,15 @@ def _ptr(a: np.ndarray):
 
 
 SELECT = {"all": 0, "het": 1, "hom": 2}   # SID_SELECT_*: the records emitted, by label (--only)
+FORMATS = {"csv": 0, "vcf": 1}            # SID_FORMAT_*: what a record is (--vcf)
+
+
+def _format(fmt) -> int:
+    if isinstance(fmt, str):
+        if fmt not in FORMATS:
+            raise SidError(1, f"format: expected one of {sorted(FORMATS)}, got {fmt!r}")
+        return FORMATS[fmt]
+    return int(fmt)   # (another value: SID_EINVAL from the setter)
 
 
 class Regions:
@@ -459,6 +472,38 @@ def format_csv(sites: Sites, code: np.ndarray, hom: np.ndarray, het: np.ndarray,
     check(L.sid_format_csv(sites.handle, begin, n, _ptr(code), _ptr(hom), _ptr(het), conf_type.encode(),
                            buf, need.value, C.byref(ln)), "format")
     return buf.raw[: ln.value]
+
+
+def format_vcf(sites: Sites, code: np.ndarray, hom: np.ndarray, het: np.ndarray, begin: int = 0,
+               end: int = None) -> bytes:
+    """sid_format_vcf: the records format_csv prints, as VCF lines (REF from the
+    sites' reference bytes, DP from their counts), without the header."""
+    L = lib()
+    code = np.ascontiguousarray(code, np.uint8)
+    hom = np.ascontiguousarray(hom, np.float64)
+    het = np.ascontiguousarray(het, np.float64)
+    need = C.c_size_t(0)
+    n = len(sites) if end is None else end
+    st = L.sid_format_vcf(sites.handle, begin, n, _ptr(code), _ptr(hom), _ptr(het), None, 0, C.byref(need))
+    if st not in (SID_OK, 3):
+        check(st, "sid_format_vcf")
+    buf = C.create_string_buffer(max(need.value, 1))
+    ln = C.c_size_t(0)
+    check(L.sid_format_vcf(sites.handle, begin, n, _ptr(code), _ptr(hom), _ptr(het), buf, need.value,
+                           C.byref(ln)), "sid_format_vcf")
+    return buf.raw[: ln.value]
+
+
+def vcf_header(method="local", **opts) -> bytes:
+    """sid_vcf_header: the VCF header of a run with these options."""
+    o = make_opts(method=method, **opts)
+    need = C.c_size_t(0)
+    st = lib().sid_vcf_header(C.byref(o), None, 0, C.byref(need))
+    if st not in (SID_OK, 3):
+        check(st, "sid_vcf_header")
+    buf = C.create_string_buffer(max(need.value, 1))
+    check(lib().sid_vcf_header(C.byref(o), buf, need.value, C.byref(need)), "sid_vcf_header")
+    return buf.raw[: need.value]
 
 
 def select_mark(code: np.ndarray, select="all") -> np.ndarray:
@@ -715,7 +760,8 @@ def crc32(data: bytes, crc: int = 0) -> int:
 class Context:
     """One sid_ctx (one device, one host thread)."""
 
-    def __init__(self, device: int = 0, min_depth: int = 0, max_depth: int = 0, **opts):
+    def __init__(self, device: int = 0, min_depth: int = 0, max_depth: int = 0, format="csv", **opts):
+        fmt = _format(format)
         self.opts = make_opts(**opts)
         self.device = device
         h = C.c_void_p()
@@ -724,6 +770,8 @@ class Context:
         self.h = h
         if min_depth or max_depth:   # (the depth bounds are no field of sid_opts)
             self.set_depth(min_depth, max_depth)
+        if fmt:                      # (nor is the record format)
+            self.set_format(fmt)
 
     @classmethod
     def wrap(cls, handle, device: int = 0):
@@ -749,6 +797,10 @@ class Context:
     def set_depth(self, min_depth: int, max_depth: int):
         """The depth bounds of every formatter call from now on (0, 0: none)."""
         check(lib().sid_set_depth(self.h, int(min_depth), int(max_depth)), "sid_set_depth")
+
+    def set_format(self, format):
+        """The record format ("csv" / "vcf", or SID_FORMAT_*) of every formatter call from now on."""
+        check(lib().sid_set_format(self.h, _format(format)), "sid_set_format")
 
     # raw device-pointer entry points -------------------------------------
     def call_local(self, counts_ptr, n, code_ptr, hom_ptr, het_ptr, stream=None):
@@ -825,7 +877,8 @@ class Engine:
 
     def __init__(self, method="local", devices=1, first_device=0, chunk_bytes=0, slots=0, hold_bytes=0,
                  retain_bytes=0, host_threads=0, verbose=False, device_sink=False, lanes=0, host_hold_bytes=0,
-                 min_depth=0, max_depth=0, **opts):
+                 min_depth=0, max_depth=0, format="csv", **opts):
+        fmt = _format(format)
         self.opts = make_opts(method=method, **opts)
         cfg = EngineCfg()
         lib().sid_engine_cfg_default(C.byref(cfg))
@@ -841,6 +894,8 @@ class Engine:
         self._keep = None
         if min_depth or max_depth:   # (the depth bounds are no field of sid_opts)
             self.set_depth(min_depth, max_depth)
+        if fmt:                      # (nor is the record format)
+            self.set_format(fmt)
 
     def close(self):
         if getattr(self, "h", None):
@@ -860,6 +915,12 @@ class Engine:
         """The depth bounds of every run from now on (0, 0: none); SID_ESTATE
         between an ingest and its emit."""
         check(lib().sid_engine_set_depth(self.h, int(min_depth), int(max_depth)), "sid_engine_set_depth")
+
+    def set_format(self, format):
+        """The record format ("csv" / "vcf", or SID_FORMAT_*) of every run from
+        now on; SID_ESTATE between an ingest and its emit.  The header stays the
+        caller's: emit(header=vcf_header(...))."""
+        check(lib().sid_engine_set_format(self.h, _format(format)), "sid_engine_set_format")
 
     def placement(self, i=0) -> dict:
         """Pipeline i's host placement: its GPU's NUMA node, the CPUs its

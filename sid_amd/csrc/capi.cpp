@@ -16,6 +16,7 @@
 #include "regions.h"
 #include "sid_internal.h"
 #include "synth.h"
+#include "vcf.h"
 
 // process-wide: the streaming engine's worker threads report through it
 static std::atomic<int> g_last_hip_error{0};
@@ -266,6 +267,34 @@ extern "C" int sid_set_depth(sid_ctx* c, int min, int max)
     }
     c->has_depth = on && !c->cx_on;
     c->cx_depth = on && c->cx_on;
+    return SID_OK;
+}
+
+// The record format (sid.h Conventions, "VCF"): the marking stages are the
+// CSV's; the VCF stage then replaces the length and put kernels, and the parse
+// keeps every site's reference byte (sid_chunk_ws::refb) as it does for the
+// variants.
+extern "C" int sid_set_format(sid_ctx* c, int format)
+{
+    if (!c || (format != SID_FORMAT_CSV && format != SID_FORMAT_VCF)) return SID_EINVAL;
+    c->format = format;
+    return SID_OK;
+}
+
+extern "C" int sid_vcf_header(const sid_opts* opts, char* buf, size_t cap, size_t* len)
+{
+    if (!opts || !len) return SID_EINVAL;
+    std::string h = "##fileformat=VCFv4.2\n##source=";
+    h += sid_version();
+    h += "\n" SID_VCF_HEAD_INFO "##sidConfType=";
+    h += opts->method == SID_METHOD_BAYES ? "probability" : "p_value";
+    h += "\n" SID_VCF_HEAD_TAIL;
+    if (!buf || cap < h.size()) {
+        *len = h.size();
+        return SID_ENOMEM;
+    }
+    std::memcpy(buf, h.data(), h.size());
+    *len = h.size();
     return SID_OK;
 }
 

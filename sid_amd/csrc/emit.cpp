@@ -14,6 +14,7 @@
 #include "../../include/sid.h"
 
 #include "sites.h"
+#include "vcf.h"
 
 namespace {
 inline char* put_double(char* p, double v)
@@ -99,6 +100,66 @@ extern "C" int sid_format_csv(const sid_sites* s, size_t begin, size_t end, cons
         std::memcpy(p, conf_type, tlen);
         p += tlen;
         *p++ = '\n';
+    }
+    *len = (size_t)(p - buf);
+    return SID_OK;
+}
+
+// The same records as VCF (sid.h Conventions, "VCF"; vcf.h): a line for
+// exactly the sites sid_format_csv prints one for, from the site's reference
+// byte and its counts beside what the CSV record holds.
+extern "C" int sid_format_vcf(const sid_sites* s, size_t begin, size_t end, const uint8_t* code,
+                              const double* hom_conf, const double* het_conf, char* buf, size_t cap, size_t* len)
+{
+    if (!s || !len || !code || !hom_conf || !het_conf) return SID_EINVAL;
+    if (end > s->pos.size() || begin > end) return SID_EINVAL;
+    // (a sid_sites the parser did not make has no reference bytes)
+    if (s->ref.size() != s->pos.size() || s->counts.size() != 4 * s->pos.size()) return SID_EINVAL;
+    static const char ACGT[] = "ACGT";
+    size_t k = 0;   // the segment containing `begin`
+    {
+        size_t lo = 0, hi = s->seg_start.size();
+        while (lo + 1 < hi) {
+            size_t mid = (lo + hi) / 2;
+            if (s->seg_start[mid] <= begin) lo = mid; else hi = mid;
+        }
+        k = lo;
+    }
+    size_t maxname = 0;
+    for (const auto& n : s->seg_name) maxname = std::max(maxname, n.size());
+    // (put_double's scratch: 32 bytes past the last field written)
+    const size_t need = (end - begin) * (maxname + SID_VCF_REC_MAX) + 64;
+    if (!buf || cap < need) {
+        *len = need;
+        return SID_ENOMEM;
+    }
+    char* p = buf;
+    size_t next_seg = k + 1 < s->seg_start.size() ? s->seg_start[k + 1] : (size_t)-1;
+    const std::string* name = s->seg_name.empty() ? nullptr : &s->seg_name[k];
+    for (size_t i = begin; i < end; ++i) {
+        while (i >= next_seg) {
+            ++k;
+            name = &s->seg_name[k];
+            next_seg = k + 1 < s->seg_start.size() ? s->seg_start[k + 1] : (size_t)-1;
+        }
+        const uint8_t c = code[i];
+        if (c & 0x40) continue;   // no record (as sid_format_csv)
+        const uint16_t* cn = s->counts.data() + 4 * i;
+        const uint32_t depth = (uint32_t)cn[0] + cn[1] + cn[2] + cn[3];
+        const uint8_t r = s->ref[i];
+        const uint8_t up = r >= 'a' && r <= 'z' ? (uint8_t)(r - 32) : r;   // (toupper, ASCII: pileup.cpp:79)
+        const uint32_t refcls = up == 'A' ? 0u : up == 'C' ? 1u : up == 'G' ? 2u : up == 'T' ? 3u : 4u;
+        const sid_vcf_gt v = sid_vcf_call(refcls, ACGT[c & 3], ACGT[(c >> 2) & 3], depth);
+        std::memcpy(p, name->data(), name->size());
+        p += name->size();
+        *p++ = '\t';
+        p = put_int(p, s->pos[i]);
+        auto put = [p](uint32_t j, uint32_t ch) { p[j] = (char)ch; };
+        p += sid_vcf_put_a(0, v, depth, put);
+        p = put_double(p, hom_conf[i]);
+        p += sid_vcf_put_b(0, [p](uint32_t j, uint32_t ch) { p[j] = (char)ch; });
+        p = put_double(p, het_conf[i]);
+        p += sid_vcf_put_c(0, v, [p](uint32_t j, uint32_t ch) { p[j] = (char)ch; });
     }
     *len = (size_t)(p - buf);
     return SID_OK;

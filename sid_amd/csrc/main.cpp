@@ -12,7 +12,19 @@
 // reference's flags): --devices N, --threads N, --stats, --host-parse,
 // --chunk-bytes N, --hold-bytes N, --retain-bytes N, --host-hold N,
 // --only het|hom|all, --regions FILE, --bgzf, --context N, --windows W,
-// --windows-out FILE, --variants, --min-depth N, --max-depth N.
+// --windows-out FILE, --variants, --min-depth N, --max-depth N, --vcf.
+//
+// --vcf (no argument) writes the records as VCF lines behind a VCF header
+// (sid_vcf_header) in place of the CSV and its header line (sid.h Conventions,
+// "VCF"): a line for exactly the sites that print a CSV record under the same
+// options, in the same order, with REF from the pileup's third column, DP the
+// counted depth, the two confidences as INFO fields and the gt field as ALT and
+// GT.  --only, --regions, --variants, --min-depth / --max-depth and --context
+// decide which records exist exactly as for the CSV; stderr, the exit status
+// and the --windows rows are as without it, and an unknown -m prints the VCF
+// header alone.  The lines are formatted on the device (sid_engine_set_format);
+// with --host-parse: sid_format_vcf.  Not listed by -h, whose text stays the
+// reference's.
 //
 // --min-depth N / --max-depth N (decimal, 0 .. 262140; given twice, the last
 // wins) write the header and only the records of the sites whose depth -- A +
@@ -302,6 +314,7 @@ int main(int argc, char** argv)
     std::atexit(free_regions);   // (the ways out that do not go through finish)
     const char* windows_out = nullptr;   // --windows-out
     int min_depth = 0, max_depth = 0;    // --min-depth, --max-depth
+    bool vcf = false;                    // --vcf
     static const struct option LONG[] = {{"devices", required_argument, nullptr, 1},
                                          {"threads", required_argument, nullptr, 2},
                                          {"stats", no_argument, nullptr, 3},
@@ -319,6 +332,7 @@ int main(int argc, char** argv)
                                          {"variants", no_argument, nullptr, 15},
                                          {"min-depth", required_argument, nullptr, 16},
                                          {"max-depth", required_argument, nullptr, 17},
+                                         {"vcf", no_argument, nullptr, 18},
                                          {nullptr, 0, nullptr, 0}};
     int flag;
     while ((flag = getopt_long(argc, argv, "E:Rhm:p:r:", LONG, nullptr)) != -1) {
@@ -433,6 +447,7 @@ int main(int argc, char** argv)
             (flag == 16 ? min_depth : max_depth) = v;   // (given twice: the last wins)
             break;
         }
+        case 18: vcf = true; break;
         default: std::exit(EXIT_FAILURE);
         }
     }
@@ -475,12 +490,25 @@ int main(int argc, char** argv)
     else if (opt.method == "bayes") method = SID_METHOD_BAYES;
     else if (opt.method == "likelihood_ratio") method = SID_METHOD_LIKELIHOOD_RATIO;
     else if (opt.method == "quality") method = SID_METHOD_QUALITY;   // call.cpp:291-372
+    // --vcf: the VCF header of the run in place of the CSV's line
+    std::string vcf_head;
+    auto vcf_header = [&] {
+        size_t need = 0;
+        (void)sid_vcf_header(&opt.o, nullptr, 0, &need);
+        vcf_head.assign(need, '\0');
+        CHECK(sid_vcf_header(&opt.o, &vcf_head[0], need, &need), "header");
+    };
     if (method < 0) {   // sid.cpp:92-102: unknown method -> header only
-        std::printf("chrom,pos,label,gt,hom_conf,het_conf,conf_type\n");
+        if (vcf) {
+            vcf_header();
+            std::fwrite(vcf_head.data(), 1, vcf_head.size(), stdout);
+        } else
+            std::printf("chrom,pos,label,gt,hom_conf,het_conf,conf_type\n");
         return 0;
     }
     opt.o.method = method;
     if (method == SID_METHOD_BAYES) opt.o.estimate_prior = 0;   // callBayes(in) ignores -R/-r/-p
+    if (vcf) vcf_header();
     const int T = opt.threads > 0 ? opt.threads
                                   : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
 
@@ -502,8 +530,10 @@ int main(int argc, char** argv)
         cfg.host_hold_bytes = opt.host_hold;
         cfg.host_threads = T;
         cfg.verbose = 1;
-        const int rc = sid_engine_create(&opt.o, &cfg, &eng);
-        return rc == SID_OK && depth_on ? sid_engine_set_depth(eng, min_depth, max_depth) : rc;
+        int rc = sid_engine_create(&opt.o, &cfg, &eng);
+        if (rc == SID_OK && depth_on) rc = sid_engine_set_depth(eng, min_depth, max_depth);
+        if (rc == SID_OK && vcf) rc = sid_engine_set_format(eng, SID_FORMAT_VCF);
+        return rc;
     };
     int dev_rc = SID_OK, eng_rc = SID_OK;
     double t0 = 0, tc = 0;
@@ -587,7 +617,7 @@ int main(int argc, char** argv)
         }
         return 0;
     };
-    const char* HEADER = "chrom,pos,label,gt,hom_conf,het_conf,conf_type\n";
+    const char* HEADER = vcf ? vcf_head.c_str() : "chrom,pos,label,gt,hom_conf,het_conf,conf_type\n";
     // --windows-out: the rows as CSV, after the records
     auto write_windows = [&](const sid_window* rows, size_t nrows) {
         size_t need = 0;
@@ -866,10 +896,12 @@ int main(int argc, char** argv)
                 if (b >= nblocks) return;
                 size_t lo = b * BLOCK, hi = std::min(n, lo + BLOCK);
                 size_t need = 0;
-                sid_format_csv(sites, lo, hi, h_code, h_hom, h_het, conf_type, nullptr, 0, &need);
+                if (vcf) sid_format_vcf(sites, lo, hi, h_code, h_hom, h_het, nullptr, 0, &need);
+                else sid_format_csv(sites, lo, hi, h_code, h_hom, h_het, conf_type, nullptr, 0, &need);
                 bufs[b].resize(need);
                 size_t len = 0;
-                int rc = sid_format_csv(sites, lo, hi, h_code, h_hom, h_het, conf_type, bufs[b].data(), need, &len);
+                int rc = vcf ? sid_format_vcf(sites, lo, hi, h_code, h_hom, h_het, bufs[b].data(), need, &len)
+                             : sid_format_csv(sites, lo, hi, h_code, h_hom, h_het, conf_type, bufs[b].data(), need, &len);
                 lens[b] = rc == SID_OK ? len : 0;
                 ready[b].store(1, std::memory_order_release);
             }

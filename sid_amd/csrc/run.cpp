@@ -1081,6 +1081,22 @@ extern "C" int sid_engine_set_depth(sid_engine* e, int min, int max)
     return SID_OK;
 }
 
+// The record format of every pipeline's context and workspace (sid.h
+// Conventions, "VCF"), under sid_engine_set_depth's state rules: -m local's
+// records are formatted during the ingest.  The workspaces keep the sites'
+// reference bytes from their next reservation on.
+extern "C" int sid_engine_set_format(sid_engine* e, int format)
+{
+    if (!e || (format != SID_FORMAT_CSV && format != SID_FORMAT_VCF)) return SID_EINVAL;
+    if (e->ingested) return SID_ESTATE;
+    for (auto& d : e->devs) {
+        const int rc = sid_set_format(d->ctx, format);
+        if (rc != SID_OK) return rc;
+        sid_chunk_bind_context(&d->ws, d->ctx);
+    }
+    return SID_OK;
+}
+
 extern "C" int sid_engine_placement(const sid_engine* e, int i, sid_placement* out)
 {
     if (!e || !out || i < 0 || i >= (int)e->devs.size()) return SID_EINVAL;
@@ -1927,7 +1943,10 @@ void compute(sid_engine* e, Dev& d, int pass)
             const bool quad = pre_tiled ? next_quad : d.tile_quad;
             if (!pre_tiled) rc = sid_chunk_reserve(&W, tbytes, sid_chunk_tile_slots(L.c0, L.c1, lg, quad));
             if (rc != SID_OK) return (void)fail(e, rc);
-            const uint64_t bound = sid_chunk_tile_bound(L.c0, L.c1, lg, quad);
+            // (VCF lines: their own bound, wherever a chunk's records are reserved -- the hold arena, the
+            // pooled buffers on the way to the host arena, the device sink's and pass 2's)
+            const uint64_t bound = W.vcf ? sid_chunk_vcf_bound(sid_chunk_tile_slots(L.c0, L.c1, lg, quad), L.c1 - L.c0)
+                                         : sid_chunk_tile_bound(L.c0, L.c1, lg, quad);
             // the records' buffer, taken as the two-pass path below takes it
             // (near the hold budget that path decides, with its exact bound)
             if (pass == 1 && d.hh && !d.hh_full) {
@@ -2188,7 +2207,7 @@ void compute(sid_engine* e, Dev& d, int pass)
                 d.prof_end(2, pe);
                 if (rc != SID_OK) return (void)fail(e, rc);
             }
-            const uint64_t bound = sid_chunk_fmt_bound(n, L.c1 - L.c0);
+            const uint64_t bound = W.vcf ? sid_chunk_vcf_bound(n, L.c1 - L.c0) : sid_chunk_fmt_bound(n, L.c1 - L.c0);
             if (n && pass == 1 && d.hh && !d.hh_full) {
                 out = d.pool.get(bound, &cap, d.s_comp);
                 via_host = out != nullptr;

@@ -145,6 +145,10 @@ struct sid_ctx {
     bool has_depth = false;
     bool cx_depth = false;
     bool cx_base = false;
+    // the record format (sid_set_format; SID_FORMAT_CSV / _VCF): with VCF the chunk formatters run the VCF
+    // stage (textpath.hip, sid_vcf_len_kernel / sid_vcf_put_kernel) behind the marking stages in place of the
+    // CSV length and put kernels, and the parse keeps every site's reference byte as for the variants
+    int format = 0;
     // the route's switch: a context in effect, or (cx_n = 0) a selection by label under sid_opts.window, whose
     // stage reads every site's label in front of the marking stage
     bool cx_on = false;
@@ -244,6 +248,8 @@ struct sid_chunk_ws {
     bool depth = false;
     bool cx_depth = false;
     uint32_t depth_min = 0, depth_max = 0;
+    // likewise the owner's record format (sid_ctx::format is SID_FORMAT_VCF): the reference bytes are kept
+    bool vcf = false;
     unsigned long long* cx_bits = nullptr;
     uint4* cx_sum = nullptr;
     uint4* cx_car = nullptr;
@@ -291,6 +297,8 @@ int sid_chunk_parse(sid_chunk_ws* W, const char* base, uint64_t c0, uint64_t c1,
 // is -m local fused with the call (counts in; sid_chunk_local_ok: options
 // the class tables cover)
 uint64_t sid_chunk_fmt_bound(uint64_t n, uint64_t text_bytes);
+// ... and of VCF lines (a workspace whose owner's format is SID_FORMAT_VCF)
+uint64_t sid_chunk_vcf_bound(uint64_t n, uint64_t text_bytes);
 int sid_chunk_fmt_len(sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n, const char* conf_type,
                       hipStream_t st);
 int sid_chunk_fmt_put(sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n, const char* conf_type, char* out,

@@ -42,6 +42,7 @@
 #include "../../include/sid.h"
 #include "context.h"
 #include "fmt.h"
+#include "vcf.h"
 #include "windows.h"
 #include "local_site.h"
 
@@ -4008,6 +4009,222 @@ static void launch_select_mark(SiteArgs<Off> A, bool var, bool dep, uint32_t dmi
     else sid_depth_mark_kernel<MODE, OPT, false, Off><<<(unsigned)nb, FTB, 0, st>>>(A);
 }
 
+// --------------------------------------------------------------------- VCF --
+// The records as VCF lines (sid_set_format, SID_FORMAT_VCF; sid.h Conventions,
+// vcf.h): one length kernel and one writer over the site view for every
+// layout, behind the window stage and every marking stage and in front of the
+// scan of the group sums, in place of the CSV length and put kernels of the
+// chunk.  A site has a VCF line exactly when the CSV kernels would print its
+// record: the markers the marking stages leave are honoured as those kernels
+// honour them (SID_CLS_SKIP, zeroed counts, SID_CODE_DROPPED / code_out, a
+// filtered tail of length 0), and a -m local group whose sum is 0 on entry
+// keeps it and has none of its words read (the marks leave such a group
+// unmarked, sv_mark).  -m local's sums otherwise come out of the parse: the
+// length kernel overwrites them.
+//
+// The genotype per mode as sv_variant reads it (the class word's bases with
+// the entry's het byte; a fix-up site's code; the Lynch tail's bytes 12-13; the
+// code's bits 0-3), the depth by sv_depth, REF from A.refb.  No %g per site:
+// the two confidence texts are the per-class record tails' ("hom_conf,
+// het_conf," from the entry's byte 8, the Lynch tail's byte 7), cut at their
+// commas; only the fix-up's sites and the code / confs layout format their
+// doubles (fmt.h), out of line.
+struct VcfRec {
+    Head h;
+    uint32_t cw[8];   // "hom_conf,het_conf," -- each text ended by its comma; 28 bytes at most
+    uint32_t hl, el;  // their lengths
+    uint32_t depth, refcls;
+    char x, y;        // the CSV record's gt bytes
+    int len;          // the line's bytes (0: no record)
+};
+
+// the texts of a site that has only its doubles; false: outside the formatter's range
+__device__ __noinline__ bool vcf_conf_text(double hm, double ht, uint32_t* cw)
+{
+    char t[32];
+    for (int k = 0; k < 32; ++k) t[k] = 0;
+    const int a = sid_g6_put(sid_g6_prep(hm), t);
+    if (a < 0) return false;
+    t[a] = ',';
+    const int b = sid_g6_put(sid_g6_prep(ht), t + a + 1);
+    if (b < 0) return false;
+    t[a + 1 + b] = ',';
+    for (int k = 0; k < 8; ++k)
+        cw[k] = (uint32_t)(uint8_t)t[4 * k] | ((uint32_t)(uint8_t)t[4 * k + 1] << 8) |
+                ((uint32_t)(uint8_t)t[4 * k + 2] << 16) | ((uint32_t)(uint8_t)t[4 * k + 3] << 24);
+    return true;
+}
+
+// bad: the formatter's range flag (lb[2]; the writer passes null: the length kernel has set it)
+template <int MODE, bool OPT, class Off>
+__device__ __forceinline__ void vcf_site(const SiteArgs<Off>& A, uint64_t i, Reader& R, unsigned long long* bad,
+                                         VcfRec& S)
+{
+    S.len = 0;
+    uint32_t w;
+    ulonglong2 te = make_ulonglong2(0, 0);
+    if (!sv_site<MODE, OPT, SV_FILTERED | SV_STORE>(A, i, &w, &te)) return;
+    bool text = false;   // S.cw holds the texts (else: from the site's doubles)
+    uint32_t c = 0;
+    const uint32_t ACGT = 0x54474341u;
+    if (MODE == REG_TILE || MODE == REG_DENSE) {
+        if (w != SID_CLS_MISS) {
+            const uint32_t k = w & 0xFFFFFu;
+            const uint4* e = (const uint4*)(k < SID_TAB_N ? A.str1 + (size_t)k * SID_STR_BYTES
+                                                          : A.str2 + (size_t)(k - SID_TAB_N) * SID_STR_BYTES);
+            const uint4 ea = e[0], eb = e[1];
+            const uint32_t L = ea.x & 0xFFu;
+            if (L == 0) return;   // (a class without a record)
+            if (L != 0xFFu) {
+                const uint32_t f = (w >> 28) & 3u, s = w >> 30;
+                const bool het = (ea.x >> 8) & 1u;
+                c = f | ((het ? s : f) << 2) | (het ? 0x80u : 0u);
+                S.cw[0] = ea.z, S.cw[1] = ea.w, S.cw[2] = eb.x, S.cw[3] = eb.y, S.cw[4] = eb.z, S.cw[5] = eb.w;
+                S.cw[6] = S.cw[7] = 0;
+                text = true;
+            }
+        }
+        if (!text) c = A.code[i];   // the fix-up's site
+        if (code_out(c, A.xm)) return;
+    } else if (MODE == REG_LYNCH) {
+        if (A.V.empty) return;
+        const uint32_t idx = lynch_class(A.counts[i], A.V);
+        if (idx == 0xFFFFFFFFu) return;
+        const uint4* e = (const uint4*)(A.V.lstr + (size_t)idx * SID_LSTR_BYTES);
+        const uint4 e0 = e[0], e1 = e[1], e2 = e[2];
+        if ((e0.x & 0xFFu) == 0) return;   // (a label the selection leaves out)
+        S.x = (char)(e0.w & 0xFFu), S.y = (char)((e0.w >> 8) & 0xFFu);   // "hom,XY,": the tail's bytes 4-5, the entry's 12-13
+        // the texts from the tail's byte 7, the entry's byte 15, on
+        const uint32_t q[9] = {e0.w, e1.x, e1.y, e1.z, e1.w, e2.x, e2.y, e2.z, e2.w};
+#pragma unroll
+        for (int k = 0; k < 8; ++k) S.cw[k] = (q[k] >> 24) | (q[k + 1] << 8);
+        text = true;
+    } else {
+        c = A.code[i];
+        if (code_out(c, A.xm)) return;
+    }
+    if (MODE != REG_LYNCH) {
+        S.x = (char)((ACGT >> (8u * (c & 3u))) & 0xFFu);
+        S.y = (char)((ACGT >> (8u * ((c >> 2) & 3u))) & 0xFFu);
+    }
+    if (!text && !vcf_conf_text(A.hom[i], A.het[i], S.cw)) {
+        if (bad) atomicExch(bad, 1ull);
+        return;
+    }
+    uint32_t hl = 32, e2 = 32;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+        const bool comma = ((S.cw[j >> 2] >> (8 * (j & 3))) & 0xFFu) == ',';
+        if (comma && hl == 32) hl = j;
+        else if (comma && e2 == 32) e2 = j;
+    }
+    if (e2 == 32) return;   // (never: both texts are 13 bytes at most)
+    S.hl = hl, S.el = e2 - hl - 1;
+    S.h = sv_head<MODE, OPT>(A, i, w, R, &te);
+    S.depth = sv_depth<MODE, OPT>(A, i, w);
+    S.refcls = A.refb[i] & 7u;
+    S.len = (int)S.h.clen + sid_i32_len(S.h.pos) + sid_vcf_mid_len(sid_vcf_call(S.refcls, S.x, S.y, S.depth), S.depth) +
+            (int)(S.hl + S.el);
+}
+
+// a line byte by byte through put(k, byte)
+template <class Put>
+__device__ __forceinline__ void vcf_record_bytes(Reader& R, const VcfRec& S, Put put)
+{
+    const Head& h = S.h;
+    uint32_t n = 0;
+    if (h.c8 || h.clen == 0) {
+        for (uint32_t k = 0; k < h.clen; ++k) put(n++, (uint32_t)(h.c8 >> (8 * k)) & 0xFFu);
+    } else {
+        for (uint32_t k = 0; k < h.clen; ++k) put(n++, R.at(h.cb + k));
+    }
+    put(n++, '\t');
+    const int pl = sid_i32_len(h.pos);
+    uint32_t u = h.pos < 0 ? 0u - (uint32_t)h.pos : (uint32_t)h.pos;
+    if (h.pos < 0) put(n, '-');
+    for (int k = pl - 1; k >= (h.pos < 0 ? 1 : 0); --k) {
+        put(n + k, '0' + u % 10u);
+        u /= 10u;
+    }
+    n += pl;
+    const sid_vcf_gt v = sid_vcf_call(S.refcls, S.x, S.y, S.depth);
+    n = sid_vcf_put_a(n, v, S.depth, put);
+    // hom_conf at n, ";HET=" behind it, het_conf behind that: text byte j > hl lands 4 bytes on
+#pragma unroll
+    for (int j = 0; j < 28; ++j) {
+        const uint32_t b = (S.cw[j >> 2] >> (8 * (j & 3))) & 0xFFu;
+        if ((uint32_t)j < S.hl) put(n + j, b);
+        else if ((uint32_t)j > S.hl && (uint32_t)j <= S.hl + S.el) put(n + j + 4, b);
+    }
+    (void)sid_vcf_put_b(n + S.hl, put);
+    (void)sid_vcf_put_c(n + S.hl + 5 + S.el, v, put);
+}
+
+template <int MODE, bool OPT, class Off>
+__global__ __launch_bounds__(FTB) void sid_vcf_len_kernel(const SiteArgs<Off> A, unsigned long long* bad)
+{
+    if ((MODE == REG_TILE || MODE == REG_DENSE) && A.bsum[blockIdx.x] == 0) return;   // (block-uniform)
+    const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
+    Reader R{A.text, A.len};
+    VcfRec S;
+    vcf_site<MODE, OPT>(A, i, R, bad, S);
+    const uint32_t tot = block_sum<FTB>((uint32_t)S.len);
+    if (threadIdx.x == 0) A.bsum[blockIdx.x] = tot;
+}
+
+// The writer: a group's lines assembled in LDS at their prefix offsets and
+// copied out with 16-B non-temporal stores (block_store), as the CSV writers
+// do.  The buffer holds a full group of lines whose chrom is 8 bytes or less
+// (512 x (SID_VCF_REC_MAX + 8) = 44 032 B; a typical 30x group is about 28 KB);
+// a group past it -- long chrom names -- goes out window by window, each line
+// putting the bytes that fall into the window.  A group whose sum is 0 costs
+// one block-uniform load, so the sparse selections need no second writer.
+// boff: the groups' offsets, less `sub` (a piece of a resident shard); lb:
+// lb[4] = the chunk's parse error key (null: none to copy)
+constexpr uint32_t VCF_LDS = 44 * 1024;
+static_assert(VCF_LDS >= FTB * (SID_VCF_REC_MAX + 8) && VCF_LDS % 16 == 0, "a full group of short-chrom lines");
+template <int MODE, bool OPT, class Off>
+__global__ __launch_bounds__(FTB) void sid_vcf_put_kernel(const SiteArgs<Off> A, const uint64_t* __restrict__ boff,
+                                                          uint64_t sub, const uint64_t* state, unsigned long long* lb,
+                                                          char* __restrict__ out)
+{
+    __shared__ __attribute__((aligned(16))) char buf[VCF_LDS + 32];
+    if (lb && blockIdx.x == 0 && threadIdx.x == 0) lb[4] = state[4];
+    if (A.bsum[blockIdx.x] == 0) return;   // (block-uniform)
+    const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
+    Reader R{A.text, A.len};
+    VcfRec S;
+    vcf_site<MODE, OPT>(A, i, R, nullptr, S);
+    uint32_t tot;
+    const uint32_t my = block_exscan_once<FTB>((uint32_t)S.len, &tot);
+    char* const dst = out + (boff[blockIdx.x] - sub);
+    for (uint32_t base = 0; base < tot; base += VCF_LDS) {   // (block-uniform; one round but for long chroms)
+        if (base) __syncthreads();   // the window before is copied out
+        if (S.len && my < base + VCF_LDS && my + (uint32_t)S.len > base)
+            vcf_record_bytes(R, S, [&](uint32_t k, uint32_t ch) {
+                const uint32_t o = my + k - base;   // (below the window: wraps past it)
+                if (o < VCF_LDS) buf[o] = (char)ch;
+            });
+        __syncthreads();
+        block_store(buf, tot - base < VCF_LDS ? tot - base : VCF_LDS, dst + base);
+    }
+}
+
+template <int MODE, bool OPT, class Off>
+static void launch_vcf_len(const SiteArgs<Off>& A, unsigned long long* bad, hipStream_t st)
+{
+    const uint64_t nb = (A.s1 - A.s0 + FTB - 1) / FTB;
+    if (nb) sid_vcf_len_kernel<MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(A, bad);
+}
+
+template <int MODE, bool OPT, class Off>
+static void launch_vcf_put(const SiteArgs<Off>& A, const uint64_t* boff, uint64_t sub, const uint64_t* state,
+                           unsigned long long* lb, char* out, hipStream_t st)
+{
+    const uint64_t nb = (A.s1 - A.s0 + FTB - 1) / FTB;
+    if (nb) sid_vcf_put_kernel<MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(A, boff, sub, state, lb, out);
+}
+
 // ---------------------------------------------------------------- context --
 // The context (sid_opts.context = N with a selection; sid_ctx::cx_n): every
 // selected record with the N records before and after it, in record rank --
@@ -5149,7 +5366,10 @@ extern "C" int sid_dtext_format(sid_ctx* ctx, const sid_dtext* T, size_t begin, 
     // ms with the same D2H rate; 64 Ki-site pieces D2H slower
     // (round-1 measurement)
     constexpr size_t PB = 1024;
-    const size_t nb = (n + TB - 1) / TB;
+    // (VCF lines, sid_set_format: the VCF stage's 512-site groups in place of the CSV kernels' blocks)
+    const bool vcf = ctx->format == SID_FORMAT_VCF;
+    const size_t GB = vcf ? (size_t)FTB : (size_t)TB;
+    const size_t nb = (n + GB - 1) / GB;
     uint32_t* d_bsum = nullptr;
     uint64_t* d_boff = nullptr;
     uint64_t* d_base = nullptr;
@@ -5191,14 +5411,14 @@ extern "C" int sid_dtext_format(sid_ctx* ctx, const sid_dtext* T, size_t begin, 
     hipError_t stage_err = hipSuccess;
     std::thread stager([&, dev = T->device] {
         (void)hipSetDevice(dev);
-        stage_err = stage(std::min<size_t>(n, PB * TB) * 64 + 64);
+        stage_err = stage(std::min<size_t>(n, PB * GB) * 64 + 64);
     });
     // record lengths of every site and their block offsets: one pass, one sync
     std::vector<uint64_t> boff(nb + 1, 0);
     hip(hipMalloc(&d_bsum, ((std::max<size_t>(nb, 1) * 4 + 7) & ~(size_t)7) + scan_ws_bytes(nb)));
     hip(hipMalloc(&d_boff, (nb + 1) * 8));
     hip(hipMalloc(&d_base, 8));
-    hip(hipMalloc(&d_bad, 4));
+    hip(hipMalloc(&d_bad, 8));
     // a region set: the sites outside get the "no record" bit in a copy of the
     // codes (the caller's array stays as it is; indexed by site like it, so `end`
     // bytes of which [begin, end) are used)
@@ -5213,7 +5433,7 @@ extern "C" int sid_dtext_format(sid_ctx* ctx, const sid_dtext* T, size_t begin, 
     }
     // the variants: the shard's reference bytes (made here when its parse had another context), and the
     // records that are none dropped likewise, behind the region stage
-    if (rc == SID_OK && nb && (ctx->has_variants || ctx->cx_variants) && !T->d_refb) {
+    if (rc == SID_OK && nb && (ctx->has_variants || ctx->cx_variants || vcf) && !T->d_refb) {
         const int r2 = dtext_refs(const_cast<sid_dtext*>(T), st);
         if (r2 != SID_OK) rc = r2;
     }
@@ -5247,10 +5467,15 @@ extern "C" int sid_dtext_format(sid_ctx* ctx, const sid_dtext* T, size_t begin, 
         }
     }
     if (rc == SID_OK && nb) {
-        hip(hipMemsetAsync(d_bad, 0, 4, st));
+        hip(hipMemsetAsync(d_bad, 0, 8, st));
         hip(hipMemsetAsync(d_base, 0, 8, st));
-        sid_fmt_len_kernel<<<(unsigned)nb, TB, 0, st>>>(T->d_text, T->len, T->d_starts, T->d_hdr, begin, end, d_code, d_hom,
-                                                        d_het, ct, d_bsum, d_bad, sel_word(ctx->opts.select));
+        if (vcf) {
+            SiteArgs<uint64_t> A = dtext_view(T, begin, end, const_cast<uint8_t*>(d_code));
+            A.hom = d_hom, A.het = d_het, A.bsum = d_bsum, A.xm = sel_word(ctx->opts.select);
+            launch_vcf_len<REG_CODE, false>(A, (unsigned long long*)d_bad, st);
+        } else
+            sid_fmt_len_kernel<<<(unsigned)nb, TB, 0, st>>>(T->d_text, T->len, T->d_starts, T->d_hdr, begin, end, d_code,
+                                                            d_hom, d_het, ct, d_bsum, d_bad, sel_word(ctx->opts.select));
         launch_scan(d_bsum, nb, d_boff, d_base, nullptr,
                     (uint64_t*)((char*)d_bsum + ((std::max<size_t>(nb, 1) * 4 + 7) & ~(size_t)7)), st);
         hip(hipGetLastError());
@@ -5282,13 +5507,18 @@ extern "C" int sid_dtext_format(sid_ctx* ctx, const sid_dtext* T, size_t begin, 
     int k = 0;
     for (size_t b0 = 0; b0 < nb && rc == SID_OK; b0 += PB, k ^= 1) {
         const size_t b1 = std::min(nb, b0 + PB);
-        const size_t s0 = begin + b0 * TB, s1 = std::min(end, begin + b1 * TB);
+        const size_t s0 = begin + b0 * GB, s1 = std::min(end, begin + b1 * GB);
         const uint64_t bytes = boff[b1] - boff[b0];
         flush(k);   // buffer k is about to be reused
         if (rc != SID_OK) break;
-        sid_fmt_write_kernel<<<(unsigned)(b1 - b0), TB, 0, st>>>(T->d_text, T->len, T->d_starts, T->d_hdr, s0, s1, d_code, d_hom,
-                                                                 d_het, ct, d_boff + b0, boff[b0], d_out[k],
-                                                                 sel_word(ctx->opts.select));
+        if (vcf) {
+            SiteArgs<uint64_t> A = dtext_view(T, s0, s1, const_cast<uint8_t*>(d_code));
+            A.hom = d_hom, A.het = d_het, A.bsum = d_bsum + b0, A.xm = sel_word(ctx->opts.select);
+            launch_vcf_put<REG_CODE, false>(A, d_boff + b0, boff[b0], nullptr, nullptr, d_out[k], st);
+        } else
+            sid_fmt_write_kernel<<<(unsigned)(b1 - b0), TB, 0, st>>>(T->d_text, T->len, T->d_starts, T->d_hdr, s0, s1, d_code,
+                                                                     d_hom, d_het, ct, d_boff + b0, boff[b0], d_out[k],
+                                                                     sel_word(ctx->opts.select));
         if (!hip(hipGetLastError())) break;
         hip(hipEventRecord(written, st));
         hip(hipStreamWaitEvent(cs, written, 0));
@@ -5632,7 +5862,7 @@ int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites)
         WCHECK(hipMalloc(&W->starts, m * sizeof(sid_off_t)));
         WCHECK(hipMalloc(&W->counts, m * 8));
         WCHECK(hipMalloc(&W->cls, m * 4));
-        if (W->variants || W->cx_variants) WCHECK(hipMalloc(&W->refb, m));   // the sites' reference bytes
+        if (W->variants || W->cx_variants || W->vcf) WCHECK(hipMalloc(&W->refb, m));   // the sites' reference bytes
         WCHECK(hipMalloc(&W->hdr, m * 16));
         WCHECK(hipMalloc(&W->twv, (m / 32 + 1) * 16));   // the tile parse's wave entries (tile_nwv)
         WCHECK(hipMalloc(&W->fb, m * 12));   // three site lists (sid_chunk_ws::fb)
@@ -5657,6 +5887,7 @@ int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites)
         }
         W->site_cap = m;
     }
+    if (W->vcf && !W->refb && W->site_cap) WCHECK(hipMalloc(&W->refb, W->site_cap));   // the format set behind the growth
     if (W->cx_on && !W->cx_bits && W->site_cap) {   // the route switched on behind the growth (sid_set_depth)
         const uint64_t ng = (W->site_cap + FTB - 1) / FTB + 1;
         WCHECK(hipMalloc(&W->cx_bits, ng * (FTB / 64) * 16));
@@ -5687,7 +5918,9 @@ void sid_chunk_release(sid_chunk_ws* W)
     const bool variants = W->variants, cx_variants = W->cx_variants;
     const bool depth = W->depth, cx_depth = W->cx_depth;
     const uint32_t depth_min = W->depth_min, depth_max = W->depth_max;
+    const bool vcf = W->vcf;
     *W = sid_chunk_ws{};
+    W->vcf = vcf;
     W->depth = depth, W->cx_depth = cx_depth, W->depth_min = depth_min, W->depth_max = depth_max;
     W->window = window;
     W->variants = variants, W->cx_variants = cx_variants;
@@ -5711,6 +5944,7 @@ void sid_chunk_bind_context(sid_chunk_ws* W, const sid_ctx* ctx)
     W->depth = ctx->has_depth;
     W->cx_depth = ctx->cx_depth;
     W->depth_min = (uint32_t)ctx->depth_min, W->depth_max = (uint32_t)ctx->depth_max;
+    W->vcf = ctx->format == SID_FORMAT_VCF;
 }
 
 // blocks of the strided index kernels (count kernel, index stage per 50M
@@ -5807,6 +6041,14 @@ static int chunk_ctype(const char* conf_type, CType* ct)
 // their lines
 uint64_t sid_chunk_fmt_bound(uint64_t n, uint64_t text_bytes) { return 64 * n + text_bytes + 64; }
 
+// a VCF line is its chrom plus at most SID_VCF_REC_MAX = 78 bytes (vcf.h: 32
+// fixed bytes -- nine tabs, the three ".", REF, "DP=", ";HOM=", ";HET=", "GT",
+// the three bytes of the genotype, the newline -- an int position of <= 11
+// characters, ALT "X,Y", a depth of <= 6 digits (4 x 65535) and two %g fields
+// of <= 13), rounded up to 80; the chroms are bytes of their lines
+uint64_t sid_chunk_vcf_bound(uint64_t n, uint64_t text_bytes) { return 80 * n + text_bytes + 64; }
+static_assert(SID_VCF_REC_MAX <= 80, "sid_chunk_vcf_bound");
+
 // the formatter's steps 1-2 (record bytes per block, their offsets); lb[1]
 // = the chunk's bytes afterwards
 static int fmt_scan(sid_chunk_ws* W, uint64_t nb, hipStream_t st)
@@ -5823,7 +6065,7 @@ int sid_chunk_fmt_len(sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n
     CType ct;
     if (chunk_ctype(conf_type, &ct)) return SID_EINVAL;
     if (n > W->site_cap) return SID_EINVAL;
-    if ((W->variants || W->cx_variants) && n && !W->refb) return SID_ESTATE;
+    if ((W->variants || W->cx_variants || W->vcf) && n && !W->refb) return SID_ESTATE;
     WCHECK(hipMemsetAsync(W->lb, 0, 8 * 8, st));
     const uint64_t nb = (n + FTB - 1) / FTB;
     const SiteArgs<sid_off_t> S = dense_view(W, base, c1, n);
@@ -5843,8 +6085,13 @@ int sid_chunk_fmt_len(sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n
     }
     // the context: the records outside the dilated selection, dropped likewise
     if (W->cx_on) launch_context_mark<REG_CODE, false>(S, W, st);
-    if (nb) sid_fmt_blen_kernel<<<(unsigned)nb, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->code, W->hom,
-                                                              W->het, ct, W->bsum, W->lb, sel_word(W->select));
+    if (nb && W->vcf) {   // the VCF lines' lengths instead
+        SiteArgs<sid_off_t> A = S;
+        A.xm = sel_word(W->select);
+        launch_vcf_len<REG_CODE, false>(A, W->lb + 2, st);
+    } else if (nb)
+        sid_fmt_blen_kernel<<<(unsigned)nb, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->code, W->hom,
+                                                          W->het, ct, W->bsum, W->lb, sel_word(W->select));
     WCHECK(hipGetLastError());
     return fmt_scan(W, nb, st);
 }
@@ -5857,8 +6104,13 @@ int sid_chunk_fmt_put(sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n
     const uint64_t nb = (n + FTB - 1) / FTB;
     if (nb == 0) return hipMemcpyAsync(W->lb + 4, W->state + 4, 8, hipMemcpyDeviceToDevice, st) == hipSuccess
                             ? SID_OK : SID_EHIP;
-    sid_fmt_put_kernel<<<(unsigned)nb, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->code, W->hom, W->het, ct,
-                                                    W->boff, W->state, W->lb, out, sel_word(W->select));
+    if (W->vcf) {
+        SiteArgs<sid_off_t> A = dense_view(W, base, c1, n);
+        A.xm = sel_word(W->select);
+        launch_vcf_put<REG_CODE, false>(A, W->boff, 0, W->state, W->lb, out, st);
+    } else
+        sid_fmt_put_kernel<<<(unsigned)nb, FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->code, W->hom, W->het, ct,
+                                                        W->boff, W->state, W->lb, out, sel_word(W->select));
     if (W->cx_on) launch_context_edge(W, out, st);
     WCHECK(hipGetLastError());
     return SID_OK;
@@ -5884,7 +6136,8 @@ int sid_chunk_local_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     CType ct;
     if (local_ctype(ctx, conf_type, &ct)) return SID_EINVAL;
     if (n > W->site_cap || n >= (1ull << 32)) return SID_EINVAL;
-    if ((ctx->has_variants || ctx->cx_variants) && n && !W->refb) return SID_ESTATE;   // (a workspace not bound)
+    const bool vcf = ctx->format == SID_FORMAT_VCF;
+    if ((ctx->has_variants || ctx->cx_variants || vcf) && n && !W->refb) return SID_ESTATE;   // (a workspace not bound)
     // the fix-up's sites in the third list of W->fb
     uint32_t* miss = W->fb + 2 * W->site_cap;
     const uint64_t nb = (n + FTB - 1) / FTB;
@@ -5930,6 +6183,14 @@ int sid_chunk_local_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
         else launch_context_mark<REG_DENSE, true>(S, W, st);
         if (nb) W->cls_ready = true;
     }
+    if (nb && vcf) {   // the VCF lines' lengths over the groups' sums (without class words: written here)
+        SiteArgs<sid_off_t> A = S;
+        A.xm = sel_word(ctx->opts.select);
+        if (local_sel(ctx)) A.len1 = ctx->ws.len1f, A.len2 = ctx->ws.len2f;   // (as the length pass)
+        if (W->cls_ready) launch_vcf_len<REG_DENSE, false>(A, W->lb + 2, st);
+        else launch_vcf_len<REG_DENSE, true>(A, W->lb + 2, st);
+        W->cls_ready = true;
+    }
     W->lens_ready = false;
     WCHECK(hipGetLastError());
     return fmt_scan(W, nb, st);
@@ -5942,6 +6203,26 @@ int sid_chunk_local_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     if (local_ctype(ctx, conf_type, &ct)) return SID_EINVAL;
     const uint64_t nb = (n + FTB - 1) / FTB;
     const bool sel = local_sel(ctx);
+    if (ctx->format == SID_FORMAT_VCF) {   // the VCF writer, for either layout and every selection
+        const uint64_t g = W->slot_cap ? (W->slots + FTB - 1) / FTB : nb;
+        if (g == 0) return hipMemcpyAsync(W->lb + 4, W->state + 4, 8, hipMemcpyDeviceToDevice, st) == hipSuccess
+                               ? SID_OK : SID_EHIP;
+        if (W->slot_cap) {
+            if (W->slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (slot_tile's exact range)
+            SiteArgs<sid_off_t> A = tile_view(W, base, c1, W->slot_cap, ctx, ct);
+            A.xm = sel_word(ctx->opts.select);
+            if (W->tile_quad) launch_vcf_put<REG_TILE, false>(A, W->boff, 0, W->state, W->lb, out, st);
+            else launch_vcf_put<REG_TILE, true>(A, W->boff, 0, W->state, W->lb, out, st);
+        } else {
+            if (!W->cls_ready) return SID_ESTATE;
+            SiteArgs<sid_off_t> A = dense_view(W, base, c1, n, ctx, ct);
+            A.xm = sel_word(ctx->opts.select);
+            launch_vcf_put<REG_DENSE, false>(A, W->boff, 0, W->state, W->lb, out, st);
+        }
+        if (ctx->cx_on) launch_context_edge(W, out, st);
+        WCHECK(hipGetLastError());
+        return SID_OK;
+    }
     if (W->slot_cap) {   // the tile parse's slots
         const uint64_t nbs = (W->slots + FTB - 1) / FTB;
         if (nbs == 0) return hipMemcpyAsync(W->lb + 4, W->state + 4, 8, hipMemcpyDeviceToDevice, st) == hipSuccess
@@ -6091,8 +6372,9 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
     const uint64_t slots = ntp * cap;
     if (slots > W->site_cap || ntp > W->tile_cap || slots >= (1ull << 32)) return SID_EINVAL;
     if (ntp * tile_nwv(cap) > W->site_cap / 32 + 1) return SID_EINVAL;   // (never: cap >= 64)
-    if ((ctx->has_variants || ctx->cx_variants) && slots && !W->refb) return SID_ESTATE;   // (a workspace not bound)
-    if ((ctx->has_regions || ctx->has_variants || ctx->has_depth || ctx->cx_on || W->window) && slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (the marking kernels' slot_tile: its exact range, as the writer's)
+    const bool vcf = ctx->format == SID_FORMAT_VCF;
+    if ((ctx->has_variants || ctx->cx_variants || vcf) && slots && !W->refb) return SID_ESTATE;   // (a workspace not bound)
+    if ((vcf || ctx->has_regions || ctx->has_variants || ctx->has_depth || ctx->cx_on || W->window) && slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (the marking kernels' slot_tile: its exact range, as the writer's)
     W->lens_ready = false;
     W->cls_ready = false;
     W->slot_cap = cap;
@@ -6149,6 +6431,12 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
     if (ctx->cx_on) {   // the context: the slots outside the dilated selection likewise
         if (quad) launch_context_mark<REG_TILE, false>(S, W, st);
         else launch_context_mark<REG_TILE, true>(S, W, st);
+    }
+    if (vcf) {   // the VCF lines' lengths over the sums the parse and the marks left
+        SiteArgs<sid_off_t> A = S;
+        A.xm = sel_word(ctx->opts.select);
+        if (quad) launch_vcf_len<REG_TILE, false>(A, W->lb + 2, st);
+        else launch_vcf_len<REG_TILE, true>(A, W->lb + 2, st);
     }
     WCHECK(hipGetLastError());
     W->cls_ready = true;
@@ -6211,7 +6499,8 @@ int sid_chunk_lynch_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     sid_lynch_fmt V;
     if (sid_lynch_fmt_view(ctx, &V) != SID_OK) return SID_ESTATE;
     if (n > W->site_cap) return SID_EINVAL;
-    if ((ctx->has_variants || ctx->cx_variants) && n && !W->refb) return SID_ESTATE;   // (a workspace not bound)
+    const bool vcf = ctx->format == SID_FORMAT_VCF;
+    if ((ctx->has_variants || ctx->cx_variants || vcf) && n && !W->refb) return SID_ESTATE;   // (a workspace not bound)
     WCHECK(hipMemsetAsync(W->lb, 0, 8 * 8, st));   // [1] bytes, [2] range flag
     const uint64_t nb = (n + FTB - 1) / FTB;
     SiteArgs<sid_off_t> S = dense_view(W, base, c1, n);
@@ -6237,8 +6526,10 @@ int sid_chunk_lynch_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
         if (ctx->has_variants || ctx->has_depth)
             launch_select_mark<REG_LYNCH, false>(S, ctx->has_variants, ctx->has_depth, (uint32_t)ctx->depth_min,
                                                  (uint32_t)ctx->depth_max, st);
-        (ctx->opts.select == SID_SELECT_HET ? sid_lynch_len_kernel<true> : sid_lynch_len_kernel<false>)
-            <<<(unsigned)((nb + LPB - 1) / LPB), FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->counts, V, W->bsum);
+        if (vcf) launch_vcf_len<REG_LYNCH, false>(S, W->lb + 2, st);   // the VCF lines' lengths instead
+        else
+            (ctx->opts.select == SID_SELECT_HET ? sid_lynch_len_kernel<true> : sid_lynch_len_kernel<false>)
+                <<<(unsigned)((nb + LPB - 1) / LPB), FTB, 0, st>>>(base, c1, W->starts, W->hdr, n, W->counts, V, W->bsum);
     }
     WCHECK(hipGetLastError());
     return fmt_scan(W, nb, st);
@@ -6255,7 +6546,11 @@ int sid_chunk_lynch_put(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     // --only het keeps about a site in a thousand: the sparse writer; hom
     // keeps nearly all, and goes through the LDS assembly with the others'
     // length 0 honoured
-    if (ctx->opts.select == SID_SELECT_HET && !V.empty)
+    if (ctx->format == SID_FORMAT_VCF) {
+        SiteArgs<sid_off_t> A = dense_view(W, base, c1, n);
+        A.V = V;
+        launch_vcf_put<REG_LYNCH, false>(A, W->boff, 0, W->state, W->lb, out, st);
+    } else if (ctx->opts.select == SID_SELECT_HET && !V.empty)
         sid_lynch_put_sparse_kernel<<<(unsigned)((nb + SPB - 1) / SPB), FTB, 0, st>>>(
             base, c1, W->starts, W->hdr, n, W->counts, V, W->bsum, W->boff, W->state, W->lb, out);
     else
