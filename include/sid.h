@@ -150,6 +150,26 @@
  *     tile shape.  The format is no field of sid_opts (whose layout stands).
  *     Host formatting: sid_format_vcf in place of sid_format_csv, after the
  *     same marks.
+ *   - Depth histogram (sid_engine_set_depth_hist; --depth-hist FILE): a summary
+ *     of the run along the depth axis, beside the records.  The sites are the
+ *     non-empty lines; a site's depth is the one the depth bounds use, A + C +
+ *     G + T of its profile_t as the parser stores it (u16 counts that wrap),
+ *     0 .. 262140.  There is one row for every depth that at least one site
+ *     has, in ascending depth order: depth; sites; records, the sites that
+ *     print a record in the unselected output; het and hom, those records by
+ *     label (records = het + hom) -- the definitions of the window rows'
+ *     columns, so for any W each of the four columns summed over the depth
+ *     rows equals the same column summed over the window rows, and sites sums
+ *     to sid_run_stats.sites.  Like the window rows, the calls and the
+ *     estimate the rows see every site: the selections by label, region,
+ *     variant and depth, the context and the record format never change them,
+ *     and the option changes neither the records, bytes_out, stderr nor the
+ *     exit status.  The rows do not depend on chunk size, device count, lanes,
+ *     budgets, source kind, sink mode or tile shape; a chunk counts once
+ *     however often it is parsed.  A run that fails has no rows; an engine
+ *     that is reused starts every run from zero.  The switch is no field of
+ *     sid_opts (whose layout stands).  Host path: sid_depth_hist_host, on the
+ *     codes before any mark.
  *   - Counts layout: profile_t (pileup.hpp:7) = 4 x uint16 {A,C,G,T} per site,
  *     array of structures, 8 bytes per site.
  */
@@ -313,6 +333,33 @@ int sid_windows_host(const struct sid_sites* s, size_t begin, size_t end, const 
                      int window, sid_window** rows, size_t* n);
 void sid_windows_free(sid_window* rows);
 int sid_windows_format(const sid_window* rows, size_t n, int with_header, char* buf, size_t cap, size_t* len);
+
+/* ------------------------------------------------------- depth histogram --
+ * The rows of the depth histogram (Conventions), in ascending depth order.
+ *
+ * sid_depth_hist_host: the rows of sites [begin, end) on the host path (the
+ *   analogue of sid_windows_host): code_all are the codes before any selection
+ *   marked them.  *rows is freed with sid_depth_hist_free.  SID_EINVAL for a
+ *   range outside the sites or a NULL pointer.
+ * sid_depth_hist_format: "depth,sites,records,het,hom\n" (with_header) and a
+ *   line per row, the integers in decimal.  Returns bytes written in *len, or
+ *   SID_ENOMEM if cap is too small (then *len is a sufficient size), as
+ *   sid_windows_format.
+ * sid_depth_hist_merge: the sum of two row sets (ranks that took site ranges
+ *   add their rows with it); *rows is freed with sid_depth_hist_free.
+ *   SID_EINVAL for a NULL pointer or input that is not strictly ascending in
+ *   depth. */
+typedef struct {
+    uint64_t sites, records, het, hom;
+    uint32_t depth;
+    uint32_t pad;
+} sid_depth_row;
+int sid_depth_hist_host(const struct sid_sites* s, size_t begin, size_t end, const uint8_t* code_all /* host */,
+                        sid_depth_row** rows, size_t* n);
+void sid_depth_hist_free(sid_depth_row* rows);
+int sid_depth_hist_format(const sid_depth_row* rows, size_t n, int with_header, char* buf, size_t cap, size_t* len);
+int sid_depth_hist_merge(const sid_depth_row* a, size_t na, const sid_depth_row* b, size_t nb, sid_depth_row** rows,
+                         size_t* n);
 
 /* ------------------------------------------------------------- contexts -- */
 typedef struct sid_ctx sid_ctx;
@@ -505,6 +552,12 @@ int sid_dtext_free(sid_dtext* t);
  * *rows is freed with sid_windows_free.  Synchronises. */
 int sid_dtext_windows(sid_ctx* ctx, const sid_dtext* t, size_t begin, size_t end, const uint8_t* code /* device */,
                       sid_window** rows, size_t* n, void* stream);
+/* The depth histogram (Conventions) of sites [begin, end) of a resident shard
+ * with the given device codes: the engine's stage over one range.  It needs no
+ * switch on the context.  *rows is freed with sid_depth_hist_free.
+ * Synchronises. */
+int sid_dtext_depth_hist(sid_ctx* ctx, const sid_dtext* t, size_t begin, size_t end, const uint8_t* code /* device */,
+                         sid_depth_row** rows, size_t* n, void* stream);
 /* -m quality (call.cpp:291-372) over a shard parsed by a context whose method
  * is SID_METHOD_QUALITY (7 fields per line): the read bases and both quality
  * fields are read from the resident text.  snp_prior / significance_level
@@ -674,6 +727,13 @@ int sid_engine_set_depth(sid_engine* e, int min, int max);
  * run until it is set again; the caller passes sid_vcf_header's text as the
  * emit's header.  bytes_out counts the VCF lines' bytes. */
 int sid_engine_set_format(sid_engine* e, int format);
+/* The depth histogram (Conventions) of every pipeline, under the same state
+ * rules: SID_EINVAL for a value other than 0 and 1, SID_ESTATE between a
+ * successful sid_engine_ingest and its emit.  The setting holds for every
+ * later run until it is set again.  Off (the default): no kernel of the stage
+ * is launched and no buffer of it allocated.  On, a selection by label goes the
+ * context's route with N = 0, as under sid_opts.window: the same records. */
+int sid_engine_set_depth_hist(sid_engine* e, int on);
 /* Host placement of pipeline i (a multi-GPU node: each GPU's uploader,
  * compute and drain threads run on the CPUs local to its PCI device, and its
  * pinned host buffers are allocated from them, so their pages sit on the
@@ -738,6 +798,13 @@ int sid_engine_records(sid_engine* e, uint64_t chunk, const char** bytes, uint64
  * the engine and valid until the next ingest or source.  SID_ESTATE before
  * that, after a failed run, or without the option. */
 int sid_engine_windows(sid_engine* e, const sid_window** rows, size_t* n);
+/* The depth histogram of the run (sid_engine_set_depth_hist), after a
+ * successful sid_engine_emit in every device_sink mode: the rows in ascending
+ * depth order, owned by the engine and valid until the next ingest or source.
+ * SID_ESTATE before that, after a failed run, or with the option off.
+ * sid_run_stats has no field for the number of rows (its layout stands, as
+ * sid_opts'): *n is that number. */
+int sid_engine_depth_hist(sid_engine* e, const sid_depth_row** rows, size_t* n);
 /* Measurement: with profiling on, every stage of every chunk is bracketed by
  * a pair of HIP events on its device's compute stream; _read sums the stages'
  * device time over the chunks and devices since the last read (synchronises). */

@@ -91,12 +91,21 @@ class RunStats(C.Structure):
                 ("chunks_tiled", C.c_uint64), ("tile_overflows", C.c_uint64),
                 ("tile_overflows_queued", C.c_uint64), ("bgzf_bytes", C.c_uint64), ("bgzf_blocks", C.c_uint64),
                 ("window_rows", C.c_uint64)]
+    # the rows of the depth histogram (Engine(depth_hist=True)): no field of sid_run_stats, whose layout
+    # stands -- Engine.emit sets it on the instance from sid_engine_depth_hist's count
+    depth_rows = 0
 
 
 class Window(C.Structure):
     """sid_window: one row of the windowed summary (chrom is not NUL-terminated)."""
     _fields_ = [("chrom", C.c_void_p), ("chrom_len", C.c_uint32), ("start", C.c_int64), ("end", C.c_int64),
                 ("sites", C.c_uint64), ("records", C.c_uint64), ("het", C.c_uint64), ("hom", C.c_uint64)]
+
+
+class DepthRow(C.Structure):
+    """sid_depth_row: one row of the depth histogram."""
+    _fields_ = [("sites", C.c_uint64), ("records", C.c_uint64), ("het", C.c_uint64), ("hom", C.c_uint64),
+                ("depth", C.c_uint32), ("pad", C.c_uint32)]
 
 
 class Placement(C.Structure):
@@ -127,6 +136,14 @@ SIGNATURES = [
     ("sid_windows_format", _I, [C.POINTER(Window), _SZ, _I, _P, _SZ, C.POINTER(C.c_size_t)]),
     ("sid_dtext_windows", _I, [_P, _P, _SZ, _SZ, _P, C.POINTER(C.POINTER(Window)), C.POINTER(C.c_size_t), _P]),
     ("sid_engine_windows", _I, [_P, C.POINTER(C.POINTER(Window)), C.POINTER(C.c_size_t)]),
+    ("sid_depth_hist_host", _I, [_P, _SZ, _SZ, _P, C.POINTER(C.POINTER(DepthRow)), C.POINTER(C.c_size_t)]),
+    ("sid_depth_hist_free", None, [C.POINTER(DepthRow)]),
+    ("sid_depth_hist_format", _I, [C.POINTER(DepthRow), _SZ, _I, _P, _SZ, C.POINTER(C.c_size_t)]),
+    ("sid_depth_hist_merge", _I, [C.POINTER(DepthRow), _SZ, C.POINTER(DepthRow), _SZ,
+                                  C.POINTER(C.POINTER(DepthRow)), C.POINTER(C.c_size_t)]),
+    ("sid_dtext_depth_hist", _I, [_P, _P, _SZ, _SZ, _P, C.POINTER(C.POINTER(DepthRow)), C.POINTER(C.c_size_t), _P]),
+    ("sid_engine_set_depth_hist", _I, [_P, _I]),
+    ("sid_engine_depth_hist", _I, [_P, C.POINTER(C.POINTER(DepthRow)), C.POINTER(C.c_size_t)]),
     ("sid_regions_from_bed", _I, [C.c_char_p, _SZ, C.POINTER(_P), C.POINTER(C.c_uint64)]),
     ("sid_regions_from_intervals", _I, [C.POINTER(C.c_char_p), _P, _P, _SZ, C.POINTER(_P)]),
     ("sid_regions_intervals", _SZ, [_P]),
@@ -406,6 +423,75 @@ def dtext_windows(ctx: "Context", dtext: "DText", code_ptr, begin: int = 0, end:
         return _window_rows(rows, n.value)
     finally:
         lib().sid_windows_free(rows)
+
+
+def _depth_rows(rows, n: int) -> list:
+    """sid_depth_row rows as tuples (depth, sites, records, het, hom)."""
+    return [(rows[k].depth, rows[k].sites, rows[k].records, rows[k].het, rows[k].hom) for k in range(n)]
+
+
+def _depth_array(rows):
+    rows = list(rows)
+    arr = (DepthRow * max(len(rows), 1))()
+    for k, (depth, sites, records, het, hom) in enumerate(rows):
+        arr[k] = DepthRow(sites, records, het, hom, depth, 0)
+    return arr, len(rows)
+
+
+def depth_hist_host(sites: "Sites", code_all: np.ndarray, begin: int = 0, end: int = None) -> list:
+    """sid_depth_hist_host: the rows of the depth histogram of sites [begin, end)
+    from their codes before any selection marked them."""
+    code_all = np.ascontiguousarray(code_all, np.uint8)
+    if end is None:
+        end = len(sites)
+    if code_all.size != len(sites):
+        raise SidError(1, "depth_hist_host: one code per site")
+    rows, n = C.POINTER(DepthRow)(), C.c_size_t(0)
+    check(lib().sid_depth_hist_host(sites.handle, begin, end, _ptr(code_all), C.byref(rows), C.byref(n)),
+          "sid_depth_hist_host")
+    try:
+        return _depth_rows(rows, n.value)
+    finally:
+        lib().sid_depth_hist_free(rows)
+
+
+def depth_hist_format(rows, header: bool = True) -> bytes:
+    """sid_depth_hist_format over rows as depth_hist_host / Engine.depth_hist return them."""
+    arr, m = _depth_array(rows)
+    n = C.c_size_t(0)
+    st = lib().sid_depth_hist_format(arr, m, int(bool(header)), None, 0, C.byref(n))
+    if st not in (SID_OK, 3):
+        check(st, "sid_depth_hist_format")
+    buf = C.create_string_buffer(max(n.value, 1))
+    check(lib().sid_depth_hist_format(arr, m, int(bool(header)), buf, n.value, C.byref(n)), "sid_depth_hist_format")
+    return buf.raw[:n.value]
+
+
+def depth_hist_merge(a, b) -> list:
+    """sid_depth_hist_merge: the sum of two row sets (ranks that took site
+    ranges add their rows with it); both strictly ascending in depth."""
+    aa, na = _depth_array(a)
+    ab, nb = _depth_array(b)
+    rows, n = C.POINTER(DepthRow)(), C.c_size_t(0)
+    check(lib().sid_depth_hist_merge(aa, na, ab, nb, C.byref(rows), C.byref(n)), "sid_depth_hist_merge")
+    try:
+        return _depth_rows(rows, n.value)
+    finally:
+        lib().sid_depth_hist_free(rows)
+
+
+def dtext_depth_hist(ctx: "Context", dtext: "DText", code_ptr, begin: int = 0, end: int = None, stream=None) -> list:
+    """sid_dtext_depth_hist: the histogram's stage over sites [begin, end) of a
+    resident shard with the given device codes."""
+    if end is None:
+        end = len(dtext)
+    rows, n = C.POINTER(DepthRow)(), C.c_size_t(0)
+    check(lib().sid_dtext_depth_hist(ctx.h, dtext.h, begin, end, code_ptr, C.byref(rows), C.byref(n), stream),
+          "sid_dtext_depth_hist")
+    try:
+        return _depth_rows(rows, n.value)
+    finally:
+        lib().sid_depth_hist_free(rows)
 
 
 def device_count() -> int:
@@ -877,7 +963,7 @@ class Engine:
 
     def __init__(self, method="local", devices=1, first_device=0, chunk_bytes=0, slots=0, hold_bytes=0,
                  retain_bytes=0, host_threads=0, verbose=False, device_sink=False, lanes=0, host_hold_bytes=0,
-                 min_depth=0, max_depth=0, format="csv", **opts):
+                 min_depth=0, max_depth=0, format="csv", depth_hist=False, **opts):
         fmt = _format(format)
         self.opts = make_opts(method=method, **opts)
         cfg = EngineCfg()
@@ -896,6 +982,8 @@ class Engine:
             self.set_depth(min_depth, max_depth)
         if fmt:                      # (nor is the record format)
             self.set_format(fmt)
+        if depth_hist:               # (nor the depth histogram's switch)
+            self.set_depth_hist(True)
 
     def close(self):
         if getattr(self, "h", None):
@@ -921,6 +1009,11 @@ class Engine:
         now on; SID_ESTATE between an ingest and its emit.  The header stays the
         caller's: emit(header=vcf_header(...))."""
         check(lib().sid_engine_set_format(self.h, _format(format)), "sid_engine_set_format")
+
+    def set_depth_hist(self, on: bool):
+        """The depth histogram of every run from now on (Engine.depth_hist);
+        SID_ESTATE between an ingest and its emit."""
+        check(lib().sid_engine_set_depth_hist(self.h, int(on)), "sid_engine_set_depth_hist")
 
     def placement(self, i=0) -> dict:
         """Pipeline i's host placement: its GPU's NUMA node, the CPUs its
@@ -1012,6 +1105,8 @@ class Engine:
         cb = WRITE_FN(w)
         st = stats if stats is not None else RunStats()
         check(lib().sid_engine_emit(self.h, header, cb, None, C.byref(st)), "sid_engine_emit")
+        rows, n = C.POINTER(DepthRow)(), C.c_size_t(0)   # (SID_ESTATE with the option off: no rows)
+        st.depth_rows = n.value if lib().sid_engine_depth_hist(self.h, C.byref(rows), C.byref(n)) == SID_OK else 0
         return b"".join(parts), st
 
     def profile_table(self):
@@ -1051,6 +1146,13 @@ class Engine:
         check(lib().sid_engine_windows(self.h, C.byref(rows), C.byref(n)), "sid_engine_windows")
         return _window_rows(rows, n.value)
 
+    def depth_hist(self) -> list:
+        """The depth histogram of the last run (depth_hist=True), after emit:
+        tuples (depth, sites, records, het, hom) in ascending depth order."""
+        rows, n = C.POINTER(DepthRow)(), C.c_size_t(0)
+        check(lib().sid_engine_depth_hist(self.h, C.byref(rows), C.byref(n)), "sid_engine_depth_hist")
+        return _depth_rows(rows, n.value)
+
     def profile(self, enable=True):
         check(lib().sid_engine_profile(self.h, int(bool(enable))), "sid_engine_profile")
 
@@ -1065,6 +1167,7 @@ class Engine:
         out, st2 = self.emit(header, sink)
         st.bytes_out, st.emit_s, st.chunks_reloaded = st2.bytes_out, st2.emit_s, st2.chunks_reloaded
         st.window_rows = st2.window_rows
+        st.depth_rows = st2.depth_rows
         st.estimate = est
         return out, st
 

@@ -270,6 +270,35 @@ extern "C" int sid_set_depth(sid_ctx* c, int min, int max)
     return SID_OK;
 }
 
+// The depth histogram under a selection by label (sid_engine_set_depth_hist): its stage needs every site's
+// label, which the selecting parse and the filtered tables do not keep, so -- as under sid_opts.window --
+// the selection goes the context's route with N = 0: the unselected tables, tails and parse, and the
+// marking stage selects.  on = false: back to what sid_create left.  Nothing to do when the route is on
+// anyway or no label is selected.
+int sid_ctx_label_route(sid_ctx* c, bool on)
+{
+    if (!c) return SID_EINVAL;
+    if (on == c->dh_route) return SID_OK;
+    if (on && (c->cx_on || c->opts.select == SID_SELECT_ALL)) return SID_OK;
+    if (on) {
+        c->cx_select = c->opts.select;
+        c->opts.select = SID_SELECT_ALL;
+    } else {
+        c->opts.select = c->cx_select;
+        c->cx_select = SID_SELECT_ALL;
+    }
+    c->dh_route = c->cx_on = c->cx_base = on;
+    c->cx_n = 0;
+    const bool regions = c->has_regions || c->cx_regions, variants = c->has_variants || c->cx_variants;
+    const bool depth = c->has_depth || c->cx_depth;
+    c->has_regions = regions && !on, c->cx_regions = regions && on;
+    c->has_variants = variants && !on, c->cx_variants = variants && on;
+    c->has_depth = depth && !on, c->cx_depth = depth && on;
+    (void)hipSetDevice(c->device);
+    const hipError_t e = sid_build_table(c);   // (the tails by opts.select)
+    return e == hipSuccess ? SID_OK : sid_set_hip_error(e);
+}
+
 // The record format (sid.h Conventions, "VCF"): the marking stages are the
 // CSV's; the VCF stage then replaces the length and put kernels, and the parse
 // keeps every site's reference byte (sid_chunk_ws::refb) as it does for the

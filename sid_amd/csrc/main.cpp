@@ -12,7 +12,21 @@
 // reference's flags): --devices N, --threads N, --stats, --host-parse,
 // --chunk-bytes N, --hold-bytes N, --retain-bytes N, --host-hold N,
 // --only het|hom|all, --regions FILE, --bgzf, --context N, --windows W,
-// --windows-out FILE, --variants, --min-depth N, --max-depth N, --vcf.
+// --windows-out FILE, --variants, --min-depth N, --max-depth N, --vcf,
+// --depth-hist FILE.
+//
+// --depth-hist FILE: beside the records, the depth histogram of the run
+// (sid_engine_set_depth_hist, sid.h Conventions) as CSV into FILE --
+// "depth,sites,records,het,hom" and a line per depth that a site has, in
+// ascending order, the columns as --windows-out's -- written after the records;
+// stdout, stderr and the exit status are as without it, whatever --only,
+// --regions, --variants, --min-depth / --max-depth, --context and --vcf select
+// or print.  A FILE that cannot be created: "sid: --depth-hist: could not open
+// FILE" on stderr, exit status 1, nothing on stdout, before any input is read;
+// a failed write: "sid: --depth-hist: could not write FILE".  As with
+// --windows-out the file is written only after the records: a failing run
+// leaves none (one that was there before stays as it was).  With --host-parse:
+// sid_depth_hist_host.  Not listed by -h, whose text stays the reference's.
 //
 // --vcf (no argument) writes the records as VCF lines behind a VCF header
 // (sid_vcf_header) in place of the CSV and its header line (sid.h Conventions,
@@ -315,6 +329,7 @@ int main(int argc, char** argv)
     const char* windows_out = nullptr;   // --windows-out
     int min_depth = 0, max_depth = 0;    // --min-depth, --max-depth
     bool vcf = false;                    // --vcf
+    const char* depth_hist_out = nullptr;   // --depth-hist
     static const struct option LONG[] = {{"devices", required_argument, nullptr, 1},
                                          {"threads", required_argument, nullptr, 2},
                                          {"stats", no_argument, nullptr, 3},
@@ -333,6 +348,7 @@ int main(int argc, char** argv)
                                          {"min-depth", required_argument, nullptr, 16},
                                          {"max-depth", required_argument, nullptr, 17},
                                          {"vcf", no_argument, nullptr, 18},
+                                         {"depth-hist", required_argument, nullptr, 19},
                                          {nullptr, 0, nullptr, 0}};
     int flag;
     while ((flag = getopt_long(argc, argv, "E:Rhm:p:r:", LONG, nullptr)) != -1) {
@@ -448,6 +464,7 @@ int main(int argc, char** argv)
             break;
         }
         case 18: vcf = true; break;
+        case 19: depth_hist_out = optarg; break;   // (given twice: the last wins)
         default: std::exit(EXIT_FAILURE);
         }
     }
@@ -472,6 +489,17 @@ int main(int argc, char** argv)
         }
         ::close(fd);
         if (!was) ::unlink(windows_out);
+    }
+    if (depth_hist_out) {   // likewise
+        const bool was = ::access(depth_hist_out, F_OK) == 0;
+        const int fd = ::open(depth_hist_out, O_WRONLY | O_CREAT, 0666);
+        if (fd < 0) {
+            std::fflush(stdout);
+            std::fprintf(stderr, "sid: --depth-hist: could not open %s\n", depth_hist_out);
+            std::exit(EXIT_FAILURE);
+        }
+        ::close(fd);
+        if (!was) ::unlink(depth_hist_out);
     }
     if (optind >= argc) {
         std::fflush(stdout);
@@ -533,6 +561,7 @@ int main(int argc, char** argv)
         int rc = sid_engine_create(&opt.o, &cfg, &eng);
         if (rc == SID_OK && depth_on) rc = sid_engine_set_depth(eng, min_depth, max_depth);
         if (rc == SID_OK && vcf) rc = sid_engine_set_format(eng, SID_FORMAT_VCF);
+        if (rc == SID_OK && depth_hist_out) rc = sid_engine_set_depth_hist(eng, 1);
         return rc;
     };
     int dev_rc = SID_OK, eng_rc = SID_OK;
@@ -637,6 +666,25 @@ int main(int argc, char** argv)
             std::exit(EXIT_FAILURE);
         }
     };
+    // --depth-hist: the rows as CSV, after the records
+    auto write_depth_hist = [&](const sid_depth_row* rows, size_t nrows) {
+        size_t need = 0;
+        (void)sid_depth_hist_format(rows, nrows, 1, nullptr, 0, &need);
+        std::string csv(need, '\0');
+        CHECK(sid_depth_hist_format(rows, nrows, 1, &csv[0], need, &need), "depth-hist");
+        const int fd = ::open(depth_hist_out, O_WRONLY | O_CREAT | O_TRUNC, 0666);
+        size_t off = 0;
+        while (fd >= 0 && off < csv.size()) {
+            const ssize_t w = ::write(fd, csv.data() + off, csv.size() - off);
+            if (w <= 0) break;
+            off += (size_t)w;
+        }
+        if (fd < 0 || off < csv.size() || ::close(fd) != 0) {
+            std::fflush(stdout);
+            std::fprintf(stderr, "sid: --depth-hist: could not write %s\n", depth_hist_out);
+            std::exit(EXIT_FAILURE);
+        }
+    };
     // --bgzf: the bytes are not BGZF from their first member on / a member further in is truncated or corrupt
     auto bgzf_error = [&](uint64_t off, bool at_index) {
         std::fflush(stdout);
@@ -693,6 +741,12 @@ int main(int argc, char** argv)
             CHECK(sid_engine_windows(eng, &rows, &nrows), "windows");
             write_windows(rows, nrows);
         }
+        size_t depth_rows = 0;   // (sid_run_stats has no field for them: its layout stands)
+        if (depth_hist_out) {
+            const sid_depth_row* rows = nullptr;
+            CHECK(sid_engine_depth_hist(eng, &rows, &depth_rows), "depth-hist");
+            write_depth_hist(rows, depth_rows);
+        }
         const double t3 = now();
         std::string place;   // per pipeline: its GPU, the CPUs its threads ran on, its pinned buffers' NUMA nodes
         if (opt.stats)
@@ -716,7 +770,7 @@ int main(int argc, char** argv)
                          "\"bytes_out\": %llu, \"ingest_s\": %.6f, \"chunks_registered\": %llu, "
                          "\"register_s\": %.6f, \"h2d_s\": %.6f, \"h2d_bytes\": %llu, \"chunks_tiled\": %llu, "
                          "\"tile_overflows\": %llu, \"tile_overflows_queued\": %llu, \"bgzf_bytes\": %llu, "
-                         "\"bgzf_blocks\": %llu, \"window_rows\": %llu, \"placement\": [%s], "
+                         "\"bgzf_blocks\": %llu, \"window_rows\": %llu, \"depth_rows\": %llu, \"placement\": [%s], "
                          "\"main_entry_unix\": %.6f, \"main_exit_unix\": %.6f}\n",
                          (unsigned long long)st.sites, D, T, tc - t0, t1 - t0, t2 - t1, t3 - t2, t3 - t0,
                          st.sites / std::max(1e-9, t3 - t0), (unsigned long long)st.chunks,
@@ -726,7 +780,8 @@ int main(int argc, char** argv)
                          st.register_s, st.h2d_s, (unsigned long long)st.h2d_bytes,
                          (unsigned long long)st.chunks_tiled, (unsigned long long)st.tile_overflows,
                          (unsigned long long)st.tile_overflows_queued, (unsigned long long)st.bgzf_bytes,
-                         (unsigned long long)st.bgzf_blocks, (unsigned long long)st.window_rows, place.c_str(),
+                         (unsigned long long)st.bgzf_blocks, (unsigned long long)st.window_rows,
+                         (unsigned long long)depth_rows, place.c_str(),
                          t_entry,
                          unix_now());
         // device memory, pinned staging and the mapping go with the process
@@ -851,7 +906,7 @@ int main(int argc, char** argv)
     // ----------------------------------------------------------------- emit --
     std::fputs(HEADER, stdout);
     std::fflush(stdout);
-    size_t window_rows = 0;
+    size_t window_rows = 0, depth_rows = 0;
     {
         uint8_t* h_code = nullptr;
         double *h_hom = nullptr, *h_het = nullptr;
@@ -875,6 +930,10 @@ int main(int argc, char** argv)
         size_t nwrows = 0;
         if (windows_out) CHECK(sid_windows_host(sites, 0, n, h_code, opt.o.window, &wrows, &nwrows), "windows");
         window_rows = nwrows;
+        sid_depth_row* drows = nullptr;   // --depth-hist: likewise
+        size_t ndrows = 0;
+        if (depth_hist_out) CHECK(sid_depth_hist_host(sites, 0, n, h_code, &drows, &ndrows), "depth-hist");
+        depth_rows = ndrows;
         std::vector<uint8_t> code_all;   // --context: the codes before the selections marked them
         if (opt.o.context > 0 && (opt.o.select != SID_SELECT_ALL || regions || opt.o.variants || depth_on))
             code_all.assign(h_code, h_code + n);
@@ -921,15 +980,17 @@ int main(int argc, char** argv)
         for (auto& x : th) x.join();
         if (windows_out) write_windows(wrows, nwrows);
         sid_windows_free(wrows);
+        if (depth_hist_out) write_depth_hist(drows, ndrows);
+        sid_depth_hist_free(drows);
     }
     double t3 = now();
     if (opt.stats) {
         std::fprintf(stderr,
                      "{\"sites\": %zu, \"devices\": %d, \"threads\": %d, \"path\": \"%s\", \"parse_s\": %.6f, "
                      "\"device_s\": %.6f, \"emit_s\": %.6f, \"total_s\": %.6f, \"sites_per_s\": %.1f, "
-                     "\"window_rows\": %zu, \"main_entry_unix\": %.6f, \"main_exit_unix\": %.6f}\n",
+                     "\"window_rows\": %zu, \"depth_rows\": %zu, \"main_entry_unix\": %.6f, \"main_exit_unix\": %.6f}\n",
                      n, D, T, "host", t1 - t0, t2 - t1, t3 - t2, t3 - t0,
-                     n / std::max(1e-9, t3 - t0), window_rows, t_entry, unix_now());
+                     n / std::max(1e-9, t3 - t0), window_rows, depth_rows, t_entry, unix_now());
     }
     // device memory, pinned staging and mappings go with the process: freeing
     // gigabytes of HBM and pinned host memory one by one only delays the exit

@@ -52,6 +52,7 @@
 #include "bgzf_dev.h"
 #include "context.h"
 #include "windows.h"
+#include "depth_hist.h"
 #include "sid_internal.h"
 #include "synth.h"
 
@@ -250,6 +251,8 @@ struct ChunkRec {
     // the windowed summary (sid_opts.window): the chunk's rows, read back with its byte count by the pass
     // that formats it -- once, whichever pass and path that is
     sid_win_chunk win;
+    // the depth histogram (sid_engine_set_depth_hist): the chunk's rows sorted by depth, read back likewise
+    std::vector<sid_dh_row> dh;
 };
 
 enum SrcKind { SRC_NONE, SRC_HOST, SRC_FILE, SRC_DEVICE, SRC_SYNTH_HOST, SRC_SYNTH_DEVICE, SRC_BGZF, SRC_BGZF_FILE };
@@ -751,6 +754,9 @@ struct sid_engine {
     bool cx_on = false;              // ... and whether its route is (sid_ctx::cx_on)
     sid_win_table win;               // sid_opts.window: the run's rows, stitched by the emit
     bool win_ready = false;
+    bool depth_hist = false;         // sid_engine_set_depth_hist
+    std::vector<sid_depth_row> dh;   // ... the run's rows, the chunks' summed by the emit
+    bool dh_ready = false;
     bool prof = false;
     double prof_ms[6] = {0, 0, 0, 0, 0, 0};   // sid_engine_prof order: index parse call hist fmt_len fmt_write
     uint64_t prof_chunks = 0;
@@ -1002,6 +1008,8 @@ static void drop_source(sid_engine* e)
     e->recs.clear();
     e->win.clear();
     e->win_ready = false;
+    e->dh.clear();
+    e->dh_ready = false;
     sid_bgzf_free(e->zidx);
     e->zidx = nullptr;
     e->src = SRC_NONE;
@@ -1845,6 +1853,24 @@ void compute(sid_engine* e, Dev& d, int pass)
         if (x == hipSuccess) x = sync();
         return x;
     };
+    // the depth histogram likewise: the set (sid_chunk_ws::dh_cur) a chunk's stage wrote, and its rows out of
+    // the set's pinned block (sid_chunk_ws::dh_eager) or, beyond what it holds, by a copy of their own.  A set
+    // holds every depth: no chunk runs again for it
+    const bool dhist = e->depth_hist;
+    int next_dset = 0;
+    auto dh_take = [&](int b, std::vector<sid_dh_row>& c) {
+        const char* hb = W.dh_eager[b];
+        const uint64_t nr = *(const uint64_t*)hb;
+        if (nr > SID_DH_BINS) return hipErrorUnknown;
+        c.resize(nr);
+        if (nr <= SID_DH_EAGER_ROWS) {
+            if (nr) std::memcpy(c.data(), hb + 16, nr * sizeof(sid_dh_row));
+            return hipSuccess;
+        }
+        hipError_t x = hipMemcpyAsync(c.data(), W.dh_rows[b], nr * sizeof(sid_dh_row), hipMemcpyDeviceToHost, d.s_comp);
+        if (x == hipSuccess) x = sync();
+        return x;
+    };
     auto take = [&](Loaded& out) {
         if (have_next) {
             out = nextL;
@@ -1906,6 +1932,7 @@ void compute(sid_engine* e, Dev& d, int pass)
         hipEvent_t pe = nullptr;
         uint64_t n = 0;
         int wset = pre_tiled ? next_wset : -1;   // the window stage's set of this chunk (none: no stage ran)
+        int dset = pre_tiled ? next_dset : -1;   // ... and the depth histogram's
         // the tile path: this chunk's records and byte count done (recorded
         // before the next chunk's tile parse is queued behind the writer: the
         // host and the records' D2H wait for this, not for that parse, which
@@ -1976,6 +2003,7 @@ void compute(sid_engine* e, Dev& d, int pass)
                     rc = sid_chunk_tile_local(d.ctx, &W, L.base, L.c0, L.c1, lg, quad, e->conf_type, d.s_comp);
                     d.prof_end(1, pe);
                     wset = W.win_cur;
+                    dset = W.dh_cur;
                 }
                 if (rc == SID_OK) {
                     pe = d.prof_begin(P);
@@ -2014,6 +2042,7 @@ void compute(sid_engine* e, Dev& d, int pass)
                         if (rc2 != SID_OK) return (void)fail(e, rc2);
                         next_tiled = x == hipSuccess;
                         next_wset = W.win_cur;
+                        next_dset = W.dh_cur;
                         next_lg = lg2;
                         next_quad = q2;
                     }
@@ -2236,6 +2265,7 @@ void compute(sid_engine* e, Dev& d, int pass)
                 d.prof_end(4, pe);
                 if (rc != SID_OK) return (void)fail(e, rc);
                 wset = W.win_cur;
+                dset = W.dh_cur;
                 pe = d.prof_begin(P);
                 rc = fused    ? sid_chunk_local_put(d.ctx, &W, L.base, L.c1, n, e->conf_type, out, d.s_comp)
                      : lfused ? sid_chunk_lynch_put(d.ctx, &W, L.base, L.c1, n, out, d.s_comp)
@@ -2320,6 +2350,15 @@ void compute(sid_engine* e, Dev& d, int pass)
                 win_want(wset);
                 x = win_take(wset, r.win);
                 if (x != hipSuccess) return (void)hipfail(e, x);
+            }
+        }
+        if (dhist) {   // (likewise)
+            r.dh.clear();
+            if (out) {
+                if (dset < 0) return (void)fail(e, SID_ESTATE);
+                x = dh_take(dset, r.dh);
+                if (x != hipSuccess) return (void)hipfail(e, x);
+                if (!sid_dh_sort(&r.dh)) return (void)fail(e, SID_ESTATE);
             }
         }
         release_slot();
@@ -2604,9 +2643,12 @@ static void reset_run(sid_engine* e)
         r.cx = sid_cx_desc{};
         r.cx_total = 0;
         r.win.clear();
+        r.dh.clear();
     }
     e->win.clear();
     e->win_ready = false;
+    e->dh.clear();
+    e->dh_ready = false;
     e->z_bytes = 0;
     e->z_blocks = 0;
     for (auto& dp : e->devs) {
@@ -2972,7 +3014,43 @@ extern "C" int sid_engine_emit(sid_engine* e, const char* header, sid_write_fn w
         }
         if (st) st->window_rows = e->win.rows.size();
     }
+    // ... and (sid_engine_set_depth_hist) the chunks' depth rows summed: a sorted merge per chunk
+    if (e && e->depth_hist && rc != SID_ESTATE && rc != SID_EINVAL) {
+        e->dh.clear();
+        e->dh_ready = rc == SID_OK;
+        if (rc == SID_OK)
+            for (const auto& r : e->recs) sid_dh_add(&e->dh, r.dh);
+    }
     return rc;
+}
+
+extern "C" int sid_engine_set_depth_hist(sid_engine* e, int on)
+{
+    if (!e || (on != 0 && on != 1)) return SID_EINVAL;
+    if (e->ingested) return SID_ESTATE;
+    for (auto& d : e->devs) {
+        // (a selection by label: through the context's route, whose parse keeps every site's label)
+        const int rc = sid_ctx_label_route(d->ctx, on != 0);
+        if (rc != SID_OK) return rc;
+        sid_chunk_bind_context(&d->ws, d->ctx);
+        d->ws.dh_on = on != 0;   // (the workspace's buffers: at its next reservation)
+    }
+    e->cx_n = e->devs[0]->ctx->cx_n;
+    e->cx_on = e->devs[0]->ctx->cx_on;
+    e->depth_hist = on != 0;
+    e->dh.clear();
+    e->dh_ready = false;
+    return SID_OK;
+}
+
+extern "C" int sid_engine_depth_hist(sid_engine* e, const sid_depth_row** rows, size_t* n)
+{
+    if (!e || !rows || !n) return SID_EINVAL;
+    *rows = nullptr, *n = 0;
+    if (!e->depth_hist || !e->dh_ready) return SID_ESTATE;
+    *rows = e->dh.data();
+    *n = e->dh.size();
+    return SID_OK;
 }
 
 extern "C" int sid_engine_windows(sid_engine* e, const sid_window** rows, size_t* n)

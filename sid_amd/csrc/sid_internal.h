@@ -152,6 +152,8 @@ struct sid_ctx {
     // the route's switch: a context in effect, or (cx_n = 0) a selection by label under sid_opts.window, whose
     // stage reads every site's label in front of the marking stage
     bool cx_on = false;
+    // ... switched on by sid_ctx_label_route (the depth histogram under a selection by label)
+    bool dh_route = false;
     // measurement (sid_timing_enable / sid_timing_read)
     int timing = 0;
     std::vector<sid_timing_ev> ev_pool, ev_pending;
@@ -275,7 +277,23 @@ struct sid_chunk_ws {
     uint32_t win_cap[2] = {0, 0}, win_ncap[2] = {0, 0};
     uint64_t win_want_rows = 0, win_want_names = 0;
     int win_cur = 0;            // the set the last stage wrote
+    // the depth histogram's stage (the owner's sid_engine_set_depth_hist; depth_hist.h, textpath.hip
+    // sid_depth_hist_*_kernel), beside the window stage: one table of three u32 counters per depth (sites,
+    // het, hom records; all zero between two stage runs -- the pack kernel clears the bins it read), and two
+    // sets of {count, rows, pinned block} used in turn, as the window stage's.  A set's rows hold every
+    // depth (SID_DH_BINS rows), so no chunk outgrows it
+    bool dh_on = false;
+    uint32_t* dh_bins = nullptr;
+    unsigned long long* dh_cnt[2] = {nullptr, nullptr};   // the chunk's rows (the bins touched)
+    struct sid_dh_row* dh_rows[2] = {nullptr, nullptr};
+    char* dh_eager[2] = {nullptr, nullptr};    // pinned host memory: the set's count and first rows, stored by the
+                                               // pack kernel (SID_DH_EAGER_BYTES)
+    int dh_cur = 0;             // the set the last stage wrote
 };
+// the rows that reach the host with every chunk's byte count (more: a copy of their own), behind two words
+// of count: 16 B a row (a 30x run has some 80 depths, a 200x run some 150)
+constexpr uint32_t SID_DH_EAGER_ROWS = 384;
+constexpr size_t SID_DH_EAGER_BYTES = 16 + SID_DH_EAGER_ROWS * 16;
 // the rows and name bytes that reach the host with every chunk's byte count (more: a copy of their own),
 // behind four words of counts: one small block (sid_window_pack_kernel; 40 B a row)
 constexpr uint32_t SID_WIN_EAGER_ROWS = 64, SID_WIN_EAGER_NAMES = 512;
@@ -361,6 +379,7 @@ hipError_t sid_scan_u32(const uint32_t* in, uint64_t m, uint64_t* out, uint64_t*
 
 // host helpers (capi.cpp)
 int sid_set_hip_error(hipError_t e);
+int sid_ctx_label_route(sid_ctx* c, bool on);
 double sid_gsl_lngamma(double x);   // GSL 2.7.1 gsl_sf_lngamma restated (x >= 0.5)
 void sid_build_local_k(const sid_opts& o, sid_local_k* K);
 // Poisson(mean) CDF as 64-bit thresholds (synth.h); returns kmax

@@ -44,6 +44,7 @@
 #include "fmt.h"
 #include "vcf.h"
 #include "windows.h"
+#include "depth_hist.h"
 #include "local_site.h"
 
 namespace {
@@ -4807,6 +4808,173 @@ static void launch_window_fill(WinArgs<Off>& C, const WinBufs& B, hipStream_t st
     sid_window_fill_kernel<MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(C);
 }
 
+// -------------------------------------------------------- depth histogram --
+// The depth histogram (sid_engine_set_depth_hist; depth_hist.h): per depth the
+// chunk's sites, het records and hom records.  The stage reads what the window
+// stage reads, through the same loaders -- sv_site on the unfiltered tables,
+// sv_label, and sv_depth for the bin -- and runs beside it, in front of the
+// marking stages.  Two steps:
+// (the set's count is zero before and after, as the bins are)
+//   hist   a block walks 512-slot groups (grid-stride) and bins its sites of
+//          depth < DH_LDS in LDS, one 64-bit word a bin: sites, het and hom in
+//          21-bit fields (a block sees at most DH_GROUPS_MAX groups = 2^20
+//          sites), so a site costs one LDS atomic.  At the end the block adds
+//          its non-zero bins to the chunk's table with global atomics: a 30x
+//          chunk some 80 bins a block instead of 3 counters a site.  Depths
+//          from DH_LDS on are rare and go straight to the table.  The add
+//          that finds a bin's site counter at 0 appends the depth to the
+//          set's rows: the chunk's bins, each once, in no order.
+//   pack   a thread per appended depth: the bin's three counters into its row,
+//          the bin cleared -- the table is all zero again for the next chunk
+//          without a 3 MB memset -- and the count and the first
+//          SID_DH_EAGER_ROWS rows stored into the set's pinned block, which the
+//          host reads after the sync that brings the chunk's byte count (as
+//          win_eager; more rows: a copy from the set's device rows).
+// FORM, the way a wave's lanes reach the LDS bins (the environment
+// variable SID_DH_FORM picks one, a measurement switch):
+//   0  every lane its own LDS atomic
+//   1  the wave's distinct depths one by one: a ballot of the lanes that share
+//      the first pending lane's depth, three popcounts, one LDS atomic by that
+//      lane (a 30x wave has some 20 distinct depths)
+constexpr uint32_t DH_LDS = 1024;          // depths binned in LDS
+constexpr uint32_t DH_GRID = 1024;         // blocks at most ...
+constexpr uint64_t DH_GROUPS_MAX = 2048;   // ... unless a block would walk more groups than this
+constexpr uint32_t DH_FIELD = 21;          // bits a field: DH_GROUPS_MAX * FTB sites fit
+static_assert(DH_GROUPS_MAX * FTB < (1ull << DH_FIELD), "a block's sites fit a field");
+static_assert(DH_LDS % FTB == 0 && DH_LDS <= SID_DH_BINS, "the flush: whole rounds of the block");
+
+template <class Off>
+struct DhArgs {
+    SiteArgs<Off> A;              // the sites
+    uint64_t ng;                  // their 512-slot groups
+    uint32_t* bins;               // per depth: [0] sites [1] het records [2] hom records
+    unsigned long long* cnt;      // the rows appended
+    sid_dh_row* rows;
+    uint32_t cap;                 // (SID_DH_BINS: every depth fits)
+};
+
+// s sites (>= 1), h het and m hom records of depth d (< SID_DH_BINS) into the table
+__device__ __forceinline__ void dh_table_add(uint32_t* bins, unsigned long long* cnt, sid_dh_row* rows, uint32_t cap,
+                                             uint32_t d, uint32_t s, uint32_t h, uint32_t m)
+{
+    uint32_t* b = bins + 3 * (size_t)d;
+    const uint32_t old = atomicAdd(b, s);
+    if (h) atomicAdd(b + 1, h);
+    if (m) atomicAdd(b + 2, m);
+    if (old == 0) {   // the bin's first sites of this chunk: its row
+        const unsigned long long at = atomicAdd(cnt, 1ull);
+        if (at < cap) rows[at].depth = d;
+    }
+}
+
+template <int MODE, bool OPT, int FORM, class Off>
+__global__ __launch_bounds__(FTB) void sid_depth_hist_kernel(const DhArgs<Off> C)
+{
+    __shared__ unsigned long long lbin[DH_LDS];
+    const SiteArgs<Off>& A = C.A;
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t k = threadIdx.x; k < DH_LDS; k += FTB) lbin[k] = 0;
+    __syncthreads();
+    for (uint64_t g = blockIdx.x; g < C.ng; g += gridDim.x) {
+        const uint64_t i = A.s0 + g * FTB + threadIdx.x;
+        uint32_t w;
+        const bool site = sv_site<MODE, OPT, 0>(A, i, &w);   // (the unselected parse, as the window stage)
+        bool rec = false, het = false;
+        uint32_t d = 0;
+        if (site) {
+            sv_label<MODE>(A, i, w, &rec, &het);
+            d = sv_depth<MODE, OPT>(A, i, w);
+        }
+        const bool rh = rec && het, rm = rec && !het;
+        if (site && d >= DH_LDS && d < SID_DH_BINS) dh_table_add(C.bins, C.cnt, C.rows, C.cap, d, 1u, rh, rm);
+        const bool low = site && d < DH_LDS;
+        if (FORM == 0) {
+            if (low) atomicAdd(&lbin[d], 1ull | ((unsigned long long)rh << DH_FIELD) | ((unsigned long long)rm << 2 * DH_FIELD));
+        } else {
+            unsigned long long left = __ballot(low);
+            while (left) {   // (wave-uniform)
+                const int src = __ffsll((long long)left) - 1;
+                const uint32_t dv = (uint32_t)__shfl((int)d, src, 64);
+                const bool mine = low && d == dv;
+                const unsigned long long bm = __ballot(mine), bh = __ballot(mine && rh), bo = __ballot(mine && rm);
+                if ((int)lane == src)
+                    atomicAdd(&lbin[dv], (unsigned long long)__popcll(bm) | ((unsigned long long)__popcll(bh) << DH_FIELD) |
+                                             ((unsigned long long)__popcll(bo) << 2 * DH_FIELD));
+                left &= ~bm;
+            }
+        }
+    }
+    __syncthreads();
+    constexpr unsigned long long FM = (1ull << DH_FIELD) - 1ull;
+    for (uint32_t k = threadIdx.x; k < DH_LDS; k += FTB) {
+        const unsigned long long v = lbin[k];
+        if (v) dh_table_add(C.bins, C.cnt, C.rows, C.cap, k, (uint32_t)(v & FM), (uint32_t)(v >> DH_FIELD & FM),
+                            (uint32_t)(v >> 2 * DH_FIELD & FM));
+    }
+}
+
+// (one block: a chunk has a few hundred rows, and the block that has read the count is the one that clears it.
+// out: where the count goes -- the set's pinned block, or a call's own word)
+__global__ __launch_bounds__(SCAN_TB) void sid_depth_hist_pack_kernel(unsigned long long* __restrict__ cnt,
+                                                                      uint32_t* __restrict__ bins,
+                                                                      sid_dh_row* __restrict__ rows, uint32_t cap,
+                                                                      char* __restrict__ eager,
+                                                                      unsigned long long* __restrict__ out)
+{
+    const uint64_t n = min((uint64_t)cnt[0], (uint64_t)cap);
+    __syncthreads();
+    if (threadIdx.x == 0) cnt[0] = 0;   // (zero again for the next chunk, as the bins)
+    if (threadIdx.x < 2) out[threadIdx.x] = threadIdx.x ? 0ull : n;
+    sid_dh_row* er = eager ? (sid_dh_row*)(eager + 16) : nullptr;
+    for (uint64_t k = threadIdx.x; k < n; k += SCAN_TB) {
+        sid_dh_row r = rows[k];
+        if (r.depth >= SID_DH_BINS) continue;   // (never: dh_table_add stores a bin's index)
+        uint32_t* b = bins + 3 * (size_t)r.depth;
+        r.sites = b[0], r.het = b[1], r.hom = b[2];
+        b[0] = b[1] = b[2] = 0;
+        rows[k] = r;
+        if (er && k < SID_DH_EAGER_ROWS) er[k] = r;
+    }
+}
+
+// 1: a wave's distinct depths one by one; 0: a lane an LDS atomic (SID_DH_FORM, a measurement switch)
+#ifndef SID_DH_FORM_DEFAULT
+#define SID_DH_FORM_DEFAULT 0
+#endif
+static int dh_form()
+{
+    static const int form = [] {
+        const char* g = std::getenv("SID_DH_FORM");
+        return g ? (std::atoi(g) != 0) : SID_DH_FORM_DEFAULT;
+    }();
+    return form;
+}
+
+// the stage's device buffers: sid_chunk_ws's dh_* (the engine) or a call's own
+struct DhBufs {
+    uint32_t* bins;
+    unsigned long long* cnt;
+    sid_dh_row* rows;
+    char* eager;               // (or null: the caller copies the rows)
+    unsigned long long* out;   // two words for the chunk's row count: the head of `eager`, or a call's own
+};
+
+// the histogram of A's sites into B's rows; B.bins and B.cnt are all zero before and after
+template <int MODE, bool OPT, class Off>
+static void launch_depth_hist(const SiteArgs<Off>& A, const DhBufs& B, hipStream_t st)
+{
+    DhArgs<Off> C{};
+    C.A = A;
+    C.ng = (A.s1 - A.s0 + FTB - 1) / FTB;
+    C.bins = B.bins, C.cnt = B.cnt, C.rows = B.rows, C.cap = SID_DH_BINS;
+    if (C.ng) {
+        const uint64_t grid = std::max<uint64_t>(std::min<uint64_t>(C.ng, DH_GRID), (C.ng + DH_GROUPS_MAX - 1) / DH_GROUPS_MAX);
+        if (dh_form()) sid_depth_hist_kernel<MODE, OPT, 1, Off><<<(unsigned)grid, FTB, 0, st>>>(C);
+        else sid_depth_hist_kernel<MODE, OPT, 0, Off><<<(unsigned)grid, FTB, 0, st>>>(C);
+    }
+    sid_depth_hist_pack_kernel<<<1, SCAN_TB, 0, st>>>(B.cnt, B.bins, B.rows, SID_DH_BINS, B.eager, B.out);
+}
+
 // tails of the U classes (one thread each), then the dense codes' lengths
 __global__ __launch_bounds__(256) void sid_lynch_str_kernel(const uint8_t* __restrict__ pcode,
                                                            const double* __restrict__ cc, uint32_t U, CType ct,
@@ -5607,6 +5775,50 @@ extern "C" int sid_dtext_windows(sid_ctx* ctx, const sid_dtext* T, size_t begin,
     return sid_win_export(tab, rows, n);
 }
 
+// The depth histogram's stage over a resident shard: a table, a count and rows of this call's own.
+extern "C" int sid_dtext_depth_hist(sid_ctx* ctx, const sid_dtext* T, size_t begin, size_t end, const uint8_t* d_code,
+                                    sid_depth_row** rows, size_t* n, void* stream)
+{
+    if (!ctx || !T || !rows || !n) return SID_EINVAL;
+    *rows = nullptr, *n = 0;
+    if (end > T->nsites || begin > end || (end > begin && !d_code)) return SID_EINVAL;
+    std::vector<sid_depth_row> tab;
+    if (end == begin) return sid_dh_export(tab, rows, n);
+    if (end - begin >= (1ull << 32)) return SID_EINVAL;   // (the stage's counters are a chunk's: 32 bits)
+    TCHECK(hipSetDevice(T->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t o_rows = ((size_t)SID_DH_BINS * 3 * 4 + 15) & ~(size_t)15, o_cnt = o_rows + (size_t)SID_DH_BINS * sizeof(sid_dh_row);
+    char* d_ws = nullptr;
+    int rc = SID_OK;
+    auto hip = [&](hipError_t x) {
+        if (x != hipSuccess && rc == SID_OK) rc = sid_set_hip_error(x);
+        return rc == SID_OK;
+    };
+    std::vector<sid_dh_row> ch;
+    // (the call's words behind the rows: [0] the stage's count, [2] [3] the pack's copy of it)
+    if (hip(hipMalloc(&d_ws, o_cnt + 32)) && hip(hipMemsetAsync(d_ws, 0, o_rows, st)) &&
+        hip(hipMemsetAsync(d_ws + o_cnt, 0, 32, st))) {
+        const DhBufs B{(uint32_t*)d_ws, (unsigned long long*)(d_ws + o_cnt), (sid_dh_row*)(d_ws + o_rows), nullptr,
+                       (unsigned long long*)(d_ws + o_cnt + 16)};
+        launch_depth_hist<REG_CODE, false>(dtext_view(T, begin, end, const_cast<uint8_t*>(d_code)), B, st);
+        hip(hipGetLastError());
+        unsigned long long nr = 0;
+        hip(hipMemcpyAsync(&nr, B.out, 8, hipMemcpyDeviceToHost, st));
+        hip(hipStreamSynchronize(st));
+        if (rc == SID_OK && nr > SID_DH_BINS) rc = SID_ESTATE;
+        if (rc == SID_OK && nr) {
+            ch.resize(nr);
+            hip(hipMemcpyAsync(ch.data(), B.rows, nr * sizeof(sid_dh_row), hipMemcpyDeviceToHost, st));
+            hip(hipStreamSynchronize(st));
+        }
+    }
+    if (d_ws) (void)hipFree(d_ws);
+    if (rc != SID_OK) return rc;
+    if (!sid_dh_sort(&ch)) return SID_ESTATE;
+    sid_dh_add(&tab, ch);
+    return sid_dh_export(tab, rows, n);
+}
+
 extern "C" int sid_format_g6(double v, char* buf, size_t cap)
 {
     char tmp[SID_FMT_MAX];
@@ -5799,6 +6011,19 @@ static int window_stage(const SiteArgs<Off>& A, sid_chunk_ws* W, uint64_t text_b
     return SID_OK;
 }
 
+// The depth histogram's stage of one chunk, beside the window stage: the next set's count, rows and pinned
+// block.  A set holds every depth, so there is nothing to size and no chunk runs again for it.
+template <int MODE, bool OPT, class Off>
+static int depth_hist_stage(const SiteArgs<Off>& A, sid_chunk_ws* W, hipStream_t st)
+{
+    if (!W->dh_bins) return SID_ESTATE;   // (a workspace not reserved)
+    const int b = (W->dh_cur ^= 1);
+    launch_depth_hist<MODE, OPT>(A, DhBufs{W->dh_bins, W->dh_cnt[b], W->dh_rows[b], W->dh_eager[b],
+                                              (unsigned long long*)W->dh_eager[b]}, st);
+    WCHECK(hipGetLastError());
+    return SID_OK;
+}
+
 int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites)
 {
     // grow-only; hipFree waits for the device, so buffers still in use by
@@ -5819,6 +6044,17 @@ int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites)
             std::memset(W->win_eager[b], 0, SID_WIN_EAGER_BYTES);
             const int rc = win_fit(W, b, 16384, 65536);
             if (rc != SID_OK) return rc;
+        }
+    }
+    if (W->dh_on && !W->dh_bins) {   // the depth histogram's table and its two sets of count, rows and pinned block
+        WCHECK(hipMalloc(&W->dh_bins, (size_t)SID_DH_BINS * 3 * 4));
+        WCHECK(hipMemset(W->dh_bins, 0, (size_t)SID_DH_BINS * 3 * 4));
+        for (int b = 0; b < 2; ++b) {
+            WCHECK(hipMalloc(&W->dh_cnt[b], 8));
+            WCHECK(hipMemset(W->dh_cnt[b], 0, 8));
+            WCHECK(hipMalloc(&W->dh_rows[b], (size_t)SID_DH_BINS * sizeof(sid_dh_row)));
+            WCHECK(hipHostMalloc((void**)&W->dh_eager[b], SID_DH_EAGER_BYTES, hipHostMallocDefault));
+            std::memset(W->dh_eager[b], 0, SID_DH_EAGER_BYTES);
         }
     }
     const uint64_t tiles = ((bytes + 16 + IX_TILE - 1) / IX_TILE + 1) * IX_SUB;   // 4 KiB tiles, in whole index tiles
@@ -5905,10 +6141,13 @@ void sid_chunk_release(sid_chunk_ws* W)
                     (void*)W->cx_bits, (void*)W->cx_sum, (void*)W->cx_car, (void*)W->cx_hk, (void*)W->cx_desc,
                     (void*)W->win_bits, W->win_key, (void*)W->win_hcnt, (void*)W->win_roff, (void*)W->win_cnt[0],
                     (void*)W->win_cnt[1], (void*)W->win_rows[0], (void*)W->win_rows[1], (void*)W->win_names[0],
-                    (void*)W->win_names[1], (void*)W->refb})
+                    (void*)W->win_names[1], (void*)W->refb, (void*)W->dh_bins, (void*)W->dh_cnt[0],
+                    (void*)W->dh_cnt[1], (void*)W->dh_rows[0], (void*)W->dh_rows[1]})
         if (p) (void)hipFree(p);
-    for (void* p : {(void*)W->win_h, (void*)W->win_eager[0], (void*)W->win_eager[1]})
+    for (void* p : {(void*)W->win_h, (void*)W->win_eager[0], (void*)W->win_eager[1], (void*)W->dh_eager[0],
+                    (void*)W->dh_eager[1]})
         if (p) (void)hipHostFree(p);
+    const bool dh_on = W->dh_on;
     const int select = W->select;   // (the owner's options, not the buffers')
     const sid_regtab* regions = W->regions;
     const int cx_n = W->cx_n, cx_select = W->cx_select;
@@ -5920,6 +6159,7 @@ void sid_chunk_release(sid_chunk_ws* W)
     const uint32_t depth_min = W->depth_min, depth_max = W->depth_max;
     const bool vcf = W->vcf;
     *W = sid_chunk_ws{};
+    W->dh_on = dh_on;
     W->vcf = vcf;
     W->depth = depth, W->cx_depth = cx_depth, W->depth_min = depth_min, W->depth_max = depth_max;
     W->window = window;
@@ -6073,6 +6313,10 @@ int sid_chunk_fmt_len(sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n
         const int rc = window_stage<REG_CODE, false>(S, W, c1, true, st);
         if (rc != SID_OK) return rc;
     }
+    if (W->dh_on) {   // the depth histogram, likewise
+        const int rc = depth_hist_stage<REG_CODE, false>(S, W, st);
+        if (rc != SID_OK) return rc;
+    }
     if (W->regions) {   // the sites outside the region set: dropped in the workspace's codes
         SiteArgs<sid_off_t> A = S;
         A.xm = sel_word(W->select), A.T = *W->regions;
@@ -6157,6 +6401,11 @@ int sid_chunk_local_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     if (W->window) {   // the windowed summary: on the class words (or the counts) before a mark rewrites them
         const int rc = W->cls_ready ? window_stage<REG_DENSE, false>(S, W, c1, true, st)
                                     : window_stage<REG_DENSE, true>(S, W, c1, true, st);
+        if (rc != SID_OK) return rc;
+    }
+    if (W->dh_on) {   // the depth histogram, likewise
+        const int rc = W->cls_ready ? depth_hist_stage<REG_DENSE, false>(S, W, st)
+                                    : depth_hist_stage<REG_DENSE, true>(S, W, st);
         if (rc != SID_OK) return rc;
     }
     if (nb && ctx->has_regions) {
@@ -6374,7 +6623,7 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
     if (ntp * tile_nwv(cap) > W->site_cap / 32 + 1) return SID_EINVAL;   // (never: cap >= 64)
     const bool vcf = ctx->format == SID_FORMAT_VCF;
     if ((ctx->has_variants || ctx->cx_variants || vcf) && slots && !W->refb) return SID_ESTATE;   // (a workspace not bound)
-    if ((vcf || ctx->has_regions || ctx->has_variants || ctx->has_depth || ctx->cx_on || W->window) && slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (the marking kernels' slot_tile: its exact range, as the writer's)
+    if ((vcf || ctx->has_regions || ctx->has_variants || ctx->has_depth || ctx->cx_on || W->window || W->dh_on) && slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (the marking kernels' slot_tile: its exact range, as the writer's)
     W->lens_ready = false;
     W->cls_ready = false;
     W->slot_cap = cap;
@@ -6388,6 +6637,10 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
         WCHECK(hipMemsetAsync(W->state + 4, 0xFF, sizeof(uint64_t), st));
         if (W->window) {   // (no row)
             const int rc = window_stage<REG_TILE, false>(S, W, 0, false, st);
+            if (rc != SID_OK) return rc;
+        }
+        if (W->dh_on) {   // (likewise)
+            const int rc = depth_hist_stage<REG_TILE, false>(S, W, st);
             if (rc != SID_OK) return rc;
         }
         if (ctx->cx_on) launch_context_mark<REG_TILE, false>(S, W, st);   // (the empty descriptor)
@@ -6411,6 +6664,10 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
     if (W->window) {   // the windowed summary: on the class words before a mark rewrites them
         const int rc = quad ? window_stage<REG_TILE, false>(S, W, 0, false, st)
                             : window_stage<REG_TILE, true>(S, W, 0, false, st);
+        if (rc != SID_OK) return rc;
+    }
+    if (W->dh_on) {   // the depth histogram, likewise
+        const int rc = quad ? depth_hist_stage<REG_TILE, false>(S, W, st) : depth_hist_stage<REG_TILE, true>(S, W, st);
         if (rc != SID_OK) return rc;
     }
     if (ctx->has_regions) {   // the slots outside the region set: the skip word, and their groups' sums again
@@ -6507,6 +6764,10 @@ int sid_chunk_lynch_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     S.V = V;
     if (W->window) {   // the windowed summary: on the counts before a mark zeroes them
         const int rc = window_stage<REG_LYNCH, false>(S, W, c1, true, st);
+        if (rc != SID_OK) return rc;
+    }
+    if (W->dh_on) {   // the depth histogram, likewise
+        const int rc = depth_hist_stage<REG_LYNCH, false>(S, W, st);
         if (rc != SID_OK) return rc;
     }
     if (ctx->cx_on) {   // the context: counts 0 likewise (no class or no site: the empty descriptor)
