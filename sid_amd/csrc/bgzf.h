@@ -1,7 +1,7 @@
 // bgzf.h — the BGZF decoder core: member header (RFC 1952 + SAM spec §4.1),
 // inflate (RFC 1951, complete) and CRC32, as __host__ __device__ code without
 // a HIP call.  One source for the host build (bgzf.cpp: the index, the host
-// inflate, the engine's chunk cuts; tests/asan_bgzf runs it under ASan +
+// inflate, the engine's chunk cuts; tests/asan runs it under ASan +
 // UBSan) and for the kernel (inflate.hip).
 //
 // Bounds.  The decoder reads only in[0, n) and hands its output policy only

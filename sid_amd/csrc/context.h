@@ -1,7 +1,7 @@
 // context.h — the context (sid_opts.context, --context N) on the host: the
 // mark of the host path (sid_context_mark) and the stitch of the chunks' forced
 // edge records (the engine's emit).  No HIP here: context.cpp builds into a
-// stand-alone host program (tests/asan_context).
+// stand-alone host program (tests/asan).
 //
 // A chunk is marked on the device before its neighbours' labels exist, so its
 // first and last min(N, records) records are always formatted (forced) and a

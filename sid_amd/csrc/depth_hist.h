@@ -2,7 +2,7 @@
 // FILE) on the host: the chunks' row lists, their sum in file order, the rows
 // of the host path (sid_depth_hist_host), the merge and the CSV formatter.  No
 // HIP here: depth_hist.cpp builds into a stand-alone host program
-// (tests/asan_depth_hist).
+// (tests/asan).
 //
 // A row is one depth that at least one site has.  The device bins the sites of
 // one chunk (textpath.hip, sid_depth_hist_*_kernel) and hands back the chunk's

@@ -9,7 +9,7 @@
 // end, pos being the integer the record prints (call.hpp:25).
 //
 // No HIP in this file: it builds into a stand-alone sanitized program
-// (tests/asan_regions).  The device table is uploaded by capi.cpp.
+// (tests/asan).  The device table is uploaded by capi.cpp.
 #include <algorithm>
 #include <cstring>
 #include <map>

@@ -1,6 +1,6 @@
 // regions.h — a region set (sid_regions, --regions): host object and the flat
 // table the device kernels search.  No HIP here: regions.cpp builds into a
-// stand-alone host program (tests/asan_regions).
+// stand-alone host program (tests/asan).
 #pragma once
 
 #include <cstdint>

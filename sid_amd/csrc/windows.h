@@ -1,7 +1,7 @@
 // windows.h — the windowed summary (sid_opts.window, --windows W) on the host:
 // the chunks' row lists, their stitch in file order, the rows of the host path
 // (sid_windows_host) and the CSV formatter.  No HIP here: windows.cpp builds
-// into a stand-alone host program (tests/asan_windows).
+// into a stand-alone host program (tests/asan).
 //
 // A row is a maximal run of consecutive sites with byte-equal chrom and equal
 // window index wi = floor((pos - 1) / W).  The device finds the runs of one

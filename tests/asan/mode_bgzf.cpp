@@ -1,6 +1,6 @@
-// driver.cpp — bgzf.cpp + bgzf.h under ASan + UBSan (tests/test_bgzf_asan.py).
-//
-//   bgzf_asan CORPUS
+// sid_asan bgzf CORPUS — bgzf.cpp and the decoder core bgzf.h (the code the
+// inflate kernel runs, host build: header parse, inflate, CRC32, the index)
+// (tests/test_bgzf_asan.py).
 //
 // CORPUS is a sequence of cases: a line "Z <bytes>", then <bytes> bytes of a
 // (possibly damaged) BGZF range and a newline.  Per case one line
@@ -12,19 +12,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <string>
 
-#include "sid.h"
+#include "harness.h"
 
-int main(int argc, char** argv)
+int mode_bgzf(const std::string& all)
 {
-    if (argc != 2) return 2;
-    FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
-    std::string all;
-    static char buf[1 << 16];
-    for (size_t k; (k = std::fread(buf, 1, sizeof buf, f)) > 0;) all.append(buf, k);
-    std::fclose(f);
     size_t p = 0;
     while (p < all.size()) {
         const size_t nl = all.find('\n', p);

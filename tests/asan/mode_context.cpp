@@ -1,6 +1,5 @@
-// driver.cpp — context.cpp under ASan + UBSan (tests/test_context_asan.py).
-//
-//   context_asan CORPUS
+// sid_asan context CORPUS — context.cpp: sid_context_mark and the stitch of
+// the chunks' forced edge records (tests/test_context_asan.py).
 //
 // CORPUS is a sequence of cases.
 //   "M <n> <context>", then a line of n characters ('.' a site with a record
@@ -18,20 +17,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <string>
 #include <vector>
 
 #include "context.h"
+#include "harness.h"
 
-int main(int argc, char** argv)
+int mode_context(const std::string& all)
 {
-    if (argc != 2) return 2;
-    FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
-    std::string all;
-    char buf[1 << 16];
-    for (size_t k; (k = std::fread(buf, 1, sizeof buf, f)) > 0;) all.append(buf, k);
-    std::fclose(f);
     size_t p = 0;
     auto line_end = [&]() {
         const size_t nl = all.find('\n', p);

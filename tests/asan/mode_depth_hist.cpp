@@ -1,23 +1,17 @@
-// driver.cpp — depth_hist.cpp (sid_depth_hist_host / _merge / _format) and
-// parse.cpp's sid_parse_text under ASan + UBSan (tests/test_depth_hist_asan.py).
+// sid_asan depth_hist CORPUS — depth_hist.cpp (sid_depth_hist_host / _merge /
+// _format) over parse.cpp's sites (tests/test_depth_hist_asan.py).
 //
-//   depth_hist_asan CORPUS
-//
-// CORPUS is a sequence of cases: a line "T <bytes> <threads>", then <bytes>
-// bytes of pileup text and a newline.  Per case one line "rc err_line sites"
-// (sid_parse_text; sites 0 after an error) and, when it parsed: "H <bytes>" and
-// the formatted rows of all sites (with the header) over codes that are a
-// fixed function of the site's index; "M <bytes>" and the formatted merge of
-// the rows of the two halves of the range (without the header); then "E" + the
-// statuses of the calls the ABI rejects.  The text, the codes and the format
-// buffers are exact-size heap blocks: an access past their ends is a report.
+// CORPUS: text cases (harness.h) "T <bytes> <threads>".  Per text that parsed:
+// "H <bytes>" and the formatted rows of all sites (with the header) over codes
+// that are a fixed function of the site's index; "M <bytes>" and the formatted
+// merge of the rows of the two halves of the range (without the header); then
+// "E" + the statuses of the calls the ABI rejects.
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <string>
 #include <vector>
 
-#include "sid.h"
+#include "harness.h"
 
 // the rows formatted through the sizing protocol into an exact-size block
 static int put_rows(const char* tag, const sid_depth_row* rows, size_t n, int header)
@@ -33,37 +27,9 @@ static int put_rows(const char* tag, const sid_depth_row* rows, size_t n, int he
     return 0;
 }
 
-int main(int argc, char** argv)
+int mode_depth_hist(const std::string& corpus)
 {
-    if (argc != 2) return 2;
-    FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
-    std::string all;
-    char buf[1 << 16];
-    for (size_t k; (k = std::fread(buf, 1, sizeof buf, f)) > 0;) all.append(buf, k);
-    std::fclose(f);
-    size_t p = 0;
-    while (p < all.size()) {
-        const size_t nl = all.find('\n', p);
-        if (nl == std::string::npos) return 3;
-        unsigned long long nbytes = 0;
-        int threads = 0;
-        if (std::sscanf(all.c_str() + p, "T %llu %d", &nbytes, &threads) != 2) return 3;
-        p = nl + 1;
-        if (p + nbytes + 1 > all.size()) return 3;
-        char* text = (char*)std::malloc(nbytes ? nbytes : 1);
-        std::memcpy(text, all.data() + p, nbytes);
-        p += nbytes + 1;
-        sid_sites* s = nullptr;
-        uint64_t bad = 0;
-        const int rc = sid_parse_text(text, nbytes, threads, &s, &bad);
-        std::free(text);
-        const size_t n = sid_sites_count(s);
-        std::printf("%d %llu %zu\n", rc, (unsigned long long)(rc ? bad : 0), n);
-        if (rc != SID_OK) {
-            if (s) return 4;
-            continue;
-        }
+    return text_cases(corpus, 0, [](sid_sites* s, size_t n, const int*) -> int {
         // exact-size codes: bits 0-3 the genotype, bit 7 het, now and then bit 6
         uint8_t* code = (uint8_t*)std::malloc(n ? n : 1);
         for (size_t i = 0; i < n; ++i) code[i] = (uint8_t)((i * 37u + (i >> 3)) & 0x8Fu) | (i % 5 == 0 ? 0x40u : 0u);
@@ -92,7 +58,6 @@ int main(int argc, char** argv)
         sid_depth_hist_free(b);
         sid_depth_hist_free(m);
         std::free(code);
-        sid_sites_free(s);
-    }
-    return 0;
+        return 0;
+    });
 }

@@ -1,6 +1,4 @@
-// driver.cpp — regions.cpp under ASan + UBSan (tests/test_regions_asan.py).
-//
-//   regions_asan CORPUS
+// sid_asan regions CORPUS — regions.cpp (tests/test_regions_asan.py).
 //
 // CORPUS is a sequence of cases: a line "B <bytes> <queries>", then <bytes>
 // bytes of BED text and a newline, then <queries> lines "chrom pos".  Per
@@ -13,21 +11,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <string>
 #include <vector>
 
+#include "harness.h"
 #include "regions.h"
 #include "sites.h"
 
-int main(int argc, char** argv)
+int mode_regions(const std::string& all)
 {
-    if (argc != 2) return 2;
-    FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
-    std::string all;
-    char buf[1 << 16];
-    for (size_t k; (k = std::fread(buf, 1, sizeof buf, f)) > 0;) all.append(buf, k);
-    std::fclose(f);
     size_t p = 0;
     while (p < all.size()) {
         size_t nl = all.find('\n', p);

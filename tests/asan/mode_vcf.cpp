@@ -1,26 +1,17 @@
-// driver.cpp — emit.cpp's sid_format_vcf over parse.cpp's sites under ASan +
-// UBSan (tests/test_vcf_asan.py).
+// sid_asan vcf CORPUS — emit.cpp's sid_format_vcf over parse.cpp's sites
+// (tests/test_vcf_asan.py).
 //
-//   vcf_asan CORPUS
-//
-// CORPUS is a sequence of cases: a line "T <bytes> <threads>", then <bytes>
-// bytes of pileup text and a newline.  Per case one line "rc err_line sites"
-// (sid_parse_text; sites 0 after an error) and, when it parsed, "V <bytes>", the
-// VCF lines of the sites (two calls that split the range, each sized by the
-// protocol and written into a heap block of exactly the size it asked for) and
-// a newline, then "E" + the statuses of the calls the ABI rejects.  The codes
-// and confidences are fixed functions of the site's index.  The text, the
-// arrays and the output are exact-size heap blocks: an access past their ends
-// is a report.
-#include <cmath>
+// CORPUS: text cases (harness.h) "T <bytes> <threads>".  Per text that parsed,
+// "V <bytes>", the VCF lines of the sites (two calls that split the range, each
+// sized by the protocol and written into a heap block of exactly the size it
+// asked for) and a newline, then "E" + the statuses of the calls the ABI
+// rejects.  The codes and confidences are fixed functions of the site's index.
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <limits>
 #include <string>
-#include <vector>
 
-#include "sid.h"
+#include "harness.h"
 
 static double conf(size_t k)
 {
@@ -29,37 +20,9 @@ static double conf(size_t k)
     return T[k % 9];
 }
 
-int main(int argc, char** argv)
+int mode_vcf(const std::string& corpus)
 {
-    if (argc != 2) return 2;
-    FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
-    std::string all;
-    char buf[1 << 16];
-    for (size_t k; (k = std::fread(buf, 1, sizeof buf, f)) > 0;) all.append(buf, k);
-    std::fclose(f);
-    size_t p = 0;
-    while (p < all.size()) {
-        const size_t nl = all.find('\n', p);
-        if (nl == std::string::npos) return 3;
-        unsigned long long nbytes = 0;
-        int threads = 0;
-        if (std::sscanf(all.c_str() + p, "T %llu %d", &nbytes, &threads) != 2) return 3;
-        p = nl + 1;
-        if (p + nbytes + 1 > all.size()) return 3;
-        char* text = (char*)std::malloc(nbytes ? nbytes : 1);
-        std::memcpy(text, all.data() + p, nbytes);
-        p += nbytes + 1;
-        sid_sites* s = nullptr;
-        uint64_t bad = 0;
-        const int rc = sid_parse_text(text, nbytes, threads, &s, &bad);
-        std::free(text);
-        const size_t n = sid_sites_count(s);
-        std::printf("%d %llu %zu\n", rc, (unsigned long long)(rc ? bad : 0), n);
-        if (rc != SID_OK) {
-            if (s) return 4;
-            continue;
-        }
+    return text_cases(corpus, 0, [](sid_sites* s, size_t n, const int*) -> int {
         // exact-size arrays: bits 0-3 the genotype, bit 7 het, now and then bit 6
         uint8_t* code = (uint8_t*)std::malloc(n ? n : 1);
         double* hom = (double*)std::malloc((n ? n : 1) * sizeof(double));
@@ -96,7 +59,6 @@ int main(int argc, char** argv)
         std::free(code);
         std::free(hom);
         std::free(het);
-        sid_sites_free(s);
-    }
-    return 0;
+        return 0;
+    });
 }

@@ -1,6 +1,4 @@
-// driver.cpp — windows.cpp under ASan + UBSan (tests/test_windows_asan.py).
-//
-//   windows_asan CORPUS
+// sid_asan windows CORPUS — windows.cpp (tests/test_windows_asan.py).
 //
 // CORPUS is a sequence of cases.
 //   "H <W> <sites> <begin> <end>", then per site a line "<chrom> <pos>
@@ -14,9 +12,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <string>
 #include <vector>
 
+#include "harness.h"
 #include "sites.h"
 #include "windows.h"
 
@@ -37,15 +35,8 @@ static void print_rows(int rc, sid_window* rows, size_t n)
     sid_windows_free(rows);
 }
 
-int main(int argc, char** argv)
+int mode_windows(const std::string& all)
 {
-    if (argc != 2) return 2;
-    FILE* f = std::fopen(argv[1], "rb");
-    if (!f) return 2;
-    std::string all;
-    char buf[1 << 16];
-    for (size_t k; (k = std::fread(buf, 1, sizeof buf, f)) > 0;) all.append(buf, k);
-    std::fclose(f);
     size_t p = 0;
     auto next_line = [&]() {
         size_t nl = all.find('\n', p);

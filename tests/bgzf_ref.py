@@ -225,3 +225,18 @@ def mangle(rng, z: bytes, blocks) -> bytes:
         k = coff + 18 + int(rng.integers(min(max(csize - 26, 1), 40)))
         b[k] = int(rng.integers(256))
     return bytes(b)
+
+
+def corpus(seed=31, mangled=260):
+    """[(bytes, blocks or None)]: the shape list, then damaged copies of its
+    smaller members (every kind of block, several members each): what the
+    sanitized host build (tests/test_bgzf_asan.py) and the device inflate's
+    status test (tests/test_bgzf_gpu.py) both run."""
+    all_shapes = shapes()
+    cases = [(z, b) for _, _, z, b in all_shapes]
+    rng = np.random.default_rng(seed)
+    small = [(z, b) for _, _, z, b in all_shapes if 0 < len(z) < 260_000]
+    for k in range(mangled):
+        z, b = small[k % len(small)]
+        cases.append((mangle(rng, z, b), None))
+    return cases

@@ -1,59 +1,27 @@
 """bgzf.cpp and the decoder core bgzf.h -- the member header parse, the
 inflate and the CRC32 that the device kernel runs, in their host build --
 compiled with AddressSanitizer + UndefinedBehaviorSanitizer into a stand-alone
-program (tests/asan_bgzf: its own main, nothing preloaded) and run over the
-shape list plus damaged inputs generated here with a fixed seed, each in
-exact-size heap blocks.  A sanitizer report fails the test; every status,
+program (tests/asan, mode bgzf: its own main, nothing preloaded) and run over
+the shape list plus damaged inputs generated with a fixed seed (bgzf_ref.corpus),
+each in exact-size heap blocks.  A sanitizer report fails the test; every status,
 offset and inflated byte must equal the unsanitized build/libsid.so's and
 zlib's verdict (a range whose every member zlib inflates to the right size and
 CRC is good, anything else is SID_EBGZF).  CPU only."""
-import os
-import subprocess
 import zlib
 
-import numpy as np
 import pytest
 
 import bgzf_ref as R
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-DIR = os.path.join(HERE, "asan_bgzf")
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0",
-           UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-
-
-@pytest.fixture(scope="module")
-def asan():
-    # (hipcc's clang, which the project's own build needs, links the sanitizer
-    # runtime into the program: no skip, a missing tool fails the test)
-    subprocess.run(["make", "-s", "-C", DIR], check=True)
-    return os.path.join(DIR, "_build", "bgzf_asan")
-
-
-def corpus(seed=31, mangled=260):
-    """[(bytes, blocks or None)]: the shape list, then damaged copies of its
-    smaller members (every kind of block, several members each)."""
-    shapes = R.shapes()
-    cases = [(z, b) for _, _, z, b in shapes]
-    rng = np.random.default_rng(seed)
-    small = [(z, b) for _, _, z, b in shapes if 0 < len(z) < 260_000]
-    for k in range(mangled):
-        z, b = small[k % len(small)]
-        cases.append((R.mangle(rng, z, b), None))
-    return cases
+from sanitized import asan, run   # noqa: F401 (asan: the fixture)
 
 
 def test_corpus_sanitized(sid, asan, tmp_path):
-    cases = corpus()
+    cases = R.corpus()
     p = tmp_path / "corpus.bin"
     with open(p, "wb") as f:
         for z, _ in cases:
             f.write(b"Z %d\n" % len(z) + z + b"\n")
-    r = subprocess.run([asan, str(p)], capture_output=True, env=ENV, timeout=600)
-    err = r.stderr.decode(errors="replace")
-    assert "AddressSanitizer" not in err and "runtime error" not in err and "LeakSanitizer" not in err, err[-3000:]
-    assert r.returncode == 0, err[-3000:]
-    out = r.stdout
+    out = run(asan, "bgzf", p)
     q = ngood = nbad = nmangled_good = 0
     for z, blocks in cases:
         nl = out.index(b"\n", q)

@@ -85,9 +85,8 @@ def test_device_inflate_reports_the_lowest_bad_block(sid, ctx, shapes):
     corpus clean, tests/test_bgzf_asan.py): SID_EBGZF and the lowest bad member,
     zlib's verdict member by member.  Status reporting only."""
     import torch
-    from test_bgzf_asan import corpus
     done = 0
-    for z, blocks in corpus():
+    for z, blocks in R.corpus():
         if blocks is not None or done >= 24:
             continue
         try:

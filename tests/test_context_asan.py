@@ -1,31 +1,15 @@
 """context.cpp -- sid_context_mark and the stitch of the chunks' forced edge
 records -- compiled with AddressSanitizer + UndefinedBehaviorSanitizer into a
-stand-alone program (tests/asan_context: its own main, nothing preloaded) and
-run over the cases of tests/test_context.py, plus chunks whose last record
+stand-alone program (tests/asan, mode context: its own main, nothing preloaded)
+and run over the cases of tests/test_context.py, plus chunks whose last record
 lacks its newline.  Every array it touches is an exact-size heap block.  A
 sanitizer report fails the test, and every result must equal the Python
 model's.  CPU only."""
-import os
-import subprocess
-
 import numpy as np
-import pytest
 
 from context_ref import chunk_desc, dilate
+from sanitized import asan, run   # noqa: F401 (asan: the fixture)
 from test_context import NS, cuts, mark_cases, records
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-DIR = os.path.join(HERE, "asan_context")
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0",
-           UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-
-
-@pytest.fixture(scope="module")
-def asan():
-    # (hipcc's clang, which the project's own build needs, links the sanitizer
-    # runtime into the program: no skip, a missing tool fails the test)
-    subprocess.run(["make", "-s", "-C", DIR], check=True)
-    return os.path.join(DIR, "_build", "context_asan")
 
 
 def mark_corpus():
@@ -77,9 +61,5 @@ def test_corpus_sanitized(asan, tmp_path):
     cases = mark_corpus() + stitch_corpus()
     p = tmp_path / "corpus.bin"
     p.write_bytes(b"".join(c for c, _ in cases))
-    r = subprocess.run([asan, str(p)], capture_output=True, env=ENV, timeout=600)
-    err = r.stderr.decode(errors="replace")
-    assert "AddressSanitizer" not in err and "runtime error" not in err and "LeakSanitizer" not in err, err[-3000:]
-    assert r.returncode == 0, (r.returncode, err[-3000:])
-    assert r.stdout == b"".join(w + b"\n" for _, w in cases)
+    assert run(asan, "context", p) == b"".join(w + b"\n" for _, w in cases)
     assert len(cases) >= 400

@@ -1,46 +1,20 @@
 """parse.cpp -- the host parser and sid_depth_mark -- compiled with
 AddressSanitizer + UndefinedBehaviorSanitizer into a stand-alone program
-(tests/asan_depth: its own main, nothing preloaded) and run over a corpus of
-valid and damaged pileup texts generated here with a fixed seed.  A sanitizer
-report fails the test, and every result must equal the unsanitized
+(tests/asan, mode depth: its own main, nothing preloaded) and run over a corpus
+of valid and damaged pileup texts generated here with a fixed seed.  A
+sanitizer report fails the test, and every result must equal the unsanitized
 build/libsid.so's; the marks of the valid texts also equal the Python
 restatement's.  CPU only."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
-import pytest
 
 import depth_ref as D
 import variants_ref as V
-from test_variants_asan import mangle
+from sanitized import asan, check_parse, mangle, random_text, run, write_cases   # noqa: F401 (asan: the fixture)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-DIR = os.path.join(HERE, "asan_depth")
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0",
-           UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-
-
-@pytest.fixture(scope="module")
-def asan():
-    # (hipcc's clang, which the project's own build needs, links the sanitizer
-    # runtime into the program: no skip, a missing tool fails the test)
-    subprocess.run(["make", "-s", "-C", DIR], check=True)
-    return os.path.join(DIR, "_build", "depth_asan")
-
-
-def random_text(rng, n: int) -> bytes:
-    refs = [b"A", b"C", b"G", b"T", b"a", b"c", b"g", b"t", b"N", b"n", b"R", b"*"]
-    out = []
-    for i in range(1, n + 1):
-        ref = refs[int(rng.integers(len(refs)))]
-        bases = V.bases_of(V.KINDS[int(rng.integers(len(V.KINDS)))], ref, int(rng.integers(1, 60)))
-        if rng.random() < 0.1:
-            bases += b"+2AC^].*N"
-        sep = [b"\t", b" ", b" \t "][int(rng.integers(3))]
-        out.append(V.vline(b"chr%d" % (i // 50), i, ref, bases).replace(b"\t", sep))
-    return b"".join(out)
 
 
 def corpus(seed=43):
@@ -65,21 +39,12 @@ def corpus(seed=43):
 def test_corpus_sanitized(sid, asan, tmp_path):
     cases = corpus()
     p = tmp_path / "corpus.bin"
-    with open(p, "wb") as f:
-        for text, threads, lo, hi in cases:
-            f.write(b"T %d %d %d %d\n" % (len(text), threads, lo, hi) + text + b"\n")
-    r = subprocess.run([asan, str(p)], capture_output=True, env=ENV, timeout=600)
-    err = r.stderr.decode(errors="replace")
-    assert "AddressSanitizer" not in err and "runtime error" not in err and "LeakSanitizer" not in err, err[-3000:]
-    assert r.returncode == 0, (r.returncode, err[-3000:])
-    lines = r.stdout.split(b"\n")
+    write_cases(p, cases)
+    lines = run(asan, "depth", p).split(b"\n")
     L = sid.lib()
     k = nbad = ngood = nmodel = 0
     for text, threads, lo, hi in cases:
-        h, bad = C.c_void_p(), C.c_uint64(0)
-        rc = L.sid_parse_text(text, len(text), threads, C.byref(h), C.byref(bad))
-        n = L.sid_sites_count(h)
-        assert lines[k] == b"%d %d %d" % (rc, bad.value if rc else 0, n), text[:200]
+        rc, h, n = check_parse(L, text, threads, lines[k])
         k += 1
         if rc != 0:
             nbad += 1

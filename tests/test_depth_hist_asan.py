@@ -1,35 +1,20 @@
 """depth_hist.cpp and parse.cpp -- the depth histogram's host code and the host
 parser -- compiled with AddressSanitizer + UndefinedBehaviorSanitizer into a
-stand-alone program (tests/asan_depth_hist: its own main, nothing preloaded)
+stand-alone program (tests/asan, mode depth_hist: its own main, nothing preloaded)
 and run over a corpus of valid and damaged pileup texts generated here with a
 fixed seed.  A sanitizer report fails the test, and every result must equal the
 unsanitized build/libsid.so's; the rows of the valid texts also equal the
 Python restatement's.  CPU only."""
-import ctypes as C
 import os
-import subprocess
 
 import numpy as np
-import pytest
 
 import depth_hist_ref as DH
 import depth_ref as D
 import variants_ref as V
-from test_depth_asan import random_text
-from test_variants_asan import mangle
+from sanitized import asan, check_parse, mangle, random_text, run, write_cases   # noqa: F401 (asan: the fixture)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-DIR = os.path.join(HERE, "asan_depth_hist")
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0",
-           UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-
-
-@pytest.fixture(scope="module")
-def asan():
-    # (hipcc's clang, which the project's own build needs, links the sanitizer
-    # runtime into the program: no skip, a missing tool fails the test)
-    subprocess.run(["make", "-s", "-C", DIR], check=True)
-    return os.path.join(DIR, "_build", "depth_hist_asan")
 
 
 def corpus(seed=47):
@@ -61,22 +46,13 @@ def take(blob: bytes, at: int, tag: bytes):
 def test_corpus_sanitized(sid, asan, tmp_path):
     cases = corpus()
     p = tmp_path / "corpus.bin"
-    with open(p, "wb") as f:
-        for text, threads in cases:
-            f.write(b"T %d %d\n" % (len(text), threads) + text + b"\n")
-    r = subprocess.run([asan, str(p)], capture_output=True, env=ENV, timeout=600)
-    err = r.stderr.decode(errors="replace")
-    assert "AddressSanitizer" not in err and "runtime error" not in err and "LeakSanitizer" not in err, err[-3000:]
-    assert r.returncode == 0, (r.returncode, err[-3000:])
-    blob = r.stdout
+    write_cases(p, cases)
+    blob = run(asan, "depth_hist", p)
     L = sid.lib()
     at = nbad = ngood = nmodel = 0
     for text, threads in cases:
-        h, bad = C.c_void_p(), C.c_uint64(0)
-        rc = L.sid_parse_text(text, len(text), threads, C.byref(h), C.byref(bad))
-        n = L.sid_sites_count(h)
         nl = blob.index(b"\n", at)
-        assert blob[at:nl] == b"%d %d %d" % (rc, bad.value if rc else 0, n), text[:200]
+        rc, h, n = check_parse(L, text, threads, blob[at:nl])
         at = nl + 1
         if rc != 0:
             nbad += 1

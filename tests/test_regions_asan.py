@@ -1,32 +1,17 @@
 """regions.cpp -- the BED parser, the merge, contains, the flat table and
 sid_regions_mark -- compiled with AddressSanitizer + UndefinedBehaviorSanitizer
-into a stand-alone program (tests/asan_regions: its own main, nothing
+into a stand-alone program (tests/asan, mode regions: its own main, nothing
 preloaded) and run over a corpus of valid and malformed BED texts generated
 here with a fixed seed, with contains queries against every set.  A sanitizer
 report fails the test, and every result must equal the unsanitized
 build/libsid.so's and the Python restatement's.  CPU only."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
-import pytest
 
 from regions_ref import BedError, RefSet
+from sanitized import asan, run   # noqa: F401 (asan: the fixture)
 from test_regions import BAD, GOOD, NAMES, boundary_queries, random_bed
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-DIR = os.path.join(HERE, "asan_regions")
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0",
-           UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-
-
-@pytest.fixture(scope="module")
-def asan():
-    # (hipcc's clang, which the project's own build needs, links the sanitizer
-    # runtime into the program: no skip, a missing tool fails the test)
-    subprocess.run(["make", "-s", "-C", DIR], check=True)
-    return os.path.join(DIR, "_build", "regions_asan")
 
 
 def mangle(rng, bed: bytes) -> bytes:
@@ -80,11 +65,7 @@ def test_corpus_sanitized(sid, asan, tmp_path):
         for bed, _, q in cases:
             f.write(b"B %d %d\n" % (len(bed), len(q)) + bed + b"\n")
             f.write(b"".join(b"%s %d\n" % (c, pos) for c, pos in q))
-    r = subprocess.run([asan, str(p)], capture_output=True, env=ENV, timeout=600)
-    err = r.stderr.decode(errors="replace")
-    assert "AddressSanitizer" not in err and "runtime error" not in err and "LeakSanitizer" not in err, err[-3000:]
-    assert r.returncode == 0, err[-3000:]
-    lines = r.stdout.split(b"\n")
+    lines = run(asan, "regions", p).split(b"\n")
     L = sid.lib()
     k = nbad = ngood = 0
     for bed, ref, q in cases:

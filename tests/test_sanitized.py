@@ -5,36 +5,16 @@
 pileups and the formatter's hard doubles.  A sanitizer report fails the test,
 and every output must equal the unsanitized build/libsid.so's.  CPU only."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from sanitized import asan, run   # noqa: F401 (asan: the fixture)
 from test_emit import sample_doubles
 from test_fmt import boundary_values, tie_values
 from test_parser import blank, fuzz_lines, product_line
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ASAN = os.path.join(HERE, "asan", "_build", "sid_asan")
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0",
-           UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-
-
-@pytest.fixture(scope="module")
-def asan():
-    if not shutil.which("make") or not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.skip("no hipcc / make")
-    subprocess.run(["make", "-s", "-C", os.path.join(HERE, "asan")], check=True)
-    return ASAN
-
-
-def run(asan, *args):
-    r = subprocess.run([asan] + list(args), capture_output=True, env=ENV, timeout=600)
-    err = r.stderr.decode(errors="replace")
-    assert "AddressSanitizer" not in err and "runtime error" not in err and "LeakSanitizer" not in err, err[-3000:]
-    assert r.returncode == 0, err[-3000:]
-    return r.stdout
 
 
 def expected_line(sid, line):

@@ -1,55 +1,23 @@
 """parse.cpp -- the host parser's reference bytes and sid_variants_mark --
 compiled with AddressSanitizer + UndefinedBehaviorSanitizer into a stand-alone
-program (tests/asan_variants: its own main, nothing preloaded) and run over a
-corpus of valid and damaged pileup texts generated here with a fixed seed.  A
-sanitizer report fails the test, and every result must equal the unsanitized
-build/libsid.so's; the reference bytes of the valid texts also equal the Python
-restatement's.  CPU only."""
+program (tests/asan, mode variants: its own main, nothing preloaded) and run
+over a corpus of valid and damaged pileup texts generated here with a fixed
+seed.  A sanitizer report fails the test, and every result must equal the
+unsanitized build/libsid.so's; the reference bytes of the valid texts also
+equal the Python restatement's.  CPU only."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
-import pytest
 
 import variants_ref as V
+from sanitized import asan, check_parse, mangle, run, write_cases   # noqa: F401 (asan: the fixture)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-DIR = os.path.join(HERE, "asan_variants")
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0",
-           UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-
-
-@pytest.fixture(scope="module")
-def asan():
-    # (hipcc's clang, which the project's own build needs, links the sanitizer
-    # runtime into the program: no skip, a missing tool fails the test)
-    subprocess.run(["make", "-s", "-C", DIR], check=True)
-    return os.path.join(DIR, "_build", "variants_asan")
-
-
-def mangle(rng, text: bytes) -> bytes:
-    """A pileup text damaged at random: bytes replaced, dropped or inserted, the text cut."""
-    b = bytearray(text)
-    for _ in range(int(rng.integers(1, 6))):
-        if not b:
-            break
-        k = int(rng.integers(len(b)))
-        op = int(rng.integers(5))
-        if op == 0:
-            b[k] = int(rng.integers(0, 256))
-        elif op == 1:
-            del b[k]
-        elif op == 2:
-            b[k:k] = bytes(rng.integers(0, 256, int(rng.integers(1, 4)), dtype=np.uint8))
-        elif op == 3:
-            b[k:k] = [b"\t", b" ", b"\n", b"\r", b"\0", b"^", b"+99999999999999999999", b"-3"][int(rng.integers(8))]
-        else:
-            del b[k:]
-    return bytes(b)
 
 
 def random_text(rng, n: int) -> bytes:
+    """(this module's own: reference bytes of every kind, the parser's metacharacters among them)"""
     refs = [b"A", b"C", b"G", b"T", b"a", b"c", b"g", b"t", b"N", b"n", b"R", b"*", b"^", b"+", b"."]
     out = []
     for i in range(1, n + 1):
@@ -82,21 +50,12 @@ def corpus(seed=41):
 def test_corpus_sanitized(sid, asan, tmp_path):
     cases = corpus()
     p = tmp_path / "corpus.bin"
-    with open(p, "wb") as f:
-        for text, threads in cases:
-            f.write(b"T %d %d\n" % (len(text), threads) + text + b"\n")
-    r = subprocess.run([asan, str(p)], capture_output=True, env=ENV, timeout=600)
-    err = r.stderr.decode(errors="replace")
-    assert "AddressSanitizer" not in err and "runtime error" not in err and "LeakSanitizer" not in err, err[-3000:]
-    assert r.returncode == 0, (r.returncode, err[-3000:])
-    lines = r.stdout.split(b"\n")
+    write_cases(p, cases)
+    lines = run(asan, "variants", p).split(b"\n")
     L = sid.lib()
     k = nbad = ngood = 0
     for text, threads in cases:
-        h, bad = C.c_void_p(), C.c_uint64(0)
-        rc = L.sid_parse_text(text, len(text), threads, C.byref(h), C.byref(bad))
-        n = L.sid_sites_count(h)
-        assert lines[k] == b"%d %d %d" % (rc, bad.value if rc else 0, n), text[:200]
+        rc, h, n = check_parse(L, text, threads, lines[k])
         k += 1
         if rc != 0:
             nbad += 1

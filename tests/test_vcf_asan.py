@@ -1,6 +1,6 @@
 """emit.cpp's sid_format_vcf over parse.cpp's sites, compiled with
 AddressSanitizer + UndefinedBehaviorSanitizer into a stand-alone program
-(tests/asan_vcf: its own main, nothing preloaded) and run over a corpus of
+(tests/asan, mode vcf: its own main, nothing preloaded) and run over a corpus of
 valid and damaged pileup texts generated here with a fixed seed.  A sanitizer
 report fails the test, and every result must equal the unsanitized
 build/libsid.so's; the lines of the valid texts also equal the Python
@@ -8,30 +8,16 @@ restatement's (tests/vcf_ref.py over the host CSV of the same arrays).  CPU
 only."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
-import pytest
 
 import depth_ref as D
 import variants_ref as V
 import vcf_ref as F
-from test_depth_asan import random_text
-from test_variants_asan import mangle
+from sanitized import asan, check_parse, mangle, random_text, run, write_cases   # noqa: F401 (asan: the fixture)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-DIR = os.path.join(HERE, "asan_vcf")
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0",
-           UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
 CONF = [1.0, 0.0, 1e-300, -4.94066e-324, float("nan"), float("inf"), 0.05, 123456.0, 1e22]
-
-
-@pytest.fixture(scope="module")
-def asan():
-    # (hipcc's clang, which the project's own build needs, links the sanitizer
-    # runtime into the program: no skip, a missing tool fails the test)
-    subprocess.run(["make", "-s", "-C", DIR], check=True)
-    return os.path.join(DIR, "_build", "vcf_asan")
 
 
 def corpus(seed=47):
@@ -61,14 +47,8 @@ def arrays(n: int):
 def test_corpus_sanitized(sid, asan, tmp_path):
     cases = corpus()
     p = tmp_path / "corpus.bin"
-    with open(p, "wb") as f:
-        for text, threads in cases:
-            f.write(b"T %d %d\n" % (len(text), threads) + text + b"\n")
-    r = subprocess.run([asan, str(p)], capture_output=True, env=ENV, timeout=600)
-    err = r.stderr.decode(errors="replace")
-    assert "AddressSanitizer" not in err and "runtime error" not in err and "LeakSanitizer" not in err, err[-3000:]
-    assert r.returncode == 0, (r.returncode, err[-3000:])
-    out = r.stdout
+    write_cases(p, cases)
+    out = run(asan, "vcf", p)
     L = sid.lib()
     at = nbad = ngood = nmodel = nrec = 0
 
@@ -79,10 +59,7 @@ def test_corpus_sanitized(sid, asan, tmp_path):
         return ln
 
     for text, threads in cases:
-        h, bad = C.c_void_p(), C.c_uint64(0)
-        rc = L.sid_parse_text(text, len(text), threads, C.byref(h), C.byref(bad))
-        n = L.sid_sites_count(h)
-        assert line() == b"%d %d %d" % (rc, bad.value if rc else 0, n), text[:200]
+        rc, h, n = check_parse(L, text, threads, line())
         if rc != 0:
             nbad += 1
             continue

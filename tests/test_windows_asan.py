@@ -1,33 +1,18 @@
 """windows.cpp -- the stitch of the chunks' row lists, sid_windows_host and
 sid_windows_format -- compiled with AddressSanitizer +
-UndefinedBehaviorSanitizer into a stand-alone program (tests/asan_windows: its
-own main, nothing preloaded) and run over the cases of tests/test_windows.py
-and random site sequences under every cut.  Every array it touches is an
-exact-size heap block.  A sanitizer report fails the test, and every result
-must equal the Python model's.  CPU only."""
+UndefinedBehaviorSanitizer into a stand-alone program (tests/asan, mode
+windows: its own main, nothing preloaded) and run over the cases of
+tests/test_windows.py and random site sequences under every cut.  Every array
+it touches is an exact-size heap block.  A sanitizer report fails the test, and
+every result must equal the Python model's.  CPU only."""
 import itertools
-import os
-import subprocess
 
 import numpy as np
-import pytest
 
 import windows_ref as WR
 from regions_ref import text_sites
+from sanitized import asan, run   # noqa: F401 (asan: the fixture)
 from test_windows import WS, quirks_text
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-DIR = os.path.join(HERE, "asan_windows")
-ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:abort_on_error=0",
-           UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
-
-
-@pytest.fixture(scope="module")
-def asan():
-    # (hipcc's clang, which the project's own build needs, links the sanitizer
-    # runtime into the program: no skip, a missing tool fails the test)
-    subprocess.run(["make", "-s", "-C", DIR], check=True)
-    return os.path.join(DIR, "_build", "windows_asan")
 
 
 def sequences():
@@ -92,9 +77,5 @@ def test_corpus_sanitized(asan, tmp_path):
     cases = corpus()
     p = tmp_path / "corpus.bin"
     p.write_bytes(b"".join(c for c, _ in cases))
-    r = subprocess.run([asan, str(p)], capture_output=True, env=ENV, timeout=600)
-    err = r.stderr.decode(errors="replace")
-    assert "AddressSanitizer" not in err and "runtime error" not in err and "LeakSanitizer" not in err, err[-3000:]
-    assert r.returncode == 0, (r.returncode, err[-3000:])
-    assert r.stdout == b"".join(w for _, w in cases)
+    assert run(asan, "windows", p) == b"".join(w for _, w in cases)
     assert len(cases) >= 300
