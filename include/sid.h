@@ -170,6 +170,38 @@
  *     that is reused starts every run from zero.  The switch is no field of
  *     sid_opts (whose layout stands).  Host path: sid_depth_hist_host, on the
  *     codes before any mark.
+ *   - Callable runs (sid_callable_host, sid_dtext_callable; --callable FILE
+ *     with --host-parse): the positions where a call could be made, as BED
+ *     rows beside the records.  The sites
+ *     are the non-empty lines in file order; a site's chrom, pos, depth and
+ *     record are as in the paragraphs on windows and depth bounds.  A site is
+ *     callable when (1) it prints a record in the unselected output -- its
+ *     unselected code has no SID_CODE_DROPPED; the Lynch methods print none
+ *     below coverage 4 -- (2) its depth d satisfies d >= 1 and min <= d and
+ *     (max == 0 or d <= max), with the depth bounds in force for the run
+ *     (sid_set_depth, or the host path's arguments; the default (0, 0)
+ *     leaves d >= 1, which keeps out -m local's "hom,TT" placeholder for a site without a
+ *     counted base), and (3) pos >= 1: the atoi position may be 0 or negative,
+ *     a BED start cannot.  A row is a maximal run of consecutive sites, with no
+ *     site of any kind between them in file order, that are all callable, whose
+ *     chroms are byte-equal and where each pos is the previous pos + 1,
+ *     compared in 64 bits (2^31-1 has no successor).  Its fields: chrom; start
+ *     = first pos - 1 and end = last pos (BED, as the region sets use it; end -
+ *     start is the run's sites); het, the run's het records.  No sorting and
+ *     no hashing: a repeated position, a position that goes back, a chrom that
+ *     returns or a non-callable site in between each opens a further row, as
+ *     uniq would, and two rows may abut or overlap.  The file has one line
+ *     "chrom\tstart\tend\thet\n" per row, integers in decimal, and no header
+ *     line.  The depth bounds are part of the definition (the ones that also
+ *     choose the records); otherwise, like the window rows, the rows see every site: the
+ *     selections by label, region and variant, the context and the record
+ *     format never change them, and the option changes neither the records,
+ *     bytes_out, stderr nor the exit status.  The rows do not depend on how
+ *     the sites are cut into ranges: sid_callable_join and the stitch of
+ *     per-range lists (callable.h) give the rows of the whole.  A run that
+ *     fails has no rows.  Host path: sid_callable_host, on the codes before
+ *     any mark; on the device: sid_dtext_callable over a resident shard.  The
+ *     streaming engine does not produce the rows yet.
  *   - Counts layout: profile_t (pileup.hpp:7) = 4 x uint16 {A,C,G,T} per site,
  *     array of structures, 8 bytes per site.
  */
@@ -360,6 +392,35 @@ void sid_depth_hist_free(sid_depth_row* rows);
 int sid_depth_hist_format(const sid_depth_row* rows, size_t n, int with_header, char* buf, size_t cap, size_t* len);
 int sid_depth_hist_merge(const sid_depth_row* a, size_t na, const sid_depth_row* b, size_t nb, sid_depth_row** rows,
                          size_t* n);
+
+/* -------------------------------------------------------- callable runs --
+ * The rows of the callable runs (Conventions), in file order.
+ *
+ * sid_callable_host: the rows of sites [begin, end) on the host path: code_all
+ *   are the codes before any selection marked them, (min, max) the depth
+ *   bounds.  *rows is freed with sid_callable_free.  SID_EINVAL for a range
+ *   outside the sites, a NULL pointer, or bounds that sid_depth_mark refuses.
+ * sid_callable_format: "chrom\tstart\tend\thet\n" per row, no header line.
+ *   Returns bytes written in *len, or SID_ENOMEM if cap is too small (then
+ *   *len is a sufficient size), as sid_windows_format.
+ * sid_callable_join: two row lists that are neighbours in file order (ranks
+ *   that took site ranges): a's rows, then b's, the boundary rows merged into
+ *   one only when a_open_end and b_open_start are both set -- a's last site
+ *   lies in its last row and b's first site in its first row -- the chroms are
+ *   equal and b's start == a's end.  *rows is freed with sid_callable_free. */
+typedef struct {
+    const char* chrom; /* chrom_len bytes, not terminated */
+    uint32_t chrom_len;
+    uint32_t pad;
+    int64_t start, end;
+    uint64_t het;
+} sid_callable_row;
+int sid_callable_host(const struct sid_sites* s, size_t begin, size_t end, const uint8_t* code_all /* host */, int min,
+                      int max, sid_callable_row** rows, size_t* n);
+void sid_callable_free(sid_callable_row* rows);
+int sid_callable_format(const sid_callable_row* rows, size_t n, char* buf, size_t cap, size_t* len);
+int sid_callable_join(const sid_callable_row* a, size_t na, int a_open_end, const sid_callable_row* b, size_t nb,
+                      int b_open_start, sid_callable_row** rows, size_t* n);
 
 /* ------------------------------------------------------------- contexts -- */
 typedef struct sid_ctx sid_ctx;
@@ -558,6 +619,13 @@ int sid_dtext_windows(sid_ctx* ctx, const sid_dtext* t, size_t begin, size_t end
  * Synchronises. */
 int sid_dtext_depth_hist(sid_ctx* ctx, const sid_dtext* t, size_t begin, size_t end, const uint8_t* code /* device */,
                          sid_depth_row** rows, size_t* n, void* stream);
+/* The callable runs (Conventions) of sites [begin, end) of a resident shard
+ * with the given device codes, under the context's depth bounds (sid_set_depth):
+ * the device stage over one range, the range's first site opening a row.  It
+ * needs no switch on the context.  *rows is freed with
+ * sid_callable_free.  Synchronises. */
+int sid_dtext_callable(sid_ctx* ctx, const sid_dtext* t, size_t begin, size_t end, const uint8_t* code /* device */,
+                       sid_callable_row** rows, size_t* n, void* stream);
 /* -m quality (call.cpp:291-372) over a shard parsed by a context whose method
  * is SID_METHOD_QUALITY (7 fields per line): the read bases and both quality
  * fields are read from the resident text.  snp_prior / significance_level

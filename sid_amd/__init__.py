@@ -108,6 +108,12 @@ class DepthRow(C.Structure):
                 ("depth", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class CallableRow(C.Structure):
+    """sid_callable_row: one callable run (BED start and end)."""
+    _fields_ = [("chrom", C.c_void_p), ("chrom_len", C.c_uint32), ("pad", C.c_uint32),
+                ("start", C.c_int64), ("end", C.c_int64), ("het", C.c_uint64)]
+
+
 class Placement(C.Structure):
     """sid_placement (include/sid.h): a pipeline's host placement."""
     _fields_ = [("device", C.c_int), ("gpu_numa_node", C.c_int), ("cpus", C.c_int), ("first_cpu", C.c_int),
@@ -144,6 +150,14 @@ SIGNATURES = [
     ("sid_dtext_depth_hist", _I, [_P, _P, _SZ, _SZ, _P, C.POINTER(C.POINTER(DepthRow)), C.POINTER(C.c_size_t), _P]),
     ("sid_engine_set_depth_hist", _I, [_P, _I]),
     ("sid_engine_depth_hist", _I, [_P, C.POINTER(C.POINTER(DepthRow)), C.POINTER(C.c_size_t)]),
+    ("sid_callable_host", _I, [_P, _SZ, _SZ, _P, _I, _I, C.POINTER(C.POINTER(CallableRow)), C.POINTER(C.c_size_t)]),
+    ("sid_callable_free", None, [C.POINTER(CallableRow)]),
+    ("sid_callable_format", _I, [C.POINTER(CallableRow), _SZ, _P, _SZ, C.POINTER(C.c_size_t)]),
+    ("sid_callable_join", _I, [C.POINTER(CallableRow), _SZ, _I, C.POINTER(CallableRow), _SZ, _I,
+                               C.POINTER(C.POINTER(CallableRow)), C.POINTER(C.c_size_t)]),
+    ("sid_callable_stitch_chunks", _I, [_P, _P, _P, _P, _P, _SZ, C.POINTER(C.POINTER(CallableRow)),
+                                        C.POINTER(C.c_size_t)]),
+    ("sid_dtext_callable", _I, [_P, _P, _SZ, _SZ, _P, C.POINTER(C.POINTER(CallableRow)), C.POINTER(C.c_size_t), _P]),
     ("sid_regions_from_bed", _I, [C.c_char_p, _SZ, C.POINTER(_P), C.POINTER(C.c_uint64)]),
     ("sid_regions_from_intervals", _I, [C.POINTER(C.c_char_p), _P, _P, _SZ, C.POINTER(_P)]),
     ("sid_regions_intervals", _SZ, [_P]),
@@ -492,6 +506,85 @@ def dtext_depth_hist(ctx: "Context", dtext: "DText", code_ptr, begin: int = 0, e
         return _depth_rows(rows, n.value)
     finally:
         lib().sid_depth_hist_free(rows)
+
+
+def _callable_rows(rows, n: int) -> list:
+    """sid_callable_row rows as tuples (chrom bytes, start, end, het)."""
+    return [(C.string_at(rows[k].chrom, rows[k].chrom_len) if rows[k].chrom_len else b"",
+             rows[k].start, rows[k].end, rows[k].het) for k in range(n)]
+
+
+def _callable_array(rows):
+    """(array, count, the chroms' buffers kept alive) of tuples (chrom, start, end, het)."""
+    rows = list(rows)
+    arr = (CallableRow * max(len(rows), 1))()
+    keep = []
+    for k, (chrom, start, end, het) in enumerate(rows):
+        buf = C.create_string_buffer(bytes(chrom), max(len(chrom), 1))
+        keep.append(buf)
+        arr[k] = CallableRow(C.cast(buf, C.c_void_p).value, len(chrom), 0, start, end, het)
+    return arr, len(rows), keep
+
+
+def callable_host(sites: "Sites", code_all: np.ndarray, min_depth: int = 0, max_depth: int = 0,
+                  begin: int = 0, end: int = None) -> list:
+    """sid_callable_host: the callable runs of sites [begin, end) from their
+    codes before any selection marked them, under the depth bounds."""
+    code_all = np.ascontiguousarray(code_all, np.uint8)
+    if end is None:
+        end = len(sites)
+    if code_all.size != len(sites):
+        raise SidError(1, "callable_host: one code per site")
+    rows, n = C.POINTER(CallableRow)(), C.c_size_t(0)
+    check(lib().sid_callable_host(sites.handle, begin, end, _ptr(code_all), min_depth, max_depth, C.byref(rows),
+                                  C.byref(n)), "sid_callable_host")
+    try:
+        return _callable_rows(rows, n.value)
+    finally:
+        lib().sid_callable_free(rows)
+
+
+def callable_format(rows) -> bytes:
+    """sid_callable_format over rows as callable_host / dtext_callable return them."""
+    arr, m, keep = _callable_array(rows)
+    n = C.c_size_t(0)
+    st = lib().sid_callable_format(arr, m, None, 0, C.byref(n))
+    if st not in (SID_OK, 3):
+        check(st, "sid_callable_format")
+    buf = C.create_string_buffer(max(n.value, 1))
+    check(lib().sid_callable_format(arr, m, buf, n.value, C.byref(n)), "sid_callable_format")
+    del keep
+    return buf.raw[:n.value]
+
+
+def callable_join(a, b, a_open_end: bool, b_open_start: bool) -> list:
+    """sid_callable_join: two row lists that are neighbours in file order (ranks
+    that took site ranges); the boundary rows merge only when both flags are
+    set, the chroms are equal and b's start is a's end."""
+    aa, na, ka = _callable_array(a)
+    ab, nb, kb = _callable_array(b)
+    rows, n = C.POINTER(CallableRow)(), C.c_size_t(0)
+    check(lib().sid_callable_join(aa, na, int(bool(a_open_end)), ab, nb, int(bool(b_open_start)), C.byref(rows),
+                                  C.byref(n)), "sid_callable_join")
+    del ka, kb
+    try:
+        return _callable_rows(rows, n.value)
+    finally:
+        lib().sid_callable_free(rows)
+
+
+def dtext_callable(ctx: "Context", dtext: "DText", code_ptr, begin: int = 0, end: int = None, stream=None) -> list:
+    """sid_dtext_callable: the callable stage over sites [begin, end) of a
+    resident shard with the given device codes, under the context's depth bounds."""
+    if end is None:
+        end = len(dtext)
+    rows, n = C.POINTER(CallableRow)(), C.c_size_t(0)
+    check(lib().sid_dtext_callable(ctx.h, dtext.h, begin, end, code_ptr, C.byref(rows), C.byref(n), stream),
+          "sid_dtext_callable")
+    try:
+        return _callable_rows(rows, n.value)
+    finally:
+        lib().sid_callable_free(rows)
 
 
 def device_count() -> int:

@@ -13,7 +13,20 @@
 // --chunk-bytes N, --hold-bytes N, --retain-bytes N, --host-hold N,
 // --only het|hom|all, --regions FILE, --bgzf, --context N, --windows W,
 // --windows-out FILE, --variants, --min-depth N, --max-depth N, --vcf,
-// --depth-hist FILE.
+// --depth-hist FILE, --callable FILE.
+//
+// --callable FILE (with --host-parse): beside the records, the callable runs
+// of the run (sid_callable_host, sid.h Conventions) as BED into FILE --
+// "chrom\tstart\tend\thet" a line per run, in file order, no header -- under the
+// depth bounds of --min-depth / --max-depth, written after the records; stdout,
+// stderr and the exit status are as without it, whatever --only, --regions,
+// --variants, --context and --vcf select or print.  Error texts and file
+// handling as --depth-hist's: "sid: --callable: could not open FILE" before any
+// input is read, "sid: --callable: could not write FILE"; a failing run leaves
+// no file.  The streaming engine does not produce the rows yet: without
+// --host-parse, "sid: --callable: needs --host-parse" and exit status 1 before
+// any input is read.  --stats prints callable_rows and callable_sites, the sum
+// of end - start.  Not listed by -h.
 //
 // --depth-hist FILE: beside the records, the depth histogram of the run
 // (sid_engine_set_depth_hist, sid.h Conventions) as CSV into FILE --
@@ -330,6 +343,7 @@ int main(int argc, char** argv)
     int min_depth = 0, max_depth = 0;    // --min-depth, --max-depth
     bool vcf = false;                    // --vcf
     const char* depth_hist_out = nullptr;   // --depth-hist
+    const char* callable_out = nullptr;     // --callable
     static const struct option LONG[] = {{"devices", required_argument, nullptr, 1},
                                          {"threads", required_argument, nullptr, 2},
                                          {"stats", no_argument, nullptr, 3},
@@ -349,6 +363,7 @@ int main(int argc, char** argv)
                                          {"max-depth", required_argument, nullptr, 17},
                                          {"vcf", no_argument, nullptr, 18},
                                          {"depth-hist", required_argument, nullptr, 19},
+                                         {"callable", required_argument, nullptr, 20},
                                          {nullptr, 0, nullptr, 0}};
     int flag;
     while ((flag = getopt_long(argc, argv, "E:Rhm:p:r:", LONG, nullptr)) != -1) {
@@ -465,6 +480,7 @@ int main(int argc, char** argv)
         }
         case 18: vcf = true; break;
         case 19: depth_hist_out = optarg; break;   // (given twice: the last wins)
+        case 20: callable_out = optarg; break;     // (likewise)
         default: std::exit(EXIT_FAILURE);
         }
     }
@@ -500,6 +516,23 @@ int main(int argc, char** argv)
         }
         ::close(fd);
         if (!was) ::unlink(depth_hist_out);
+    }
+    if (callable_out && (!opt.host_parse || opt.method == "quality")) {
+        // (the rows come from sid_callable_host; -m quality always takes the device text path)
+        std::fflush(stdout);
+        std::fputs("sid: --callable: needs --host-parse\n", stderr);
+        std::exit(EXIT_FAILURE);
+    }
+    if (callable_out) {   // likewise
+        const bool was = ::access(callable_out, F_OK) == 0;
+        const int fd = ::open(callable_out, O_WRONLY | O_CREAT, 0666);
+        if (fd < 0) {
+            std::fflush(stdout);
+            std::fprintf(stderr, "sid: --callable: could not open %s\n", callable_out);
+            std::exit(EXIT_FAILURE);
+        }
+        ::close(fd);
+        if (!was) ::unlink(callable_out);
     }
     if (optind >= argc) {
         std::fflush(stdout);
@@ -684,6 +717,28 @@ int main(int argc, char** argv)
             std::fprintf(stderr, "sid: --depth-hist: could not write %s\n", depth_hist_out);
             std::exit(EXIT_FAILURE);
         }
+    };
+    // --callable: the rows as BED, after the records; returns the sum of end - start
+    auto write_callable = [&](const sid_callable_row* rows, size_t nrows) {
+        size_t need = 0;
+        (void)sid_callable_format(rows, nrows, nullptr, 0, &need);
+        std::string bed(need, '\0');
+        if (need) CHECK(sid_callable_format(rows, nrows, &bed[0], need, &need), "callable");
+        const int fd = ::open(callable_out, O_WRONLY | O_CREAT | O_TRUNC, 0666);
+        size_t off = 0;
+        while (fd >= 0 && off < bed.size()) {
+            const ssize_t w = ::write(fd, bed.data() + off, bed.size() - off);
+            if (w <= 0) break;
+            off += (size_t)w;
+        }
+        if (fd < 0 || off < bed.size() || ::close(fd) != 0) {
+            std::fflush(stdout);
+            std::fprintf(stderr, "sid: --callable: could not write %s\n", callable_out);
+            std::exit(EXIT_FAILURE);
+        }
+        unsigned long long sites = 0;
+        for (size_t k = 0; k < nrows; ++k) sites += (unsigned long long)(rows[k].end - rows[k].start);
+        return sites;
     };
     // --bgzf: the bytes are not BGZF from their first member on / a member further in is truncated or corrupt
     auto bgzf_error = [&](uint64_t off, bool at_index) {
@@ -906,7 +961,8 @@ int main(int argc, char** argv)
     // ----------------------------------------------------------------- emit --
     std::fputs(HEADER, stdout);
     std::fflush(stdout);
-    size_t window_rows = 0, depth_rows = 0;
+    size_t window_rows = 0, depth_rows = 0, callable_rows = 0;
+    unsigned long long callable_sites = 0;
     {
         uint8_t* h_code = nullptr;
         double *h_hom = nullptr, *h_het = nullptr;
@@ -934,6 +990,11 @@ int main(int argc, char** argv)
         size_t ndrows = 0;
         if (depth_hist_out) CHECK(sid_depth_hist_host(sites, 0, n, h_code, &drows, &ndrows), "depth-hist");
         depth_rows = ndrows;
+        sid_callable_row* crows = nullptr;   // --callable: likewise, under the depth bounds
+        size_t ncrows = 0;
+        if (callable_out)
+            CHECK(sid_callable_host(sites, 0, n, h_code, min_depth, max_depth, &crows, &ncrows), "callable");
+        callable_rows = ncrows;
         std::vector<uint8_t> code_all;   // --context: the codes before the selections marked them
         if (opt.o.context > 0 && (opt.o.select != SID_SELECT_ALL || regions || opt.o.variants || depth_on))
             code_all.assign(h_code, h_code + n);
@@ -982,15 +1043,19 @@ int main(int argc, char** argv)
         sid_windows_free(wrows);
         if (depth_hist_out) write_depth_hist(drows, ndrows);
         sid_depth_hist_free(drows);
+        if (callable_out) callable_sites = write_callable(crows, ncrows);
+        sid_callable_free(crows);
     }
     double t3 = now();
     if (opt.stats) {
         std::fprintf(stderr,
                      "{\"sites\": %zu, \"devices\": %d, \"threads\": %d, \"path\": \"%s\", \"parse_s\": %.6f, "
                      "\"device_s\": %.6f, \"emit_s\": %.6f, \"total_s\": %.6f, \"sites_per_s\": %.1f, "
-                     "\"window_rows\": %zu, \"depth_rows\": %zu, \"main_entry_unix\": %.6f, \"main_exit_unix\": %.6f}\n",
+                     "\"window_rows\": %zu, \"depth_rows\": %zu, \"callable_rows\": %zu, \"callable_sites\": %llu, "
+                     "\"main_entry_unix\": %.6f, \"main_exit_unix\": %.6f}\n",
                      n, D, T, "host", t1 - t0, t2 - t1, t3 - t2, t3 - t0,
-                     n / std::max(1e-9, t3 - t0), window_rows, depth_rows, t_entry, unix_now());
+                     n / std::max(1e-9, t3 - t0), window_rows, depth_rows, callable_rows, callable_sites,
+                     t_entry, unix_now());
     }
     // device memory, pinned staging and mappings go with the process: freeing
     // gigabytes of HBM and pinned host memory one by one only delays the exit

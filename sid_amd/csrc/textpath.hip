@@ -45,6 +45,7 @@
 #include "vcf.h"
 #include "windows.h"
 #include "depth_hist.h"
+#include "callable.h"
 #include "local_site.h"
 
 namespace {
@@ -4975,6 +4976,249 @@ static void launch_depth_hist(const SiteArgs<Off>& A, const DhBufs& B, hipStream
     sid_depth_hist_pack_kernel<<<1, SCAN_TB, 0, st>>>(B.cnt, B.bins, B.rows, SID_DH_BINS, B.eager, B.out);
 }
 
+// --------------------------------------------------------- callable runs --
+// The callable runs (sid_dtext_callable; callable.h): the rows of a site range,
+// a row being a maximal run of consecutive sites that are all callable -- a
+// record in the unselected output, a depth >= 1 within the bounds, pos >= 1 --
+// with equal chrom and each pos the previous pos + 1.  The stage reads what the
+// window stage reads, through the same loaders (sv_site, sv_label, sv_depth,
+// sv_head; templated on the layout as that stage is, instantiated for the
+// resident shard's), and has its steps:
+//   flag   per slot: holds a site, is callable, is callable and het (wave
+//          ballots), and whether it opens a row against the previous site of
+//          its wave (the ballot's nearest lower lane, its key by shuffle): the
+//          previous site not callable, another chrom, or pos != its pos + 1 in
+//          64 bits; per wave its first and last site's key with that site's
+//          callable bit.  A wave's first site waits for the link.
+//   link   one thread per wave: the nearest earlier wave with a site and its
+//          last key against this wave's first, if that is callable; the chunk's
+//          first site, if callable, is a head.  The wave's head count, the
+//          bytes of the heads' long names, and the chunk's edge words: the
+//          first site's callable bit, and (an atomic max over the waves) the
+//          last site's.
+//   scan   exclusive scan of the waves' head counts.
+//   fill   a lane per head: its row's chrom and first pos, and the popcounts
+//          of the callable and het ballots masked to its run's lanes -- from
+//          the head up to, not including, the next lane that is a head or a
+//          site that is not callable -- added to the row; lane 0 adds the
+//          callable lanes in front of the wave's first such break to the row
+//          before.  A run of many waves costs two atomic adds a wave.  Rows
+//          from `cap` on and names past `ncap` are dropped: the caller sizes
+//          both from the counts before the fill.
+struct CallKey {
+    uint64_t c8;
+    uint64_t cb;        // clen > 8: the chrom's offset in the text
+    uint32_t clen;
+    int32_t pos;
+    uint32_t callable;
+    uint32_t pad;
+};
+static_assert(sizeof(CallKey) == 32, "two keys a wave");
+
+template <class Off>
+struct CallArgs {
+    SiteArgs<Off> A;              // the sites (A.dmin, A.dmax: the depth bounds)
+    unsigned long long* bits;     // per wave of slots: [0] sites [1] callable [2] callable and het [3] heads
+    CallKey* key;                 // per wave: [0] its first site's key, [1] its last site's
+    uint32_t* hcnt;               // per wave: its heads
+    const uint64_t* roff;         // ... and its first head's row
+    unsigned long long* cnt;      // [0] rows [1] name bytes [2] the fill's name cursor [3] the last wave with a
+                                  // site and its last site's callable bit [4] the first site's callable bit
+    sid_call_row* rows;
+    uint32_t cap;
+    char* names;
+    uint32_t ncap;
+};
+
+// whether site b, which follows site a with no site between, goes on a's run (both callable)
+__device__ __forceinline__ bool call_follows(const char* text, uint64_t len, const CallKey& a, const CallKey& b)
+{
+    if (a.c8 != b.c8 || a.clen != b.clen || (int64_t)b.pos != (int64_t)a.pos + 1) return false;
+    return a.clen <= 8 || win_name_eq(text, len, a.cb, b.cb, a.clen);
+}
+
+template <int MODE, bool OPT, class Off>
+__device__ __forceinline__ CallKey call_key(const SiteArgs<Off>& A, uint64_t i, uint32_t w, Reader& R)
+{
+    const Head h = sv_head<MODE, OPT>(A, i, w, R);
+    CallKey k;
+    k.c8 = reg_c8(R, h);
+    k.cb = h.clen > 8 ? h.cb : 0;
+    k.clen = h.clen;
+    k.pos = h.pos;
+    k.callable = 0;
+    k.pad = 0;
+    return k;
+}
+
+template <int MODE, bool OPT, class Off>
+__global__ __launch_bounds__(FTB) void sid_callable_flag_kernel(const CallArgs<Off> C)
+{
+    const SiteArgs<Off>& A = C.A;
+    const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
+    const uint64_t gw = ((uint64_t)blockIdx.x * FTB + threadIdx.x) >> 6;
+    const uint32_t lane = threadIdx.x & 63u;
+    Reader R{A.text, A.len};
+    uint32_t w;
+    const bool site = sv_site<MODE, OPT, 0>(A, i, &w);   // (the unselected parse, as the window stage)
+    bool rec = false, het = false;
+    CallKey k{0, 0, 0, 0, 0, 0};
+    if (site) {
+        sv_label<MODE>(A, i, w, &rec, &het);
+        k = call_key<MODE, OPT>(A, i, w, R);
+        const uint32_t d = sv_depth<MODE, OPT>(A, i, w);
+        k.callable = rec && d >= 1u && d >= A.dmin && (A.dmax == 0 || d <= A.dmax) && k.pos >= 1;
+    }
+    const bool ok = k.callable != 0;
+    const unsigned long long bs = __ballot(site);
+    if (!bs) {   // (wave-uniform) no site: the link passes over the wave
+        if (lane == 0) C.bits[4 * gw] = 0;
+        return;
+    }
+    const unsigned long long bc = __ballot(ok), bh = __ballot(ok && het);
+    // the previous site of the wave: the ballot's nearest lower lane
+    const unsigned long long pm = bs & ((1ull << lane) - 1ull);
+    const int src = pm ? 63 - __clzll((long long)pm) : (int)lane;
+    CallKey p;
+    p.c8 = shfl64(k.c8, src);
+    p.cb = shfl64(k.cb, src);
+    p.clen = (uint32_t)__shfl((int)k.clen, src, 64);
+    p.pos = __shfl(k.pos, src, 64);
+    const bool head = ok && pm && (!((bc >> src) & 1ull) || !call_follows(A.text, A.len, p, k));
+    const unsigned long long bd = __ballot(head);
+    const uint32_t nb = wave_sum(head && k.clen > 8 ? k.clen : 0u);
+    if (lane == 0) {
+        C.bits[4 * gw] = bs;
+        C.bits[4 * gw + 1] = bc;
+        C.bits[4 * gw + 2] = bh;
+        C.bits[4 * gw + 3] = bd;
+        if (nb) atomicAdd(C.cnt + 1, (unsigned long long)nb);
+    }
+    if (site && !pm) C.key[2 * gw] = k;
+    if (site && !(bs >> lane >> 1)) C.key[2 * gw + 1] = k;
+}
+
+__global__ __launch_bounds__(TB) void sid_callable_link_kernel(const char* __restrict__ text, uint64_t len, uint64_t nw,
+                                                               unsigned long long* __restrict__ bits,
+                                                               const CallKey* __restrict__ key,
+                                                               uint32_t* __restrict__ hcnt, unsigned long long* cnt)
+{
+    const uint64_t g = (uint64_t)blockIdx.x * TB + threadIdx.x;
+    if (g >= nw) return;
+    const unsigned long long bs = bits[4 * g];
+    uint32_t n = 0;
+    if (bs) {
+        unsigned long long hd = bits[4 * g + 3];
+        uint64_t v = g;
+        while (v > 0 && bits[4 * (v - 1)] == 0) --v;   // (the sites' ballots: no thread writes them here)
+        const CallKey a = key[2 * g];
+        if (v == 0) cnt[4] = a.callable;   // the chunk's first site
+        atomicMax(cnt + 3, (unsigned long long)((g + 1) << 1) | (unsigned long long)(key[2 * g + 1].callable & 1u));
+        if (a.callable) {
+            bool head = true;
+            if (v > 0) {
+                const CallKey b = key[2 * (v - 1) + 1];
+                head = !b.callable || !call_follows(text, len, b, a);
+            }
+            if (head) {
+                hd |= bs & (~bs + 1ull);
+                bits[4 * g + 3] = hd;
+                if (a.clen > 8) atomicAdd(cnt + 1, (unsigned long long)a.clen);
+            }
+        }
+        n = (uint32_t)__popcll(hd);
+    }
+    hcnt[g] = n;
+}
+
+template <int MODE, bool OPT, class Off>
+__global__ __launch_bounds__(FTB) void sid_callable_fill_kernel(const CallArgs<Off> C)
+{
+    const SiteArgs<Off>& A = C.A;
+    const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
+    const uint64_t gw = ((uint64_t)blockIdx.x * FTB + threadIdx.x) >> 6;
+    const uint32_t lane = threadIdx.x & 63u;
+    const unsigned long long bs = C.bits[4 * gw];
+    if (!bs) return;   // (wave-uniform)
+    const unsigned long long bc = C.bits[4 * gw + 1], bh = C.bits[4 * gw + 2], hd = C.bits[4 * gw + 3];
+    const unsigned long long brk = hd | (bs & ~bc);   // where a run ends: a head, or a site that is not callable
+    const uint64_t r0 = C.roff[gw];
+    const unsigned long long below = (1ull << lane) - 1ull;
+    if ((hd >> lane) & 1ull) {
+        const uint64_t r = r0 + (uint64_t)__popcll(hd & below);
+        const unsigned long long up = brk >> lane >> 1;
+        unsigned long long m = ~below;
+        if (up) m &= (1ull << (lane + (uint32_t)__ffsll(up))) - 1ull;   // (the next break's lane <= 63)
+        if (r < C.cap) {
+            Reader R{A.text, A.len};
+            uint32_t w;
+            (void)sv_site<MODE, OPT, 0>(A, i, &w);
+            const CallKey k = call_key<MODE, OPT>(A, i, w, R);
+            sid_call_row* row = C.rows + r;
+            uint32_t name = 0;
+            if (k.clen > 8) {
+                const unsigned long long at = atomicAdd(C.cnt + 2, (unsigned long long)k.clen);
+                name = (uint32_t)min(at, (unsigned long long)0xFFFFFFFFu);
+                if (at + k.clen <= C.ncap)
+                    for (uint32_t j = 0; j < k.clen; ++j) C.names[at + j] = (char)R.at(k.cb + j);
+            }
+            row->c8 = k.c8;
+            row->pos = k.pos;
+            row->clen = k.clen;
+            row->name = name;
+            atomicAdd(&row->sites, (uint32_t)__popcll(bc & m));
+            if (bh & m) atomicAdd(&row->het, (uint32_t)__popcll(bh & m));
+        }
+    }
+    if (lane == 0) {   // the callable sites in front of the wave's first break: the run of the row before
+        const unsigned long long m = brk ? (brk & (~brk + 1ull)) - 1ull : ~0ull;
+        if ((bc & m) && r0 > 0 && r0 - 1 < C.cap) {
+            sid_call_row* row = C.rows + (r0 - 1);
+            atomicAdd(&row->sites, (uint32_t)__popcll(bc & m));
+            if (bh & m) atomicAdd(&row->het, (uint32_t)__popcll(bh & m));
+        }
+    }
+}
+
+// the stage's device buffers for `slots` slots (sid_dtext_callable's own)
+struct CallBufs {
+    unsigned long long* bits;
+    CallKey* key;
+    uint32_t* hcnt;     // followed by the scan's workspace
+    uint64_t* roff;
+    unsigned long long* cnt;
+    sid_call_row* rows;
+    uint32_t cap;
+    char* names;
+    uint32_t ncap;
+};
+
+// flag, link and scan for A's slots: afterwards cnt[0] = the rows, cnt[1] = their long names' bytes
+template <int MODE, bool OPT, class Off>
+static void launch_callable_count(CallArgs<Off>& C, const CallBufs& B, hipStream_t st)
+{
+    C.bits = B.bits, C.key = B.key, C.hcnt = B.hcnt, C.roff = B.roff, C.cnt = B.cnt;
+    C.rows = B.rows, C.cap = B.cap, C.names = B.names, C.ncap = B.ncap;
+    const uint64_t nb = (C.A.s1 - C.A.s0 + FTB - 1) / FTB, nw = nb * (FTB / 64);
+    (void)hipMemsetAsync(B.cnt, 0, 8 * 8, st);
+    if (!nb) return;
+    sid_callable_flag_kernel<MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(C);
+    sid_callable_link_kernel<<<(unsigned)((nw + TB - 1) / TB), TB, 0, st>>>(C.A.text, C.A.len, nw, B.bits, B.key,
+                                                                            B.hcnt, B.cnt);
+    launch_scan(B.hcnt, nw, B.roff, (uint64_t*)B.cnt, nullptr,
+                (uint64_t*)((char*)B.hcnt + ((nw * 4 + 7) & ~(size_t)7)), st);
+}
+// the rows (the first B.cap of them) after launch_callable_count
+template <int MODE, bool OPT, class Off>
+static void launch_callable_fill(CallArgs<Off>& C, const CallBufs& B, hipStream_t st)
+{
+    C.rows = B.rows, C.cap = B.cap, C.names = B.names, C.ncap = B.ncap;
+    const uint64_t nb = (C.A.s1 - C.A.s0 + FTB - 1) / FTB;
+    if (!nb || !B.cap) return;
+    (void)hipMemsetAsync(B.rows, 0, (size_t)B.cap * sizeof(sid_call_row), st);
+    sid_callable_fill_kernel<MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(C);
+}
+
 // tails of the U classes (one thread each), then the dense codes' lengths
 __global__ __launch_bounds__(256) void sid_lynch_str_kernel(const uint8_t* __restrict__ pcode,
                                                            const double* __restrict__ cc, uint32_t U, CType ct,
@@ -5817,6 +6061,67 @@ extern "C" int sid_dtext_depth_hist(sid_ctx* ctx, const sid_dtext* T, size_t beg
     if (!sid_dh_sort(&ch)) return SID_ESTATE;
     sid_dh_add(&tab, ch);
     return sid_dh_export(tab, rows, n);
+}
+
+// The callable stage over a resident shard: buffers of this call's own, the rows sized from the counts, the
+// context's depth bounds.
+extern "C" int sid_dtext_callable(sid_ctx* ctx, const sid_dtext* T, size_t begin, size_t end, const uint8_t* d_code,
+                                  sid_callable_row** rows, size_t* n, void* stream)
+{
+    if (!ctx || !T || !rows || !n) return SID_EINVAL;
+    *rows = nullptr, *n = 0;
+    if (end > T->nsites || begin > end || (end > begin && !d_code)) return SID_EINVAL;
+    sid_call_table tab;
+    const size_t m = end - begin;
+    if (m == 0) return sid_call_export(tab, rows, n);
+    if (m >= (1ull << 32)) return SID_EINVAL;   // (the stage's counters are a chunk's: 32 bits)
+    TCHECK(hipSetDevice(T->device));
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t nw = win_waves(m);
+    const size_t o_key = nw * 32, o_hcnt = o_key + nw * 2 * sizeof(CallKey);
+    const size_t o_roff = (o_hcnt + win_hcnt_bytes(nw) + 15) & ~(size_t)15, o_cnt = o_roff + nw * 8;
+    char* d_ws = nullptr;
+    void* d_rows = nullptr;
+    char* d_names = nullptr;
+    int rc = SID_OK;
+    auto hip = [&](hipError_t x) {
+        if (x != hipSuccess && rc == SID_OK) rc = sid_set_hip_error(x);
+        return rc == SID_OK;
+    };
+    sid_call_chunk ch;
+    unsigned long long need[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (hip(hipMalloc(&d_ws, o_cnt + 8 * 8))) {
+        CallBufs B{(unsigned long long*)d_ws, (CallKey*)(d_ws + o_key), (uint32_t*)(d_ws + o_hcnt),
+                   (uint64_t*)(d_ws + o_roff), (unsigned long long*)(d_ws + o_cnt), nullptr, 0, nullptr, 0};
+        CallArgs<uint64_t> C{};
+        C.A = dtext_view(T, begin, end, const_cast<uint8_t*>(d_code));
+        C.A.dmin = (uint32_t)ctx->depth_min, C.A.dmax = (uint32_t)ctx->depth_max;
+        launch_callable_count<REG_CODE, false>(C, B, st);
+        hip(hipGetLastError());
+        hip(hipMemcpyAsync(need, B.cnt, sizeof need, hipMemcpyDeviceToHost, st));
+        hip(hipStreamSynchronize(st));
+        if (rc == SID_OK && need[0] >= (1ull << 32)) rc = SID_ENOMEM;
+        if (rc == SID_OK && need[0] && hip(hipMalloc(&d_rows, need[0] * sizeof(sid_call_row))) &&
+            hip(hipMalloc(&d_names, std::max<size_t>(need[1], 16)))) {
+            B.rows = (sid_call_row*)d_rows, B.cap = (uint32_t)need[0];
+            B.names = d_names, B.ncap = (uint32_t)std::min<unsigned long long>(need[1], 0xFFFFFFFFull);
+            launch_callable_fill<REG_CODE, false>(C, B, st);
+            hip(hipGetLastError());
+            ch.rows.resize(need[0]);
+            ch.names.resize(need[1]);
+            hip(hipMemcpyAsync(ch.rows.data(), d_rows, need[0] * sizeof(sid_call_row), hipMemcpyDeviceToHost, st));
+            if (need[1]) hip(hipMemcpyAsync(&ch.names[0], d_names, need[1], hipMemcpyDeviceToHost, st));
+            hip(hipStreamSynchronize(st));
+        }
+    }
+    for (void* p : {(void*)d_ws, d_rows, (void*)d_names})
+        if (p) (void)hipFree(p);
+    if (rc != SID_OK) return rc;
+    for (const sid_call_row& r : ch.rows)
+        if ((r.clen > 8 && (uint64_t)r.name + r.clen > ch.names.size()) || r.pos < 1 || r.sites == 0) return SID_ESTATE;
+    ch.edge = SID_CALL_HAS_SITE;   // (one list: its edges join nothing)
+    sid_call_stitch_push(&tab, ch);
+    return sid_call_export(tab, rows, n);
 }
 
 extern "C" int sid_format_g6(double v, char* buf, size_t cap)
