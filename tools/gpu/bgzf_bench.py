@@ -27,35 +27,27 @@ beside every difference between the two.
 
 DIR is a checkout of the parent commit built with `make` (build/libsid.so).
 Needs an MI355X; there is no CPU fallback."""
-import argparse
 import hashlib
 import json
 import os
 import statistics
 import struct
-import subprocess
 import sys
 import time
 import zlib
 from concurrent.futures import ThreadPoolExecutor
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("HSA_ENABLE_SDMA", "1")   # as bench.py: the copy engines for host<->device copies
-DEPTH, SEED, PAYLOAD = 30.0, 2, 0xff00
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import optbench as ob
+
+SEED, PAYLOAD = 2, 0xff00
 
 
 def parse_args(argv=None):
-    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("--parent", default=None, help="a built checkout of the parent commit (none: this tree only)")
-    p.add_argument("--sites", type=int, default=2_000_000)
+    p = ob.arg_parser(__file__, __doc__, sites=2_000_000, steps=10, warmup=3, step_timeout=300,
+                      process="(tree, round)")
     p.add_argument("--level", type=int, default=6)
-    p.add_argument("--steps", type=int, default=10)
-    p.add_argument("--warmup", type=int, default=3)
-    p.add_argument("--rounds", type=int, default=3)
     p.add_argument("--chunk-bytes", type=int, default=0, help="engine chunk_bytes (0: its default)")
-    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "bgzf_bench.json"))
-    p.add_argument("--step-timeout", type=int, default=300, help="seconds a (tree, round) process may take")
-    p.add_argument("--worker", default=None, metavar="TREE")
     p.add_argument("--plain-only", action="store_true")
     return p.parse_args(argv)
 
@@ -68,45 +60,24 @@ def bgzf_member(payload: bytes, level: int) -> bytes:
 
 
 def worker(a):
-    sys.path.insert(0, a.worker)
-    import numpy as np
+    sid_amd = ob.load_tree(a.worker)
     import torch
-    import sid_amd
-    assert os.path.dirname(os.path.abspath(sid_amd.__file__)).startswith(os.path.abspath(a.worker))
     n = a.sites
     dev = torch.device("cuda", 0)
-    cap = int(n * (2.72 * DEPTH + 2) * 1.03) + (64 << 20)
-    text = torch.empty(cap, dtype=torch.uint8, device=dev)
-    ctx = sid_amd.Context(0)
-    ln = ctx.synth_text_device(SEED, DEPTH, 0, n, text.data_ptr(), cap - 512)
-    torch.cuda.synchronize(dev)
-    host = text[:ln].cpu().pin_memory()
-    del text
+    ctx = sid_amd.Context(0)   # (kept for the inflate kernel)
+    ln, host = ob.make_text(SEED, ob.DEPTH, n, ctx)[1:]   # (the device copy is dropped)
     out = {"sites": n, "text_bytes": ln, "steps": a.steps, "warmup": a.warmup,
            "version": sid_amd.lib().sid_version().decode()}
 
-    def step(eng):
-        st = eng.ingest()
-        eng.estimate()
-        _, st2 = eng.emit()
-        return st, st2
-
-    def timed(eng):
+    def each_step_ms(eng):
+        """(every step's ms after the warm-up, the last step's two stats)."""
         for _ in range(a.warmup):
-            step(eng)
-        ms = []
-        for _ in range(a.steps):
-            torch.cuda.synchronize(dev)
-            t0 = time.perf_counter()
-            st, st2 = step(eng)
-            torch.cuda.synchronize(dev)
-            ms.append((time.perf_counter() - t0) * 1e3)
-        return ms, st, st2
+            ob.step(eng)
+        ms = [ob.timed(eng, 1) for _ in range(a.steps)]
+        return [m[0] for m in ms], ms[-1][1], ms[-1][2]
 
     def records_digest(eng, chunks):
-        h = hashlib.blake2b()
-        h.update(eng.records_bytes(chunks))
-        return h.hexdigest()
+        return hashlib.blake2b(eng.records_bytes(chunks)).hexdigest()
 
     def engine():
         return sid_amd.Engine(method="local", devices=1, device_sink=2, host_hold_bytes=int(n * 48) + (64 << 20),
@@ -114,7 +85,7 @@ def worker(a):
 
     eng = engine()
     eng.source_host_ptr(host.data_ptr(), ln, keep=host)
-    ms, st, st2 = timed(eng)
+    ms, st, st2 = each_step_ms(eng)
     out["plain"] = {"ms": ms, "chunks": st.chunks, "bytes_out": st2.bytes_out, "h2d_bytes": st.h2d_bytes,
                     "records": records_digest(eng, st.chunks)}
     eng.close()
@@ -156,41 +127,26 @@ def worker(a):
         # (b) the PCIe step on the compressed bytes
         eng = engine()
         eng.source_bgzf_host_ptr(zh.data_ptr(), len(z), keep=zh)
-        ms, st, st2 = timed(eng)
+        ms, st, st2 = each_step_ms(eng)
         out["bgzf"] = {"ms": ms, "chunks": st.chunks, "bytes_out": st2.bytes_out, "h2d_bytes": st.h2d_bytes,
                        "bgzf_bytes": st.bgzf_bytes, "bgzf_blocks": st.bgzf_blocks,
                        "records": records_digest(eng, st.chunks)}
         eng.close()
         out["records_equal"] = out["bgzf"]["records"] == out["plain"]["records"]
     ctx.close()
-    print("BGZF_BENCH " + json.dumps(out), flush=True)
-    return 0
-
-
-def spread(xs):
-    xs = list(xs)
-    return {"median": statistics.median(xs), "min": min(xs), "max": max(xs)}
+    return ob.emit(__file__, out)
 
 
 def main():
     a = parse_args()
     if a.worker:
         return worker(a)
-    trees = ([("parent", os.path.abspath(a.parent))] if a.parent else []) + [("this", ROOT)]
     runs = []
     for rnd in range(a.rounds):
-        for name, tree in trees:
-            cmd = [sys.executable, os.path.abspath(__file__), "--worker", tree, "--sites", str(a.sites), "--level",
-                   str(a.level), "--steps", str(a.steps), "--warmup", str(a.warmup), "--chunk-bytes",
-                   str(a.chunk_bytes)] + (["--plain-only"] if name == "parent" else [])
-            env = dict(os.environ)
-            env.pop("SID_LIB_PATH", None)   # each tree loads its own build/libsid.so
-            p = subprocess.run(cmd, capture_output=True, text=True, timeout=a.step_timeout, env=env)
-            line = [ln for ln in p.stdout.splitlines() if ln.startswith("BGZF_BENCH ")]
-            if p.returncode != 0 or not line:
-                sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
-                raise SystemExit(f"bgzf_bench: {name} failed (exit {p.returncode})")
-            r = json.loads(line[0][len("BGZF_BENCH "):])
+        for name, tree in ob.trees(a):
+            r = ob.run_worker(__file__, ["--worker", tree, "--sites", str(a.sites), "--level", str(a.level), "--steps",
+                                         str(a.steps), "--warmup", str(a.warmup), "--chunk-bytes", str(a.chunk_bytes)] +
+                              (["--plain-only"] if name == "parent" else []), a.step_timeout, name)
             r["build"], r["round"] = name, rnd
             runs.append(r)
             msg = f"round {rnd} {name}: plain {statistics.median(r['plain']['ms']):.2f} ms"
@@ -204,32 +160,26 @@ def main():
     tb = this[0]["text_bytes"]
     summary = {
         "text_bytes": tb, "bgzf_bytes": this[0]["bgzf_bytes"], "level": a.level, "ratio": this[0]["ratio"],
-        "kernel_ms": spread(statistics.median(r["kernel"]["ms"]) for r in this),
-        "pcie_bgzf_ms": spread(statistics.median(r["bgzf"]["ms"]) for r in this),
-        "pcie_plain_ms": spread(statistics.median(r["plain"]["ms"]) for r in this),
-        "zlib_inflate_ms": spread(r["zlib_inflate_ms"] for r in this),
+        "kernel_ms": ob.spread((statistics.median(r["kernel"]["ms"]) for r in this), runs=False),
+        "pcie_bgzf_ms": ob.spread((statistics.median(r["bgzf"]["ms"]) for r in this), runs=False),
+        "pcie_plain_ms": ob.spread((statistics.median(r["plain"]["ms"]) for r in this), runs=False),
+        "zlib_inflate_ms": ob.spread((r["zlib_inflate_ms"] for r in this), runs=False),
         "records_equal": all(r["records_equal"] for r in this),
     }
     summary["kernel_text_GBps"] = tb / (summary["kernel_ms"]["median"] * 1e-3) / 1e9
     summary["pcie_bgzf_sites_per_s"] = a.sites / (summary["pcie_bgzf_ms"]["median"] * 1e-3)
     summary["pcie_plain_sites_per_s"] = a.sites / (summary["pcie_plain_ms"]["median"] * 1e-3)
     if par:
-        summary["parent_pcie_plain_ms"] = spread(statistics.median(r["plain"]["ms"]) for r in par)
-    doc = {"tool": "tools/gpu/bgzf_bench.py", "sites": a.sites, "steps": a.steps, "warmup": a.warmup,
-           "rounds": a.rounds, "depth": DEPTH, "chunk_bytes": a.chunk_bytes,
+        summary["parent_pcie_plain_ms"] = ob.spread((statistics.median(r["plain"]["ms"]) for r in par), runs=False)
+    doc = {**ob.doc_head(__file__, a), "depth": ob.DEPTH, "chunk_bytes": a.chunk_bytes,
            "note": "ms per step, wall time; every figure of a process is the median of its steps, its spread the "
                    "min .. max of those medians over the rounds.  kernel: sid_bgzf_inflate_device on the file in "
                    "HBM (table upload, launch and sync included).  pcie: pinned host bytes in, records into the "
                    "pinned host arena (device_sink 2).  zlib: one host core inflating the same members.  parent / "
                    "this tree alternate within every round",
            "summary": summary, "runs": runs}
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
     print(json.dumps(summary))
-    print("wrote", a.out)
-    return 0
+    return ob.write_doc(a, doc)
 
 
 if __name__ == "__main__":

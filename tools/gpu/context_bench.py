@@ -34,43 +34,22 @@ indices of the whole run, cut at the chunks' ends.
 
 DIR is a checkout of the parent commit built with `make` (build/libsid.so).
 Needs an MI355X; there is no CPU fallback."""
-import argparse
 import hashlib
-import json
 import os
-import statistics
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("HSA_ENABLE_SDMA", "1")   # as bench.py: the copy engines for host<->device copies
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import optbench as ob
+from optbench import rng
 
-CONFIGS = {"C2": dict(method="local", R=False, seed=2), "C3": dict(method="likelihood_ratio", R=True, seed=3)}
-DEPTH = 30.0
 N = 2
 SELS = {"none": {}, "het": {"select": "het"}, "hetctx": {"select": "het", "context": N}}
-STAGES = ("index", "parse", "call", "hist", "fmt_len", "fmt_write")
 
 
 def parse_args(argv=None):
-    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("--parent", default=None, help="a built checkout of the parent commit (none: this tree only)")
-    p.add_argument("--parent-all", action="store_true",
-                   help="the parent runs every selection this tree runs (a parent that has them all)")
-    p.add_argument("--sites", type=int, default=50_000_000)
-    p.add_argument("--steps", type=int, default=8)
-    p.add_argument("--warmup", type=int, default=2)
-    p.add_argument("--rounds", type=int, default=3)
-    p.add_argument("--configs", default="C2,C3")
-    p.add_argument("--no-check", action="store_true", help="skip the comparison of the records")
-    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "context_bench.json"))
-    p.add_argument("--step-timeout", type=int, default=600, help="seconds a (tree, config) process may take")
-    # one (tree, config) process
-    p.add_argument("--worker", default=None, metavar="TREE")
-    p.add_argument("--config", default="C2")
-    p.add_argument("--sels", default="none")
-    p.add_argument("--check", action="store_true")
+    p = ob.arg_parser(__file__, __doc__, sets=("--sels", "none"))
+    ob.add_parent_all(p)
+    ob.add_check_args(p, "comparison of the records")
     return p.parse_args(argv)
 
 
@@ -108,78 +87,19 @@ def model_digests(chunks, n, np):
 
 
 def worker(a):
-    sys.path.insert(0, a.worker)
-    import ctypes as C
     import numpy as np
-    import torch
-    import sid_amd
-    assert os.path.dirname(os.path.abspath(sid_amd.__file__)).startswith(os.path.abspath(a.worker))
-    cfg = CONFIGS[a.config]
-    n = a.sites
-    dev = torch.device("cuda", 0)
-    cap = int(n * (2.72 * DEPTH + 2) * 1.03) + (64 << 20)
-    text = torch.empty(cap, dtype=torch.uint8, device=dev)
-    ctx = sid_amd.Context(0)
-    ln = ctx.synth_text_device(cfg["seed"], DEPTH, 0, n, text.data_ptr(), cap - 512)
-    text[ln:ln + 512].zero_()
-    torch.cuda.synchronize(dev)
-    ctx.close()
-    host = text[:ln].cpu().pin_memory()
-    out = {"config": a.config, "sites": n, "text_bytes": ln, "steps": a.steps, "warmup": a.warmup,
-           "version": sid_amd.lib().sid_version().decode(), "sels": {}}
-
-    def step(eng):
-        st = eng.ingest()
-        eng.estimate()
-        _, st2 = eng.emit()
-        return st, st2
-
-    def timed(eng, steps):
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            st, st2 = step(eng)
-        torch.cuda.synchronize(dev)
-        return (time.perf_counter() - t0) / steps * 1e3, st, st2
-
+    cfg, n, text, ln, host, out = ob.worker_start(a, "sels")
     digests, model = {}, None
     for name in a.sels.split(","):
         kw = SELS[name]
-        r = {}
-        eng = sid_amd.Engine(method=cfg["method"], estimate_prior=cfg["R"], devices=1, device_sink=1, **kw)
-        eng.source_device_text(text.data_ptr(), ln, keep=text)
-        eng.profile(False)
-        for _ in range(a.warmup):
-            step(eng)
-        r["device_ms_per_step"], st, st2 = timed(eng, a.steps)
-        eng.profile(True)
-        step(eng)
-        eng.profile_read()
-        for _ in range(a.steps):
-            step(eng)
-        prof = eng.profile_read()
-        eng.profile(False)
-        eng.close()
-        r["device_stages_ms"] = {k[:-3]: v / a.steps for k, v in prof.items() if k.endswith("_ms")}
-        r["device_bytes_out"] = st2.bytes_out
-        r["chunks_tiled"] = st.chunks_tiled
-        eng = sid_amd.Engine(method=cfg["method"], estimate_prior=cfg["R"], devices=1, device_sink=2,
-                             host_hold_bytes=int(n * 48) + (64 << 20), **kw)
-        eng.source_host_ptr(host.data_ptr(), ln, keep=host)
-        for _ in range(a.warmup):
-            step(eng)
-        r["pcie_ms_per_step"], st, st2 = timed(eng, a.steps)
-        r["pcie_bytes_out"] = st2.bytes_out
-        r["pcie_chunks"] = st.chunks
+        r = ob.device_pass(a, cfg, text, ln, kw, omit=("device_chunks_per_step", "tile_overflows"))
+        eng, st = ob.pcie_pass(a, cfg, host, ln, n, kw, r)
         if a.check and name in ("none", "hetctx"):
-            raws = []
-            for j in range(st.chunks):
-                p, m = eng.records(j)
-                raws.append(C.string_at(p, m) if m else b"")
+            raws = list(ob.record_chunks(eng, st.chunks))
             if name == "none":
                 model = model_digests(raws, N, np)
             else:
-                digests[name] = [(len(x), hashlib.blake2b(x).hexdigest()) for x in raws]
+                digests[name] = [ob.chunk_digest(x) for x in raws]
             del raws
         eng.close()
         out["sels"][name] = r
@@ -191,33 +111,20 @@ def worker(a):
                "bytes_out_stat": out["sels"]["hetctx"]["pcie_bytes_out"],
                "device_sink_bytes_out_stat": out["sels"]["hetctx"]["device_bytes_out"]}
         if want != got:
-            chk["first_bad_chunk"] = next((j for j, (w, g) in enumerate(zip(want, got)) if w != g), min(len(want), len(got)))
+            chk["first_bad_chunk"] = ob.first_bad(want, got)
         out["records_check"] = chk
-    print("CONTEXT_BENCH " + json.dumps(out), flush=True)
-    return 0
+    return ob.emit(__file__, out)
 
 
 # ------------------------------------------------------------------ driver --
-def spread(xs):
-    xs = list(xs)
-    return {"median": statistics.median(xs), "min": min(xs), "max": max(xs), "runs": xs}
-
-
 def comparisons(summary):
-    def rng(e, k):
-        return [round(e[k]["min"], 3), round(e[k]["max"], 3)]
-
     out = {}
-    keys = ["device_ms_per_step", "pcie_ms_per_step"] + [s + "_ms" for s in STAGES]
     for config, c in summary.items():
         if "parent_none" not in c:
             continue
         o = {}
         for s in ("none", "het"):
-            p, t = c["parent_" + s], c["this_" + s]
-            o[f"unchanged_without_the_option_{s}"] = {
-                "met": all(rng(t, k)[0] <= rng(p, k)[1] and rng(p, k)[0] <= rng(t, k)[1] for k in keys),
-                "this": {k: rng(t, k) for k in keys}, "parent": {k: rng(p, k) for k in keys}}
+            o[f"unchanged_without_the_option_{s}"] = ob.within_parent_spread(c["this_" + s], c["parent_" + s])
         x, h, u, pu = c["this_hetctx"], c["this_het"], c["this_none"], c["parent_none"]
         o["context_cost"] = {
             "context_ms": rng(x, "context_ms"),
@@ -238,77 +145,36 @@ def comparisons(summary):
     return out
 
 
+def derive(r, config):
+    stage = "parse" if config == "C2" else "fmt_len"   # the stage that holds the marking kernels
+    if "hetctx" in r["sels"]:
+        r["sels"]["hetctx"]["context_ms"] = (r["sels"]["hetctx"]["device_stages_ms"][stage] -
+                                             r["sels"]["none"]["device_stages_ms"][stage])
+
+
+def entry(ser, s):
+    e = ob.summary_entry(ser)
+    if s == "hetctx":
+        e["context_ms"] = ob.spread(ser(lambda v: v["context_ms"]))
+    return e
+
+
 def main():
     a = parse_args()
     if a.worker:
         return worker(a)
-    runs = []
-    trees = ([("parent", os.path.abspath(a.parent))] if a.parent else []) + [("this", ROOT)]
-    for rnd in range(a.rounds):
-        for config in a.configs.split(","):
-            for name, tree in trees:
-                check = name == "this" and rnd == 0 and not a.no_check
-                cmd = [sys.executable, os.path.abspath(__file__), "--worker", tree, "--config", config, "--sites",
-                       str(a.sites), "--steps", str(a.steps), "--warmup", str(a.warmup), "--sels",
-                       "none,het,hetctx" if name == "this" or a.parent_all else "none,het"] + (["--check"] if check else [])
-                env = dict(os.environ)
-                env.pop("SID_LIB_PATH", None)   # each tree loads its own build/libsid.so
-                p = subprocess.run(cmd, capture_output=True, text=True, timeout=a.step_timeout, env=env)
-                line = [ln for ln in p.stdout.splitlines() if ln.startswith("CONTEXT_BENCH ")]
-                if p.returncode != 0 or not line:
-                    sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
-                    raise SystemExit(f"context_bench: {name} {config} failed (exit {p.returncode})")
-                r = json.loads(line[0][len("CONTEXT_BENCH "):])
-                r["build"], r["round"] = name, rnd
-                stage = "parse" if config == "C2" else "fmt_len"   # the stage that holds the marking kernels
-                if "hetctx" in r["sels"]:
-                    r["sels"]["hetctx"]["context_ms"] = (r["sels"]["hetctx"]["device_stages_ms"][stage] -
-                                                         r["sels"]["none"]["device_stages_ms"][stage])
-                runs.append(r)
-                print(f"round {rnd} {config} {name}: " + ", ".join(
-                    f"{s}: device {v['device_ms_per_step']:.2f} ms (parse {v['device_stages_ms']['parse']:.3f}, "
-                    f"len {v['device_stages_ms']['fmt_len']:.3f}, write {v['device_stages_ms']['fmt_write']:.3f}), "
-                    f"pcie {v['pcie_ms_per_step']:.1f} ms, {v['pcie_bytes_out']} B"
-                    for s, v in r["sels"].items()) + (f"; check {r['records_check']['equal']}" if "records_check" in r else ""),
-                      flush=True)
-
-    def series(build, config, s, get):
-        return [get(r["sels"][s]) for r in runs if r["build"] == build and r["config"] == config and s in r["sels"]]
-
-    summary = {}
-    for config in a.configs.split(","):
-        c = {}
-        for build, _ in trees:
-            for s in SELS:
-                if not series(build, config, s, lambda v: 0):
-                    continue
-                e = {"device_ms_per_step": spread(series(build, config, s, lambda v: v["device_ms_per_step"])),
-                     "pcie_ms_per_step": spread(series(build, config, s, lambda v: v["pcie_ms_per_step"])),
-                     "bytes_out": series(build, config, s, lambda v: v["pcie_bytes_out"])[0]}
-                for stg in STAGES:
-                    e[stg + "_ms"] = spread(series(build, config, s, lambda v: v["device_stages_ms"][stg]))
-                if s == "hetctx":
-                    e["context_ms"] = spread(series(build, config, s, lambda v: v["context_ms"]))
-                c[f"{build}_{s}"] = e
-        checks = [r["records_check"] for r in runs if r["config"] == config and "records_check" in r]
-        if checks:
-            c["records_check"] = checks[0]
-        summary[config] = c
-    doc = {"tool": "tools/gpu/context_bench.py", "sites": a.sites, "steps": a.steps, "warmup": a.warmup,
-           "rounds": a.rounds, "depth": DEPTH, "context": N,
-           "note": "ms per step; device: text and records in HBM (device_sink 1), stages from HIP event pairs in a "
-                   "profiled run of the same steps; pcie: pinned host text in, records into the pinned host arena "
-                   "(device_sink 2), wall time.  context_ms: the stage that holds the marking kernels (C2: parse, "
-                   "the tile parse; C3: fmt_len) with --only het --context 2 minus the unselected run's, same "
-                   "process.  parent / this tree alternate within every round; the spread of a figure is its "
-                   "min .. max over the rounds",
-           "comparisons": comparisons(summary), "summary": summary, "runs": runs}
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
-    print("wrote", a.out)
-    return 0
+    trees = ob.trees(a)
+    runs, _ = ob.run_rounds(
+        a, __file__, [(name, tree, ["--sels", "none,het,hetctx" if name == "this" or a.parent_all else "none,het"],
+                       name == "this", None) for name, tree in trees],
+        derive, progress=lambda r: ", ".join(f"{s}: " + ob.set_line(v) for s, v in r["sels"].items()) +
+        ob.check_note(r, "records_check"))
+    summary = ob.summarise(a, runs, "sels", [b for b, _ in trees], SELS, entry, check_key="records_check")
+    return ob.write_doc(a, {
+        **ob.doc_head(__file__, a), "depth": ob.DEPTH, "context": N,
+        "note": ob.NOTE + "context_ms: the stage that holds the marking kernels (C2: parse, the tile parse; C3: "
+                "fmt_len) with --only het --context 2 minus the unselected run's, same process.  " + ob.NOTE_ROUNDS,
+        "comparisons": comparisons(summary), "summary": summary, "runs": runs})
 
 
 if __name__ == "__main__":

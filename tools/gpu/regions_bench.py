@@ -36,51 +36,31 @@ chunk by chunk (the chunks are cut by input bytes: the same in every run).
 
 DIR is a checkout of the parent commit built with `make` (build/libsid.so).
 Needs an MI355X; there is no CPU fallback."""
-import argparse
 import hashlib
-import json
 import os
-import statistics
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("HSA_ENABLE_SDMA", "1")   # as bench.py: the copy engines for host<->device copies
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import optbench as ob
+from optbench import rng
 
-CONFIGS = {"C2": dict(method="local", R=False, seed=2), "C3": dict(method="likelihood_ratio", R=True, seed=3)}
-DEPTH = 30.0
 PERIOD, LEN_LO, LEN_HI, SET_SEED = 12_000, 200, 400, 1234
 
 
 def parse_args(argv=None):
-    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("--parent", default=None, help="a built checkout of the parent commit (none: this tree only)")
-    p.add_argument("--parent-all", action="store_true",
-                   help="the parent runs every selection this tree runs (a parent that has them all)")
-    p.add_argument("--sites", type=int, default=50_000_000)
-    p.add_argument("--steps", type=int, default=8)
-    p.add_argument("--warmup", type=int, default=2)
-    p.add_argument("--rounds", type=int, default=3)
-    p.add_argument("--configs", default="C2,C3")
-    p.add_argument("--no-check", action="store_true", help="skip the comparison of the filtered records")
-    p.add_argument("--out", default=os.path.join(ROOT, "profiles", "regions_bench.json"))
-    p.add_argument("--step-timeout", type=int, default=600, help="seconds a (tree, config) process may take")
-    # one (tree, config) process
-    p.add_argument("--worker", default=None, metavar="TREE")
-    p.add_argument("--config", default="C2")
-    p.add_argument("--sets", default="none")
-    p.add_argument("--check", action="store_true")
+    p = ob.arg_parser(__file__, __doc__, sets=("--sets", "none"))
+    ob.add_parent_all(p)
+    ob.add_check_args(p, "comparison of the filtered records")
     return p.parse_args(argv)
 
 
 # ------------------------------------------------------------------ worker --
 def sparse_intervals(n, np):
     """(starts, ends), BED convention, over positions 1..n: one interval per PERIOD positions."""
-    rng = np.random.default_rng(SET_SEED)
+    gen = np.random.default_rng(SET_SEED)
     k = np.arange(0, n, PERIOD, dtype=np.int64)
-    s = k + rng.integers(0, PERIOD - LEN_HI, k.size)
-    e = np.minimum(s + rng.integers(LEN_LO, LEN_HI + 1, k.size), n)
+    s = np.minimum(k + gen.integers(0, PERIOD - LEN_HI, k.size), n - 1)   # (the last one starts inside the text)
+    e = np.minimum(s + gen.integers(LEN_LO, LEN_HI + 1, k.size), n)
     return s, e
 
 
@@ -106,24 +86,9 @@ def filtered_digest(raw, starts, ends, np):
 
 
 def worker(a):
-    sys.path.insert(0, a.worker)
     import numpy as np
-    import torch
+    cfg, n, text, ln, host, out = ob.worker_start(a, "sets")
     import sid_amd
-    assert os.path.dirname(os.path.abspath(sid_amd.__file__)).startswith(os.path.abspath(a.worker))
-    cfg = CONFIGS[a.config]
-    n = a.sites
-    dev = torch.device("cuda", 0)
-    cap = int(n * (2.72 * DEPTH + 2) * 1.03) + (64 << 20)
-    text = torch.empty(cap, dtype=torch.uint8, device=dev)
-    ctx = sid_amd.Context(0)
-    ln = ctx.synth_text_device(cfg["seed"], DEPTH, 0, n, text.data_ptr(), cap - 512)
-    text[ln:ln + 512].zero_()
-    torch.cuda.synchronize(dev)
-    ctx.close()
-    host = text[:ln].cpu().pin_memory()
-    out = {"config": a.config, "sites": n, "text_bytes": ln, "steps": a.steps, "warmup": a.warmup,
-           "version": sid_amd.lib().sid_version().decode(), "sets": {}}
     sp_s, sp_e = sparse_intervals(n, np)
 
     def make_set(name):
@@ -133,65 +98,15 @@ def worker(a):
             return sid_amd.Regions(b"chr1\n")
         return sid_amd.Regions(b"".join(b"chr1\t%d\t%d\n" % (s, e) for s, e in zip(sp_s.tolist(), sp_e.tolist())))
 
-    def step(eng):
-        st = eng.ingest()
-        eng.estimate()
-        _, st2 = eng.emit()
-        return st, st2
-
-    def timed(eng, steps):
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            st, st2 = step(eng)
-        torch.cuda.synchronize(dev)
-        return (time.perf_counter() - t0) / steps * 1e3, st, st2
-
     digests = {}
     for name in a.sets.split(","):
         rg = make_set(name)
         kw = {} if rg is None else {"regions": rg}
-        r = {"intervals": 0 if rg is None else len(rg)}
-        # text and records in HBM: the kernels, per stage
-        eng = sid_amd.Engine(method=cfg["method"], estimate_prior=cfg["R"], devices=1, device_sink=1, **kw)
-        eng.source_device_text(text.data_ptr(), ln, keep=text)
-        eng.profile(False)
-        for _ in range(a.warmup):
-            step(eng)
-        r["device_ms_per_step"], st, st2 = timed(eng, a.steps)
-        eng.profile(True)
-        step(eng)
-        eng.profile_read()
-        for _ in range(a.steps):
-            step(eng)
-        prof = eng.profile_read()
-        eng.profile(False)
-        eng.close()
-        r["device_stages_ms"] = {k[:-3]: v / a.steps for k, v in prof.items() if k.endswith("_ms")}
-        r["device_chunks_per_step"] = prof["chunks"] / a.steps
-        r["device_bytes_out"] = st2.bytes_out
-        r["chunks_tiled"] = st.chunks_tiled
-        r["tile_overflows"] = st.tile_overflows
-        # the PCIe path: host text in, records into the pinned host arena
-        eng = sid_amd.Engine(method=cfg["method"], estimate_prior=cfg["R"], devices=1, device_sink=2,
-                             host_hold_bytes=int(n * 48) + (64 << 20), **kw)
-        eng.source_host_ptr(host.data_ptr(), ln, keep=host)
-        for _ in range(a.warmup):
-            step(eng)
-        r["pcie_ms_per_step"], st, st2 = timed(eng, a.steps)
-        r["pcie_bytes_out"] = st2.bytes_out
-        r["pcie_chunks"] = st.chunks
+        r = {"intervals": 0 if rg is None else len(rg), **ob.device_pass(a, cfg, text, ln, kw)}
+        eng, st = ob.pcie_pass(a, cfg, host, ln, n, kw, r)
         if a.check:
-            import ctypes as C
-            d = []
-            for j in range(st.chunks):
-                p, m = eng.records(j)
-                raw = C.string_at(p, m) if m else b""
-                if name == "none":
-                    d.append({"sparse": filtered_digest(raw, sp_s, sp_e, np), "whole": (m, hashlib.blake2b(raw).hexdigest())})
-                else:
-                    d.append((m, hashlib.blake2b(raw).hexdigest()))
-            digests[name] = d
+            digests[name] = [{"sparse": filtered_digest(raw, sp_s, sp_e, np), "whole": ob.chunk_digest(raw)}
+                             if name == "none" else ob.chunk_digest(raw) for raw in ob.record_chunks(eng, st.chunks)]
         eng.close()
         if rg is not None:
             rg.close()
@@ -205,23 +120,14 @@ def worker(a):
                 chk[name] = {"equal": want == got, "chunks": len(got), "bytes": sum(x[0] for x in got),
                              "records_all_bytes": out["sets"]["none"]["pcie_bytes_out"]}
                 if want != got:
-                    chk[name]["first_bad_chunk"] = next(j for j, (w, g) in enumerate(zip(want, got)) if w != g)
+                    chk[name]["first_bad_chunk"] = ob.first_bad(want, got)
         out["filtered_bytes_check"] = chk
-    print("REGIONS_BENCH " + json.dumps(out), flush=True)
-    return 0
+    return ob.emit(__file__, out)
 
 
 # ------------------------------------------------------------------ driver --
-def spread(xs):
-    xs = list(xs)
-    return {"median": statistics.median(xs), "min": min(xs), "max": max(xs), "runs": xs}
-
-
 def comparisons(summary):
     """The four comparisons against the parent build, each stated with its ranges (min .. max over the rounds)."""
-    def rng(e, k):
-        return [round(e[k]["min"], 3), round(e[k]["max"], 3)]
-
     def overlap_or_lower(x, y):   # x not above y: the ranges overlap, or x lies below
         return x[0] <= y[1]
 
@@ -231,9 +137,7 @@ def comparisons(summary):
             continue
         p, n, s, w = c["parent_none"], c["this_none"], c["this_sparse"], c["this_whole"]
         keys = ["device_ms_per_step", "pcie_ms_per_step", "parse_ms", "fmt_len_ms", "fmt_write_ms"]
-        o = {"1_no_set_within_parent_spread": {
-                 "met": all(rng(n, k)[0] <= rng(p, k)[1] and rng(p, k)[0] <= rng(n, k)[1] for k in keys),
-                 "this": {k: rng(n, k) for k in keys}, "parent": {k: rng(p, k) for k in keys}},
+        o = {"1_no_set_within_parent_spread": ob.within_parent_spread(n, p, keys),
              "2_sparse_device_path_not_slower": {
                  "met": overlap_or_lower(rng(s, "device_ms_per_step"), rng(p, "device_ms_per_step")),
                  "this_sparse": rng(s, "device_ms_per_step"), "parent": rng(p, "device_ms_per_step"),
@@ -253,78 +157,38 @@ def comparisons(summary):
     return out
 
 
+def derive(r, config):
+    stage = "parse" if config == "C2" else "fmt_len"   # the stage that holds the region kernel
+    for s, v in r["sets"].items():
+        if s != "none":
+            v["region_ms"] = v["device_stages_ms"][stage] - r["sets"]["none"]["device_stages_ms"][stage]
+
+
+def entry(ser, s):
+    e = ob.summary_entry(ser, mid={"intervals": ser(lambda v: v["intervals"])[0]})
+    if s != "none":
+        e["region_ms"] = ob.spread(ser(lambda v: v["region_ms"]))
+    return e
+
+
 def main():
     a = parse_args()
     if a.worker:
         return worker(a)
-    runs = []
-    trees = ([("parent", os.path.abspath(a.parent))] if a.parent else []) + [("this", ROOT)]
-    for rnd in range(a.rounds):
-        for config in a.configs.split(","):
-            for name, tree in trees:
-                check = name == "this" and rnd == 0 and not a.no_check
-                cmd = [sys.executable, os.path.abspath(__file__), "--worker", tree, "--config", config, "--sites",
-                       str(a.sites), "--steps", str(a.steps), "--warmup", str(a.warmup), "--sets",
-                       "none,sparse,whole" if name == "this" or a.parent_all else "none"] + (["--check"] if check else [])
-                env = dict(os.environ)
-                env.pop("SID_LIB_PATH", None)   # each tree loads its own build/libsid.so
-                p = subprocess.run(cmd, capture_output=True, text=True, timeout=a.step_timeout, env=env)
-                line = [ln for ln in p.stdout.splitlines() if ln.startswith("REGIONS_BENCH ")]
-                if p.returncode != 0 or not line:
-                    sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
-                    raise SystemExit(f"regions_bench: {name} {config} failed (exit {p.returncode})")
-                r = json.loads(line[0][len("REGIONS_BENCH "):])
-                r["build"], r["round"] = name, rnd
-                stage = "parse" if config == "C2" else "fmt_len"   # the stage that holds the region kernel
-                for s, v in r["sets"].items():
-                    if s != "none":
-                        v["region_ms"] = v["device_stages_ms"][stage] - r["sets"]["none"]["device_stages_ms"][stage]
-                runs.append(r)
-                print(f"round {rnd} {config} {name}: " + ", ".join(
-                    f"{s}: device {v['device_ms_per_step']:.2f} ms (parse {v['device_stages_ms']['parse']:.3f}, "
-                    f"len {v['device_stages_ms']['fmt_len']:.3f}, write {v['device_stages_ms']['fmt_write']:.3f}), "
-                    f"pcie {v['pcie_ms_per_step']:.1f} ms, {v['pcie_bytes_out']} B"
-                    for s, v in r["sets"].items()), flush=True)
-
-    def series(build, config, s, get):
-        return [get(r["sets"][s]) for r in runs if r["build"] == build and r["config"] == config and s in r["sets"]]
-
-    summary = {}
-    for config in a.configs.split(","):
-        c = {}
-        for build, _ in trees:
-            for s in ("none", "sparse", "whole"):
-                if not series(build, config, s, lambda v: 0):
-                    continue
-                e = {"device_ms_per_step": spread(series(build, config, s, lambda v: v["device_ms_per_step"])),
-                     "pcie_ms_per_step": spread(series(build, config, s, lambda v: v["pcie_ms_per_step"])),
-                     "bytes_out": series(build, config, s, lambda v: v["pcie_bytes_out"])[0],
-                     "intervals": series(build, config, s, lambda v: v["intervals"])[0]}
-                for stg in ("index", "parse", "call", "hist", "fmt_len", "fmt_write"):
-                    e[stg + "_ms"] = spread(series(build, config, s, lambda v: v["device_stages_ms"][stg]))
-                if s != "none":
-                    e["region_ms"] = spread(series(build, config, s, lambda v: v["region_ms"]))
-                c[f"{build}_{s}"] = e
-        checks = [r["filtered_bytes_check"] for r in runs if r["config"] == config and "filtered_bytes_check" in r]
-        if checks:
-            c["filtered_bytes_check"] = checks[0]
-        summary[config] = c
-    doc = {"tool": "tools/gpu/regions_bench.py", "sites": a.sites, "steps": a.steps, "warmup": a.warmup,
-           "rounds": a.rounds, "depth": DEPTH,
-           "sets": {"sparse": f"an interval of {LEN_LO}-{LEN_HI} positions in every {PERIOD} (seed {SET_SEED})",
-                    "whole": "chr1"},
-           "note": "ms per step; device: text and records in HBM (device_sink 1), stages from HIP event pairs in a "
-                   "profiled run of the same steps; pcie: pinned host text in, records into the pinned host arena "
-                   "(device_sink 2), wall time.  region_ms: the stage that holds the region kernel (C2: parse, the "
-                   "tile parse; C3: fmt_len) with the set minus without, same process.  parent / this tree "
-                   "alternate within every round; the spread of a figure is its min .. max over the rounds",
-           "comparisons": comparisons(summary), "summary": summary, "runs": runs}
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
-    print("wrote", a.out)
-    return 0
+    trees = ob.trees(a)
+    runs, _ = ob.run_rounds(
+        a, __file__, [(name, tree, ["--sets", "none,sparse,whole" if name == "this" or a.parent_all else "none"],
+                       name == "this", None) for name, tree in trees],
+        derive, progress=lambda r: ", ".join(f"{s}: " + ob.set_line(v) for s, v in r["sets"].items()))
+    summary = ob.summarise(a, runs, "sets", [b for b, _ in trees], ("none", "sparse", "whole"), entry,
+                           check_key="filtered_bytes_check")
+    return ob.write_doc(a, {
+        **ob.doc_head(__file__, a), "depth": ob.DEPTH,
+        "sets": {"sparse": f"an interval of {LEN_LO}-{LEN_HI} positions in every {PERIOD} (seed {SET_SEED})",
+                 "whole": "chr1"},
+        "note": ob.NOTE + "region_ms: the stage that holds the region kernel (C2: parse, the tile parse; C3: "
+                "fmt_len) with the set minus without, same process.  " + ob.NOTE_ROUNDS,
+        "comparisons": comparisons(summary), "summary": summary, "runs": runs})
 
 
 if __name__ == "__main__":
