@@ -12,7 +12,7 @@ HOSTFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Iinclude
 HIPFLAGS += $(EXTRA)
 
 KERNELS := local synth lynch textpath inflate
-HOSTSRC := capi lynch_host parse emit regions context windows depth_hist callable bgzf run
+HOSTSRC := capi lynch_host parse emit regions context windows depth_hist region_stats callable bgzf run
 OBJS := $(KERNELS:%=$(BUILD)/%.o) $(HOSTSRC:%=$(BUILD)/%.o)
 HDRS := include/sid.h $(wildcard $(SRC)/*.h)
 
@@ -23,7 +23,7 @@ $(BUILD)/%.o: $(SRC)/%.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # host-only translation units: compiled by hipcc as HIP (they include the HIP
-# runtime headers); parse/emit/regions/context/windows/depth_hist/callable use no HIP at all
+# runtime headers); parse/emit/regions/context/windows/depth_hist/region_stats/callable use no HIP at all
 $(BUILD)/%.o: $(SRC)/%.cpp $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@

@@ -170,6 +170,44 @@
  *     that is reused starts every run from zero.  The switch is no field of
  *     sid_opts (whose layout stands).  Host path: sid_depth_hist_host, on the
  *     codes before any mark.
+ *   - Region rows (sid_engine_set_region_stats; --region-stats FILE with
+ *     --regions): a summary of the run along the region set, beside the
+ *     records: one row for every interval of the set after its merge, exactly
+ *     the intervals sid_regions_intervals counts, an interval without a site
+ *     included.  The sites are the non-empty lines; a site's chrom, pos, depth,
+ *     record and label are as in the paragraphs on windows and depth bounds:
+ *     the atoi position, A + C + G + T of the stored profile_t, and the
+ *     unselected code.  A site belongs to interval j when sid_regions_contains
+ *     holds for it and j is the interval that holds it: chrom byte-equal, start
+ *     < pos <= end.  The intervals are disjoint, so a site belongs to at most
+ *     one; sites outside every interval count nowhere.  The columns: chrom,
+ *     start, end (the interval, BED); sites; depth, the sum of the sites'
+ *     depths in 64 bits (what samtools bedcov prints); records, the sites that
+ *     print a record in the unselected output; het and hom, those records by
+ *     label (records = het + hom).  Row order: the chroms in the order of their
+ *     first non-empty interval in the source (BED line order; array order for
+ *     sid_regions_from_intervals), a chrom's intervals ascending by start --
+ *     sid_regions_interval enumerates them; the device's flat table keeps its
+ *     own order, (first 8 bytes, length, bytes), byte for byte what it was.
+ *     Like the other summaries the rows see every site: the selections by
+ *     label, variant and depth, the context and the record format never change
+ *     them; the region set is where the intervals come from, and its selection
+ *     of the records does not change what the rows count; the option changes
+ *     neither the records, bytes_out, stderr nor the exit status.  The rows do
+ *     not depend on chunk size, device count, lanes, budgets, source kind, sink
+ *     mode or tile shape; a chunk counts once however often it is parsed.  A
+ *     run that fails has no rows; an engine that is reused starts every run
+ *     from zero.  A set of more than SID_REGION_STATS_MAX = 2^20 merged
+ *     intervals is refused when the option is switched on
+ *     (sid_region_stats_valid): a memory budget -- the device's per-chunk table
+ *     and its two row sets take 24 bytes an interval each, 72 MiB a workspace
+ *     at the cap -- not a measured figure; a finer tiling is what the windows
+ *     are for.  By construction sites sums to the number of sites for which
+ *     sid_regions_contains is true, records to the records of a run whose only
+ *     selection is the set, het to its het records.  The switch is no field of
+ *     sid_opts (whose layout stands).  Host path: sid_region_stats_host, on
+ *     the codes before any mark; over a resident shard:
+ *     sid_dtext_region_stats.
  *   - Callable runs (sid_callable_host, sid_dtext_callable; --callable FILE
  *     with --host-parse): the positions where a call could be made, as BED
  *     rows beside the records.  The sites
@@ -392,6 +430,44 @@ void sid_depth_hist_free(sid_depth_row* rows);
 int sid_depth_hist_format(const sid_depth_row* rows, size_t n, int with_header, char* buf, size_t cap, size_t* len);
 int sid_depth_hist_merge(const sid_depth_row* a, size_t na, const sid_depth_row* b, size_t nb, sid_depth_row** rows,
                          size_t* n);
+
+/* ----------------------------------------------------------- region rows --
+ * The region rows (Conventions), one per merged interval in the set's source
+ * order.  chrom is not NUL-terminated.
+ *
+ * sid_regions_interval: interval j (0 .. sid_regions_intervals - 1) of the set
+ *   in row order; *chrom points into the set.  Any out pointer may be NULL.
+ *   SID_EINVAL for a NULL set or j out of range.
+ * sid_region_stats_valid: SID_OK when the option can be switched on for the
+ *   set, SID_EINVAL for NULL or more than SID_REGION_STATS_MAX intervals.
+ * sid_region_stats_host: the rows of sites [begin, end) on the host path (the
+ *   analogue of sid_depth_hist_host): code_all are the codes before any
+ *   selection marked them.  *n is sid_regions_intervals.  *rows is freed with
+ *   sid_region_stats_free and holds its own copy of the names.  SID_EINVAL for
+ *   a NULL set, a range outside the sites or a NULL pointer.
+ * sid_region_stats_format: "chrom,start,end,sites,depth,records,het,hom\n"
+ *   (with_header) and a line per row, the integers in decimal.  Returns bytes
+ *   written in *len, or SID_ENOMEM if cap is too small (then *len is a
+ *   sufficient size), as sid_depth_hist_format.
+ * sid_region_stats_merge: the elementwise sum of two lists of n rows over the
+ *   same set (ranks that took site ranges add their rows with it); *rows is
+ *   freed with sid_region_stats_free.  SID_EINVAL for a NULL pointer or two
+ *   lists whose keys (chrom, start, end) differ in any row. */
+#define SID_REGION_STATS_MAX (1u << 20)
+typedef struct {
+    const char* chrom;
+    uint32_t chrom_len;
+    int64_t start, end;
+    uint64_t sites, depth, records, het, hom;
+} sid_region_row;
+int sid_regions_interval(const sid_regions* r, size_t j, const char** chrom, uint32_t* chrom_len, int64_t* start,
+                         int64_t* end);
+int sid_region_stats_valid(const sid_regions* r);
+int sid_region_stats_host(const sid_regions* r, const struct sid_sites* s, size_t begin, size_t end,
+                          const uint8_t* code_all /* host */, sid_region_row** rows, size_t* n);
+void sid_region_stats_free(sid_region_row* rows);
+int sid_region_stats_format(const sid_region_row* rows, size_t n, int with_header, char* buf, size_t cap, size_t* len);
+int sid_region_stats_merge(const sid_region_row* a, const sid_region_row* b, size_t n, sid_region_row** rows);
 
 /* -------------------------------------------------------- callable runs --
  * The rows of the callable runs (Conventions), in file order.
@@ -619,6 +695,14 @@ int sid_dtext_windows(sid_ctx* ctx, const sid_dtext* t, size_t begin, size_t end
  * Synchronises. */
 int sid_dtext_depth_hist(sid_ctx* ctx, const sid_dtext* t, size_t begin, size_t end, const uint8_t* code /* device */,
                          sid_depth_row** rows, size_t* n, void* stream);
+/* The region rows (Conventions) of sites [begin, end) of a resident shard with
+ * the given device codes, for the context's region set (sid_opts.regions at
+ * sid_create): the engine's stage over one range.  It needs no switch on the
+ * context.  *rows (sid_regions_intervals of them, with their own copy of the
+ * names) is freed with sid_region_stats_free.  SID_EINVAL for a context
+ * without a set or with one sid_region_stats_valid refuses.  Synchronises. */
+int sid_dtext_region_stats(sid_ctx* ctx, const sid_dtext* t, size_t begin, size_t end,
+                           const uint8_t* code /* device */, sid_region_row** rows, size_t* n, void* stream);
 /* The callable runs (Conventions) of sites [begin, end) of a resident shard
  * with the given device codes, under the context's depth bounds (sid_set_depth):
  * the device stage over one range, the range's first site opening a row.  It
@@ -802,6 +886,15 @@ int sid_engine_set_format(sid_engine* e, int format);
  * is launched and no buffer of it allocated.  On, a selection by label goes the
  * context's route with N = 0, as under sid_opts.window: the same records. */
 int sid_engine_set_depth_hist(sid_engine* e, int on);
+/* The region rows (Conventions) of every pipeline, under the same state rules:
+ * SID_EINVAL for a value other than 0 and 1, for an engine created without
+ * sid_opts.regions, or for a set of more than SID_REGION_STATS_MAX intervals;
+ * SID_ESTATE between a successful sid_engine_ingest and its emit.  The setting
+ * holds for every later run until it is set again.  Off (the default): no
+ * kernel of the stage is launched and no buffer of it allocated.  On, a
+ * selection by label goes the context's route with N = 0, as under
+ * sid_engine_set_depth_hist: the same records. */
+int sid_engine_set_region_stats(sid_engine* e, int on);
 /* Host placement of pipeline i (a multi-GPU node: each GPU's uploader,
  * compute and drain threads run on the CPUs local to its PCI device, and its
  * pinned host buffers are allocated from them, so their pages sit on the
@@ -873,6 +966,12 @@ int sid_engine_windows(sid_engine* e, const sid_window** rows, size_t* n);
  * sid_run_stats has no field for the number of rows (its layout stands, as
  * sid_opts'): *n is that number. */
 int sid_engine_depth_hist(sid_engine* e, const sid_depth_row** rows, size_t* n);
+/* The region rows of the run (sid_engine_set_region_stats), after a successful
+ * sid_engine_emit in every device_sink mode: one row per interval of the set in
+ * row order, owned by the engine (the names too) and valid until the next
+ * ingest or source.  SID_ESTATE before that, after a failed run, or with the
+ * option off.  sid_run_stats has no field for them (its layout stands). */
+int sid_engine_region_stats(sid_engine* e, const sid_region_row** rows, size_t* n);
 /* Measurement: with profiling on, every stage of every chunk is bracketed by
  * a pair of HIP events on its device's compute stream; _read sums the stages'
  * device time over the chunks and devices since the last read (synchronises). */

@@ -108,6 +108,16 @@ class DepthRow(C.Structure):
                 ("depth", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class RegionRow(C.Structure):
+    """sid_region_row: one row of the region rows (chrom is not NUL-terminated)."""
+    _fields_ = [("chrom", C.c_void_p), ("chrom_len", C.c_uint32), ("start", C.c_int64), ("end", C.c_int64),
+                ("sites", C.c_uint64), ("depth", C.c_uint64), ("records", C.c_uint64), ("het", C.c_uint64),
+                ("hom", C.c_uint64)]
+
+
+REGION_STATS_MAX = 1 << 20   # SID_REGION_STATS_MAX
+
+
 class CallableRow(C.Structure):
     """sid_callable_row: one callable run (BED start and end)."""
     _fields_ = [("chrom", C.c_void_p), ("chrom_len", C.c_uint32), ("pad", C.c_uint32),
@@ -150,6 +160,16 @@ SIGNATURES = [
     ("sid_dtext_depth_hist", _I, [_P, _P, _SZ, _SZ, _P, C.POINTER(C.POINTER(DepthRow)), C.POINTER(C.c_size_t), _P]),
     ("sid_engine_set_depth_hist", _I, [_P, _I]),
     ("sid_engine_depth_hist", _I, [_P, C.POINTER(C.POINTER(DepthRow)), C.POINTER(C.c_size_t)]),
+    ("sid_regions_interval", _I, [_P, _SZ, C.POINTER(_P), C.POINTER(C.c_uint32), C.POINTER(C.c_int64),
+                                  C.POINTER(C.c_int64)]),
+    ("sid_region_stats_valid", _I, [_P]),
+    ("sid_region_stats_host", _I, [_P, _P, _SZ, _SZ, _P, C.POINTER(C.POINTER(RegionRow)), C.POINTER(C.c_size_t)]),
+    ("sid_region_stats_free", None, [C.POINTER(RegionRow)]),
+    ("sid_region_stats_format", _I, [C.POINTER(RegionRow), _SZ, _I, _P, _SZ, C.POINTER(C.c_size_t)]),
+    ("sid_region_stats_merge", _I, [C.POINTER(RegionRow), C.POINTER(RegionRow), _SZ, C.POINTER(C.POINTER(RegionRow))]),
+    ("sid_dtext_region_stats", _I, [_P, _P, _SZ, _SZ, _P, C.POINTER(C.POINTER(RegionRow)), C.POINTER(C.c_size_t), _P]),
+    ("sid_engine_set_region_stats", _I, [_P, _I]),
+    ("sid_engine_region_stats", _I, [_P, C.POINTER(C.POINTER(RegionRow)), C.POINTER(C.c_size_t)]),
     ("sid_callable_host", _I, [_P, _SZ, _SZ, _P, _I, _I, C.POINTER(C.POINTER(CallableRow)), C.POINTER(C.c_size_t)]),
     ("sid_callable_free", None, [C.POINTER(CallableRow)]),
     ("sid_callable_format", _I, [C.POINTER(CallableRow), _SZ, _P, _SZ, C.POINTER(C.c_size_t)]),
@@ -340,6 +360,19 @@ class Regions:
     def chroms(self) -> int:
         return int(lib().sid_regions_chroms(self._handle()))
 
+    def interval(self, j: int) -> tuple:
+        """sid_regions_interval: (chrom bytes, start, end) of merged interval j
+        in row order -- the chroms by their first non-empty interval in the
+        source, a chrom's intervals ascending."""
+        chrom, clen, start, end = C.c_void_p(), C.c_uint32(0), C.c_int64(0), C.c_int64(0)
+        check(lib().sid_regions_interval(self._handle(), int(j), C.byref(chrom), C.byref(clen), C.byref(start),
+                                         C.byref(end)), "sid_regions_interval")
+        return (C.string_at(chrom.value, clen.value) if clen.value else b"", start.value, end.value)
+
+    def region_stats_valid(self) -> bool:
+        """sid_region_stats_valid: the region rows can be switched on for the set."""
+        return lib().sid_region_stats_valid(self._handle()) == SID_OK
+
     def close(self):
         if getattr(self, "h", None) and _LIB is not None:
             _LIB.sid_regions_free(self.h)
@@ -506,6 +539,88 @@ def dtext_depth_hist(ctx: "Context", dtext: "DText", code_ptr, begin: int = 0, e
         return _depth_rows(rows, n.value)
     finally:
         lib().sid_depth_hist_free(rows)
+
+
+def _region_rows(rows, n: int) -> list:
+    """sid_region_row rows as tuples (chrom, start, end, sites, depth, records, het, hom)."""
+    out = []
+    for k in range(n):
+        r = rows[k]
+        chrom = C.string_at(r.chrom, r.chrom_len) if r.chrom_len else b""
+        out.append((chrom, r.start, r.end, r.sites, r.depth, r.records, r.het, r.hom))
+    return out
+
+
+def _region_array(rows):
+    """(array, n, keep-alive list of the chrom buffers)"""
+    rows = list(rows)
+    arr = (RegionRow * max(len(rows), 1))()
+    keep = []
+    for k, (chrom, start, end, sites, depth, records, het, hom) in enumerate(rows):
+        c = chrom if isinstance(chrom, bytes) else str(chrom).encode()
+        b = C.create_string_buffer(c, max(len(c), 1))
+        keep.append(b)
+        arr[k] = RegionRow(C.cast(b, C.c_void_p), len(c), start, end, sites, depth, records, het, hom)
+    return arr, len(rows), keep
+
+
+def region_stats_host(regions: "Regions", sites: "Sites", code_all: np.ndarray, begin: int = 0, end: int = None) -> list:
+    """sid_region_stats_host: the region rows of sites [begin, end) from their
+    codes before any selection marked them, one per interval of the set."""
+    code_all = np.ascontiguousarray(code_all, np.uint8)
+    if end is None:
+        end = len(sites)
+    if code_all.size != len(sites):
+        raise SidError(1, "region_stats_host: one code per site")
+    rows, n = C.POINTER(RegionRow)(), C.c_size_t(0)
+    check(lib().sid_region_stats_host(regions._handle(), sites.handle, begin, end, _ptr(code_all), C.byref(rows),
+                                      C.byref(n)), "sid_region_stats_host")
+    try:
+        return _region_rows(rows, n.value)
+    finally:
+        lib().sid_region_stats_free(rows)
+
+
+def region_stats_format(rows, header: bool = True) -> bytes:
+    """sid_region_stats_format over rows as region_stats_host / Engine.region_stats return them."""
+    arr, m, _keep = _region_array(rows)
+    n = C.c_size_t(0)
+    st = lib().sid_region_stats_format(arr, m, int(bool(header)), None, 0, C.byref(n))
+    if st not in (SID_OK, 3):
+        check(st, "sid_region_stats_format")
+    buf = C.create_string_buffer(max(n.value, 1))
+    check(lib().sid_region_stats_format(arr, m, int(bool(header)), buf, n.value, C.byref(n)), "sid_region_stats_format")
+    return buf.raw[:n.value]
+
+
+def region_stats_merge(a, b) -> list:
+    """sid_region_stats_merge: the elementwise sum of two row lists over the same
+    set (ranks that took site ranges add their rows with it); SidError when the
+    lists' lengths or keys differ."""
+    aa, na, _ka = _region_array(a)
+    ab, nb, _kb = _region_array(b)
+    if na != nb:
+        raise SidError(1, "region_stats_merge: the lists differ in length")
+    rows = C.POINTER(RegionRow)()
+    check(lib().sid_region_stats_merge(aa, ab, na, C.byref(rows)), "sid_region_stats_merge")
+    try:
+        return _region_rows(rows, na)
+    finally:
+        lib().sid_region_stats_free(rows)
+
+
+def dtext_region_stats(ctx: "Context", dtext: "DText", code_ptr, begin: int = 0, end: int = None, stream=None) -> list:
+    """sid_dtext_region_stats: the region rows' stage over sites [begin, end) of
+    a resident shard with the given device codes, for the context's region set."""
+    if end is None:
+        end = len(dtext)
+    rows, n = C.POINTER(RegionRow)(), C.c_size_t(0)
+    check(lib().sid_dtext_region_stats(ctx.h, dtext.h, begin, end, code_ptr, C.byref(rows), C.byref(n), stream),
+          "sid_dtext_region_stats")
+    try:
+        return _region_rows(rows, n.value)
+    finally:
+        lib().sid_region_stats_free(rows)
 
 
 def _callable_rows(rows, n: int) -> list:
@@ -1056,7 +1171,7 @@ class Engine:
 
     def __init__(self, method="local", devices=1, first_device=0, chunk_bytes=0, slots=0, hold_bytes=0,
                  retain_bytes=0, host_threads=0, verbose=False, device_sink=False, lanes=0, host_hold_bytes=0,
-                 min_depth=0, max_depth=0, format="csv", depth_hist=False, **opts):
+                 min_depth=0, max_depth=0, format="csv", depth_hist=False, region_stats=False, **opts):
         fmt = _format(format)
         self.opts = make_opts(method=method, **opts)
         cfg = EngineCfg()
@@ -1077,6 +1192,12 @@ class Engine:
             self.set_format(fmt)
         if depth_hist:               # (nor the depth histogram's switch)
             self.set_depth_hist(True)
+        if region_stats:             # (nor the region rows')
+            try:
+                self.set_region_stats(True)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "h", None):
@@ -1107,6 +1228,12 @@ class Engine:
         """The depth histogram of every run from now on (Engine.depth_hist);
         SID_ESTATE between an ingest and its emit."""
         check(lib().sid_engine_set_depth_hist(self.h, int(on)), "sid_engine_set_depth_hist")
+
+    def set_region_stats(self, on: bool):
+        """The region rows of every run from now on (Engine.region_stats);
+        SID_EINVAL without a region set or past SID_REGION_STATS_MAX intervals,
+        SID_ESTATE between an ingest and its emit."""
+        check(lib().sid_engine_set_region_stats(self.h, int(on)), "sid_engine_set_region_stats")
 
     def placement(self, i=0) -> dict:
         """Pipeline i's host placement: its GPU's NUMA node, the CPUs its
@@ -1245,6 +1372,14 @@ class Engine:
         rows, n = C.POINTER(DepthRow)(), C.c_size_t(0)
         check(lib().sid_engine_depth_hist(self.h, C.byref(rows), C.byref(n)), "sid_engine_depth_hist")
         return _depth_rows(rows, n.value)
+
+    def region_stats(self) -> list:
+        """The region rows of the last run (region_stats=True), after emit: tuples
+        (chrom, start, end, sites, depth, records, het, hom), one per interval of
+        the region set in row order."""
+        rows, n = C.POINTER(RegionRow)(), C.c_size_t(0)
+        check(lib().sid_engine_region_stats(self.h, C.byref(rows), C.byref(n)), "sid_engine_region_stats")
+        return _region_rows(rows, n.value)
 
     def profile(self, enable=True):
         check(lib().sid_engine_profile(self.h, int(bool(enable))), "sid_engine_profile")

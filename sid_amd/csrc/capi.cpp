@@ -197,6 +197,7 @@ extern "C" int sid_create(int device, const sid_opts* opts, sid_ctx** out)
                                b + L.names, L.nc, L.ni};
         c->has_regions = !c->cx_on;
         c->cx_regions = c->cx_on;
+        c->regions_host = new sid_regions(*rg);   // (the region rows' names and order)
         c->opts.regions = nullptr;
     }
     if (e != hipSuccess) {
@@ -222,6 +223,7 @@ extern "C" int sid_destroy(sid_ctx* c)
     if (c->ws.miss) (void)hipFree(c->ws.miss);
     if (c->ws.ctr) (void)hipFree(c->ws.ctr);
     if (c->d_regions) (void)hipFree(c->d_regions);
+    delete c->regions_host;
     if (c->lynch) sid_lynch_dev_destroy(c->lynch);
     for (int b = 0; b < 2; ++b) {
         if (c->fmt_d[b]) (void)hipFree(c->fmt_d[b]);

@@ -28,6 +28,23 @@
 // any input is read.  --stats prints callable_rows and callable_sites, the sum
 // of end - start.  Not listed by -h.
 //
+// --region-stats FILE (with --regions BED): beside the records, the region rows
+// of the run (sid_engine_set_region_stats, sid.h Conventions) as CSV into FILE
+// -- "chrom,start,end,sites,depth,records,het,hom" and a line for every interval
+// of the set after its merge, one without a site included, the chroms in the
+// BED's order and a chrom's intervals ascending -- written after the records.
+// The rows count every site inside an interval: stdout, stderr and the exit
+// status are as without it, and --only, --variants, --min-depth / --max-depth,
+// --context and --vcf, like --regions' own selection of the records, never
+// change the rows.  Error texts and file handling as --depth-hist's: "sid:
+// --region-stats: could not open FILE" before any input is read, "sid:
+// --region-stats: could not write FILE"; a failing run leaves no file.  Without
+// --regions: "sid: --region-stats: needs --regions"; a set of more than 2^20
+// merged intervals: "sid: --region-stats: more than 1048576 intervals"; either
+// with exit status 1 before any input is read.  With --host-parse:
+// sid_region_stats_host.  --stats then also prints region_rows and
+// region_sites, the sum of the sites column.  Not listed by -h.
+//
 // --depth-hist FILE: beside the records, the depth histogram of the run
 // (sid_engine_set_depth_hist, sid.h Conventions) as CSV into FILE --
 // "depth,sites,records,het,hom" and a line per depth that a site has, in
@@ -344,6 +361,7 @@ int main(int argc, char** argv)
     bool vcf = false;                    // --vcf
     const char* depth_hist_out = nullptr;   // --depth-hist
     const char* callable_out = nullptr;     // --callable
+    const char* region_stats_out = nullptr; // --region-stats
     static const struct option LONG[] = {{"devices", required_argument, nullptr, 1},
                                          {"threads", required_argument, nullptr, 2},
                                          {"stats", no_argument, nullptr, 3},
@@ -364,6 +382,7 @@ int main(int argc, char** argv)
                                          {"vcf", no_argument, nullptr, 18},
                                          {"depth-hist", required_argument, nullptr, 19},
                                          {"callable", required_argument, nullptr, 20},
+                                         {"region-stats", required_argument, nullptr, 21},
                                          {nullptr, 0, nullptr, 0}};
     int flag;
     while ((flag = getopt_long(argc, argv, "E:Rhm:p:r:", LONG, nullptr)) != -1) {
@@ -481,6 +500,7 @@ int main(int argc, char** argv)
         case 18: vcf = true; break;
         case 19: depth_hist_out = optarg; break;   // (given twice: the last wins)
         case 20: callable_out = optarg; break;     // (likewise)
+        case 21: region_stats_out = optarg; break; // (likewise)
         default: std::exit(EXIT_FAILURE);
         }
     }
@@ -533,6 +553,27 @@ int main(int argc, char** argv)
         }
         ::close(fd);
         if (!was) ::unlink(callable_out);
+    }
+    if (region_stats_out && !regions) {
+        std::fflush(stdout);
+        std::fputs("sid: --region-stats: needs --regions\n", stderr);
+        std::exit(EXIT_FAILURE);
+    }
+    if (region_stats_out && sid_region_stats_valid(regions) != SID_OK) {
+        std::fflush(stdout);
+        std::fprintf(stderr, "sid: --region-stats: more than %u intervals\n", (unsigned)SID_REGION_STATS_MAX);
+        std::exit(EXIT_FAILURE);
+    }
+    if (region_stats_out) {   // the file must be creatable, as --depth-hist's
+        const bool was = ::access(region_stats_out, F_OK) == 0;
+        const int fd = ::open(region_stats_out, O_WRONLY | O_CREAT, 0666);
+        if (fd < 0) {
+            std::fflush(stdout);
+            std::fprintf(stderr, "sid: --region-stats: could not open %s\n", region_stats_out);
+            std::exit(EXIT_FAILURE);
+        }
+        ::close(fd);
+        if (!was) ::unlink(region_stats_out);
     }
     if (optind >= argc) {
         std::fflush(stdout);
@@ -595,6 +636,7 @@ int main(int argc, char** argv)
         if (rc == SID_OK && depth_on) rc = sid_engine_set_depth(eng, min_depth, max_depth);
         if (rc == SID_OK && vcf) rc = sid_engine_set_format(eng, SID_FORMAT_VCF);
         if (rc == SID_OK && depth_hist_out) rc = sid_engine_set_depth_hist(eng, 1);
+        if (rc == SID_OK && region_stats_out) rc = sid_engine_set_region_stats(eng, 1);
         return rc;
     };
     int dev_rc = SID_OK, eng_rc = SID_OK;
@@ -718,6 +760,36 @@ int main(int argc, char** argv)
             std::exit(EXIT_FAILURE);
         }
     };
+    // --region-stats: the rows as CSV, after the records; returns the sum of the sites column
+    auto write_region_stats = [&](const sid_region_row* rows, size_t nrows) {
+        size_t need = 0;
+        (void)sid_region_stats_format(rows, nrows, 1, nullptr, 0, &need);
+        std::string csv(need, '\0');
+        CHECK(sid_region_stats_format(rows, nrows, 1, &csv[0], need, &need), "region-stats");
+        const int fd = ::open(region_stats_out, O_WRONLY | O_CREAT | O_TRUNC, 0666);
+        size_t off = 0;
+        while (fd >= 0 && off < csv.size()) {
+            const ssize_t w = ::write(fd, csv.data() + off, csv.size() - off);
+            if (w <= 0) break;
+            off += (size_t)w;
+        }
+        if (fd < 0 || off < csv.size() || ::close(fd) != 0) {
+            std::fflush(stdout);
+            std::fprintf(stderr, "sid: --region-stats: could not write %s\n", region_stats_out);
+            std::exit(EXIT_FAILURE);
+        }
+        unsigned long long sites = 0;
+        for (size_t k = 0; k < nrows; ++k) sites += (unsigned long long)rows[k].sites;
+        return sites;
+    };
+    // --stats under --region-stats: its two fields (else nothing: the line as it was)
+    auto region_stats_json = [&](size_t nrows, unsigned long long sites) {
+        char b[96];
+        b[0] = 0;
+        if (region_stats_out)
+            std::snprintf(b, sizeof b, "\"region_rows\": %zu, \"region_sites\": %llu, ", nrows, sites);
+        return std::string(b);
+    };
     // --callable: the rows as BED, after the records; returns the sum of end - start
     auto write_callable = [&](const sid_callable_row* rows, size_t nrows) {
         size_t need = 0;
@@ -802,6 +874,13 @@ int main(int argc, char** argv)
             CHECK(sid_engine_depth_hist(eng, &rows, &depth_rows), "depth-hist");
             write_depth_hist(rows, depth_rows);
         }
+        size_t region_rows = 0;
+        unsigned long long region_sites = 0;
+        if (region_stats_out) {
+            const sid_region_row* rows = nullptr;
+            CHECK(sid_engine_region_stats(eng, &rows, &region_rows), "region-stats");
+            region_sites = write_region_stats(rows, region_rows);
+        }
         const double t3 = now();
         std::string place;   // per pipeline: its GPU, the CPUs its threads ran on, its pinned buffers' NUMA nodes
         if (opt.stats)
@@ -825,7 +904,7 @@ int main(int argc, char** argv)
                          "\"bytes_out\": %llu, \"ingest_s\": %.6f, \"chunks_registered\": %llu, "
                          "\"register_s\": %.6f, \"h2d_s\": %.6f, \"h2d_bytes\": %llu, \"chunks_tiled\": %llu, "
                          "\"tile_overflows\": %llu, \"tile_overflows_queued\": %llu, \"bgzf_bytes\": %llu, "
-                         "\"bgzf_blocks\": %llu, \"window_rows\": %llu, \"depth_rows\": %llu, \"placement\": [%s], "
+                         "\"bgzf_blocks\": %llu, \"window_rows\": %llu, \"depth_rows\": %llu, %s\"placement\": [%s], "
                          "\"main_entry_unix\": %.6f, \"main_exit_unix\": %.6f}\n",
                          (unsigned long long)st.sites, D, T, tc - t0, t1 - t0, t2 - t1, t3 - t2, t3 - t0,
                          st.sites / std::max(1e-9, t3 - t0), (unsigned long long)st.chunks,
@@ -836,7 +915,8 @@ int main(int argc, char** argv)
                          (unsigned long long)st.chunks_tiled, (unsigned long long)st.tile_overflows,
                          (unsigned long long)st.tile_overflows_queued, (unsigned long long)st.bgzf_bytes,
                          (unsigned long long)st.bgzf_blocks, (unsigned long long)st.window_rows,
-                         (unsigned long long)depth_rows, place.c_str(),
+                         (unsigned long long)depth_rows, region_stats_json(region_rows, region_sites).c_str(),
+                         place.c_str(),
                          t_entry,
                          unix_now());
         // device memory, pinned staging and the mapping go with the process
@@ -961,8 +1041,8 @@ int main(int argc, char** argv)
     // ----------------------------------------------------------------- emit --
     std::fputs(HEADER, stdout);
     std::fflush(stdout);
-    size_t window_rows = 0, depth_rows = 0, callable_rows = 0;
-    unsigned long long callable_sites = 0;
+    size_t window_rows = 0, depth_rows = 0, callable_rows = 0, region_rows = 0;
+    unsigned long long callable_sites = 0, region_sites = 0;
     {
         uint8_t* h_code = nullptr;
         double *h_hom = nullptr, *h_het = nullptr;
@@ -990,6 +1070,11 @@ int main(int argc, char** argv)
         size_t ndrows = 0;
         if (depth_hist_out) CHECK(sid_depth_hist_host(sites, 0, n, h_code, &drows, &ndrows), "depth-hist");
         depth_rows = ndrows;
+        sid_region_row* rrows = nullptr;   // --region-stats: likewise
+        size_t nrrows = 0;
+        if (region_stats_out)
+            CHECK(sid_region_stats_host(regions, sites, 0, n, h_code, &rrows, &nrrows), "region-stats");
+        region_rows = nrrows;
         sid_callable_row* crows = nullptr;   // --callable: likewise, under the depth bounds
         size_t ncrows = 0;
         if (callable_out)
@@ -1043,6 +1128,8 @@ int main(int argc, char** argv)
         sid_windows_free(wrows);
         if (depth_hist_out) write_depth_hist(drows, ndrows);
         sid_depth_hist_free(drows);
+        if (region_stats_out) region_sites = write_region_stats(rrows, nrrows);
+        sid_region_stats_free(rrows);
         if (callable_out) callable_sites = write_callable(crows, ncrows);
         sid_callable_free(crows);
     }
@@ -1051,11 +1138,11 @@ int main(int argc, char** argv)
         std::fprintf(stderr,
                      "{\"sites\": %zu, \"devices\": %d, \"threads\": %d, \"path\": \"%s\", \"parse_s\": %.6f, "
                      "\"device_s\": %.6f, \"emit_s\": %.6f, \"total_s\": %.6f, \"sites_per_s\": %.1f, "
-                     "\"window_rows\": %zu, \"depth_rows\": %zu, \"callable_rows\": %zu, \"callable_sites\": %llu, "
+                     "\"window_rows\": %zu, \"depth_rows\": %zu, \"callable_rows\": %zu, \"callable_sites\": %llu, %s"
                      "\"main_entry_unix\": %.6f, \"main_exit_unix\": %.6f}\n",
                      n, D, T, "host", t1 - t0, t2 - t1, t3 - t2, t3 - t0,
                      n / std::max(1e-9, t3 - t0), window_rows, depth_rows, callable_rows, callable_sites,
-                     t_entry, unix_now());
+                     region_stats_json(region_rows, region_sites).c_str(), t_entry, unix_now());
     }
     // device memory, pinned staging and mappings go with the process: freeing
     // gigabytes of HBM and pinned host memory one by one only delays the exit

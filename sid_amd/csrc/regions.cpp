@@ -24,7 +24,18 @@ constexpr int64_t POS_MAX = 2147483647;   // 2^31 - 1
 struct Raw {
     int32_t start, end;
 };
-using RawSet = std::map<std::string, std::vector<Raw>>;
+struct RawChrom {
+    std::vector<Raw> iv;
+    uint64_t first = UINT64_MAX;   // the source index of its first non-empty interval
+};
+using RawSet = std::map<std::string, RawChrom>;
+
+void raw_add(RawSet& raw, std::string chrom, Raw x, uint64_t at)
+{
+    RawChrom& c = raw[std::move(chrom)];
+    c.iv.push_back(x);
+    if (x.start < x.end && c.first == UINT64_MAX) c.first = at;
+}
 
 bool is_sep(char c) { return c == ' ' || c == '\t'; }
 
@@ -55,12 +66,15 @@ sid_regions* build(RawSet& raw)
         uint64_t c8;
         const std::string* name;
         std::vector<Raw>* iv;
+        uint64_t first;
     };
     std::vector<Ent> ents;
-    for (auto& kv : raw) ents.push_back(Ent{sid_regions_c8(kv.first.data(), kv.first.size()), &kv.first, &kv.second});
+    for (auto& kv : raw)
+        ents.push_back(Ent{sid_regions_c8(kv.first.data(), kv.first.size()), &kv.first, &kv.second.iv, kv.second.first});
     std::sort(ents.begin(), ents.end(), [](const Ent& a, const Ent& b) {
         return key_less(a.c8, a.name->size(), a.name->data(), b.c8, b.name->size(), b.name->data());
     });
+    std::vector<std::pair<uint64_t, uint32_t>> by;   // (first source index, chrom)
     for (const Ent& en : ents) {
         std::vector<Raw>& v = *en.iv;
         std::sort(v.begin(), v.end(), [](const Raw& a, const Raw& b) { return a.start < b.start; });
@@ -76,8 +90,17 @@ sid_regions* build(RawSet& raw)
         r->name.push_back(*en.name);
         r->c8.push_back(en.c8);
         r->ibeg.push_back((uint32_t)first);
+        by.push_back({en.first, (uint32_t)r->name.size() - 1});
     }
     r->ibeg.push_back((uint32_t)r->start.size());
+    std::sort(by.begin(), by.end());   // the source order: the kept chroms by their first non-empty interval
+    r->rank.assign(r->name.size(), 0);
+    r->row.reserve(r->start.size());
+    for (size_t q = 0; q < by.size(); ++q) {
+        const uint32_t k = by[q].second;
+        r->rank[k] = (uint32_t)q;
+        for (uint32_t j = r->ibeg[k]; j < r->ibeg[k + 1]; ++j) r->row.push_back(j);
+    }
     return r;
 }
 
@@ -151,7 +174,7 @@ extern "C" int sid_regions_from_bed(const char* text, size_t len, sid_regions** 
         }
         s = std::min<uint64_t>(s, (uint64_t)POS_MAX);
         e = std::min<uint64_t>(e, (uint64_t)POS_MAX);
-        raw[std::string(fb[0], fe[0])].push_back(Raw{(int32_t)s, (int32_t)e});
+        raw_add(raw, std::string(fb[0], fe[0]), Raw{(int32_t)s, (int32_t)e}, line);
     }
     *out = build(raw);
     return SID_OK;
@@ -167,7 +190,7 @@ extern "C" int sid_regions_from_intervals(const char* const* chrom, const int32_
         if (!chrom[i] || !chrom[i][0] || start[i] < 0 || start[i] > end[i]) return SID_EINVAL;
         for (const char* q = chrom[i]; *q; ++q)
             if (is_sep(*q) || *q == '\n') return SID_EINVAL;   // the pileup's separators: no chrom holds one
-        raw[chrom[i]].push_back(Raw{start[i], end[i]});
+        raw_add(raw, chrom[i], Raw{start[i], end[i]}, i);
     }
     *out = build(raw);
     return SID_OK;
@@ -181,6 +204,19 @@ extern "C" int sid_regions_contains(const sid_regions* r, const char* chrom, siz
     if (!r || (chrom_len && !chrom)) return 0;
     const long k = find_chrom(r, chrom, chrom_len);
     return k >= 0 && chrom_has(r, k, pos) ? 1 : 0;
+}
+
+extern "C" int sid_regions_interval(const sid_regions* r, size_t j, const char** chrom, uint32_t* chrom_len,
+                                    int64_t* start, int64_t* end)
+{
+    if (!r || j >= r->row.size()) return SID_EINVAL;
+    const uint32_t t = r->row[j];
+    const size_t k = (size_t)(std::upper_bound(r->ibeg.begin(), r->ibeg.end(), t) - r->ibeg.begin()) - 1;
+    if (chrom) *chrom = r->name[k].data();
+    if (chrom_len) *chrom_len = (uint32_t)r->name[k].size();
+    if (start) *start = r->start[t];
+    if (end) *end = r->end[t];
+    return SID_OK;
 }
 
 extern "C" void sid_regions_free(sid_regions* r) { delete r; }

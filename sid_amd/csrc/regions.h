@@ -19,6 +19,12 @@ struct sid_regions {
     std::vector<uint64_t> c8;
     std::vector<uint32_t> ibeg;   // name.size() + 1 entries
     std::vector<int32_t> start, end;
+    // The source order (the region rows, region_stats.h): rank[k] is chrom k's
+    // place among the chroms by their first non-empty interval in the source,
+    // and row[r] the interval of row r -- chroms by rank, a chrom's intervals
+    // ascending.  Neither is part of the flat table.
+    std::vector<uint32_t> rank;   // name.size() entries
+    std::vector<uint32_t> row;    // start.size() entries
 };
 
 // first 8 bytes of a name, byte k in bits 8k.., zero beyond its length

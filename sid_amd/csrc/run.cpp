@@ -53,6 +53,7 @@
 #include "context.h"
 #include "windows.h"
 #include "depth_hist.h"
+#include "region_stats.h"
 #include "sid_internal.h"
 #include "synth.h"
 
@@ -253,6 +254,8 @@ struct ChunkRec {
     sid_win_chunk win;
     // the depth histogram (sid_engine_set_depth_hist): the chunk's rows sorted by depth, read back likewise
     std::vector<sid_dh_row> dh;
+    // the region rows (sid_engine_set_region_stats): the chunk's touched intervals, checked, read back likewise
+    std::vector<sid_rs_row> rs;
 };
 
 enum SrcKind { SRC_NONE, SRC_HOST, SRC_FILE, SRC_DEVICE, SRC_SYNTH_HOST, SRC_SYNTH_DEVICE, SRC_BGZF, SRC_BGZF_FILE };
@@ -757,6 +760,10 @@ struct sid_engine {
     bool depth_hist = false;         // sid_engine_set_depth_hist
     std::vector<sid_depth_row> dh;   // ... the run's rows, the chunks' summed by the emit
     bool dh_ready = false;
+    bool region_stats = false;       // sid_engine_set_region_stats
+    sid_region_row* rs = nullptr;    // ... the run's rows, the chunks' summed by the emit (sid_rs_export)
+    size_t rs_n = 0;
+    bool rs_ready = false;
     bool prof = false;
     double prof_ms[6] = {0, 0, 0, 0, 0, 0};   // sid_engine_prof order: index parse call hist fmt_len fmt_write
     uint64_t prof_chunks = 0;
@@ -1010,6 +1017,9 @@ static void drop_source(sid_engine* e)
     e->win_ready = false;
     e->dh.clear();
     e->dh_ready = false;
+    sid_region_stats_free(e->rs);
+    e->rs = nullptr, e->rs_n = 0;
+    e->rs_ready = false;
     sid_bgzf_free(e->zidx);
     e->zidx = nullptr;
     e->src = SRC_NONE;
@@ -1871,6 +1881,22 @@ void compute(sid_engine* e, Dev& d, int pass)
         if (x == hipSuccess) x = sync();
         return x;
     };
+    // the region rows likewise (sid_chunk_ws::rs_cur, rs_eager): a set holds every interval
+    const bool rstats = e->region_stats;
+    int next_rset = 0;
+    auto rs_take = [&](int b, std::vector<sid_rs_row>& c) {
+        const char* hb = W.rs_eager[b];
+        const uint64_t nr = *(const uint64_t*)hb;
+        if (nr > W.rs_ni) return hipErrorUnknown;
+        c.resize(nr);
+        if (nr <= SID_RS_EAGER_ROWS) {
+            if (nr) std::memcpy(c.data(), hb + 16, nr * sizeof(sid_rs_row));
+            return hipSuccess;
+        }
+        hipError_t x = hipMemcpyAsync(c.data(), W.rs_rows[b], nr * sizeof(sid_rs_row), hipMemcpyDeviceToHost, d.s_comp);
+        if (x == hipSuccess) x = sync();
+        return x;
+    };
     auto take = [&](Loaded& out) {
         if (have_next) {
             out = nextL;
@@ -1933,6 +1959,7 @@ void compute(sid_engine* e, Dev& d, int pass)
         uint64_t n = 0;
         int wset = pre_tiled ? next_wset : -1;   // the window stage's set of this chunk (none: no stage ran)
         int dset = pre_tiled ? next_dset : -1;   // ... and the depth histogram's
+        int rset = pre_tiled ? next_rset : -1;   // ... and the region rows'
         // the tile path: this chunk's records and byte count done (recorded
         // before the next chunk's tile parse is queued behind the writer: the
         // host and the records' D2H wait for this, not for that parse, which
@@ -2004,6 +2031,7 @@ void compute(sid_engine* e, Dev& d, int pass)
                     d.prof_end(1, pe);
                     wset = W.win_cur;
                     dset = W.dh_cur;
+                    rset = W.rs_cur;
                 }
                 if (rc == SID_OK) {
                     pe = d.prof_begin(P);
@@ -2043,6 +2071,7 @@ void compute(sid_engine* e, Dev& d, int pass)
                         next_tiled = x == hipSuccess;
                         next_wset = W.win_cur;
                         next_dset = W.dh_cur;
+                        next_rset = W.rs_cur;
                         next_lg = lg2;
                         next_quad = q2;
                     }
@@ -2266,6 +2295,7 @@ void compute(sid_engine* e, Dev& d, int pass)
                 if (rc != SID_OK) return (void)fail(e, rc);
                 wset = W.win_cur;
                 dset = W.dh_cur;
+                rset = W.rs_cur;
                 pe = d.prof_begin(P);
                 rc = fused    ? sid_chunk_local_put(d.ctx, &W, L.base, L.c1, n, e->conf_type, out, d.s_comp)
                      : lfused ? sid_chunk_lynch_put(d.ctx, &W, L.base, L.c1, n, out, d.s_comp)
@@ -2359,6 +2389,15 @@ void compute(sid_engine* e, Dev& d, int pass)
                 x = dh_take(dset, r.dh);
                 if (x != hipSuccess) return (void)hipfail(e, x);
                 if (!sid_dh_sort(&r.dh)) return (void)fail(e, SID_ESTATE);
+            }
+        }
+        if (rstats) {   // (likewise)
+            r.rs.clear();
+            if (out) {
+                if (rset < 0) return (void)fail(e, SID_ESTATE);
+                x = rs_take(rset, r.rs);
+                if (x != hipSuccess) return (void)hipfail(e, x);
+                if (!sid_rs_check(r.rs, W.rs_ni)) return (void)fail(e, SID_ESTATE);
             }
         }
         release_slot();
@@ -2644,11 +2683,15 @@ static void reset_run(sid_engine* e)
         r.cx_total = 0;
         r.win.clear();
         r.dh.clear();
+        r.rs.clear();
     }
     e->win.clear();
     e->win_ready = false;
     e->dh.clear();
     e->dh_ready = false;
+    sid_region_stats_free(e->rs);
+    e->rs = nullptr, e->rs_n = 0;
+    e->rs_ready = false;
     e->z_bytes = 0;
     e->z_blocks = 0;
     for (auto& dp : e->devs) {
@@ -3021,6 +3064,20 @@ extern "C" int sid_engine_emit(sid_engine* e, const char* header, sid_write_fn w
         if (rc == SID_OK)
             for (const auto& r : e->recs) sid_dh_add(&e->dh, r.dh);
     }
+    // ... and (sid_engine_set_region_stats) the chunks' region rows summed into one entry per interval
+    if (e && e->region_stats && rc != SID_ESTATE && rc != SID_EINVAL) {
+        sid_region_stats_free(e->rs);
+        e->rs = nullptr, e->rs_n = 0;
+        e->rs_ready = false;
+        const sid_regions* rg = e->devs[0]->ctx->regions_host;
+        if (rc == SID_OK && rg) {
+            std::vector<sid_rs_sum> tab(rg->start.size());
+            for (const auto& r : e->recs) sid_rs_add(&tab, r.rs);
+            const int xrc = sid_rs_export(rg, tab, false, &e->rs, &e->rs_n);
+            if (xrc != SID_OK) return xrc;
+            e->rs_ready = true;
+        }
+    }
     return rc;
 }
 
@@ -3029,8 +3086,9 @@ extern "C" int sid_engine_set_depth_hist(sid_engine* e, int on)
     if (!e || (on != 0 && on != 1)) return SID_EINVAL;
     if (e->ingested) return SID_ESTATE;
     for (auto& d : e->devs) {
-        // (a selection by label: through the context's route, whose parse keeps every site's label)
-        const int rc = sid_ctx_label_route(d->ctx, on != 0);
+        // (a selection by label: through the context's route, whose parse keeps every site's label; the
+        // region rows need the same route)
+        const int rc = sid_ctx_label_route(d->ctx, on != 0 || e->region_stats);
         if (rc != SID_OK) return rc;
         sid_chunk_bind_context(&d->ws, d->ctx);
         d->ws.dh_on = on != 0;   // (the workspace's buffers: at its next reservation)
@@ -3040,6 +3098,38 @@ extern "C" int sid_engine_set_depth_hist(sid_engine* e, int on)
     e->depth_hist = on != 0;
     e->dh.clear();
     e->dh_ready = false;
+    return SID_OK;
+}
+
+extern "C" int sid_engine_set_region_stats(sid_engine* e, int on)
+{
+    if (!e || (on != 0 && on != 1)) return SID_EINVAL;
+    const sid_regions* rg = e->devs[0]->ctx->regions_host;
+    if (on && (!rg || sid_region_stats_valid(rg) != SID_OK)) return SID_EINVAL;
+    if (e->ingested) return SID_ESTATE;
+    for (auto& d : e->devs) {
+        // (a selection by label: through the context's route, as the depth histogram)
+        const int rc = sid_ctx_label_route(d->ctx, on != 0 || e->depth_hist);
+        if (rc != SID_OK) return rc;
+        sid_chunk_bind_context(&d->ws, d->ctx);
+        d->ws.rs_on = on != 0;   // (the workspace's buffers: at its next reservation)
+    }
+    e->cx_n = e->devs[0]->ctx->cx_n;
+    e->cx_on = e->devs[0]->ctx->cx_on;
+    e->region_stats = on != 0;
+    sid_region_stats_free(e->rs);
+    e->rs = nullptr, e->rs_n = 0;
+    e->rs_ready = false;
+    return SID_OK;
+}
+
+extern "C" int sid_engine_region_stats(sid_engine* e, const sid_region_row** rows, size_t* n)
+{
+    if (!e || !rows || !n) return SID_EINVAL;
+    *rows = nullptr, *n = 0;
+    if (!e->region_stats || !e->rs_ready) return SID_ESTATE;
+    *rows = e->rs;
+    *n = e->rs_n;
     return SID_OK;
 }
 

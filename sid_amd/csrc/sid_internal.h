@@ -124,6 +124,9 @@ struct sid_ctx {
     bool has_regions = false;
     char* d_regions = nullptr;   // the table's device buffer
     sid_regtab regtab;
+    // ... and the context's host copy of the set, for the region rows' names and order (region_stats.h;
+    // sid_dtext_region_stats, the engine's sid_engine_region_stats); null without a set
+    struct sid_regions* regions_host = nullptr;
     // the context (sid_opts.context with a selection; else cx_n = 0 and nothing below is used): the parse,
     // tables and tails are then the unselected ones (opts.select is SID_SELECT_ALL and has_regions false from
     // sid_create on), and the marking stage (textpath.hip, sid_context_*_kernel) tests the label and the
@@ -289,7 +292,26 @@ struct sid_chunk_ws {
     char* dh_eager[2] = {nullptr, nullptr};    // pinned host memory: the set's count and first rows, stored by the
                                                // pack kernel (SID_DH_EAGER_BYTES)
     int dh_cur = 0;             // the set the last stage wrote
+    // the region rows' stage (the owner's sid_engine_set_region_stats; region_stats.h, textpath.hip
+    // sid_region_stats_*_kernel), beside the depth histogram's: one table of a bin per interval of rs_tab
+    // (sid_rs_bin; all zero between two stage runs -- the pack kernel clears the bins it read), and two sets
+    // of {count, rows, pinned block} used in turn.  A set's rows hold every interval (rs_tab->ni rows), so no
+    // chunk outgrows it.  rs_tab: the owner's region set whatever selects (its context's regtab), or null
+    bool rs_on = false;
+    const sid_regtab* rs_tab = nullptr;
+    struct sid_rs_bin* rs_bins = nullptr;
+    unsigned long long* rs_cnt[2] = {nullptr, nullptr};   // the chunk's rows (the bins touched)
+    struct sid_rs_row* rs_rows[2] = {nullptr, nullptr};
+    char* rs_eager[2] = {nullptr, nullptr};    // pinned host memory: the set's count and first rows, stored by the
+                                               // pack kernel (SID_RS_EAGER_BYTES)
+    uint32_t rs_ni = 0;         // the intervals the buffers were sized for
+    int rs_cur = 0;             // the set the last stage wrote
 };
+// the region rows that reach the host with every chunk's byte count (more: a copy of their own), behind two
+// words of count: 24 B a row (a 128 MiB chunk of an exome-like set touches a few thousand intervals, a
+// whole-chromosome set one)
+constexpr uint32_t SID_RS_EAGER_ROWS = 256;
+constexpr size_t SID_RS_EAGER_BYTES = 16 + SID_RS_EAGER_ROWS * 24;
 // the rows that reach the host with every chunk's byte count (more: a copy of their own), behind two words
 // of count: 16 B a row (a 30x run has some 80 depths, a 200x run some 150)
 constexpr uint32_t SID_DH_EAGER_ROWS = 384;

@@ -45,6 +45,7 @@
 #include "vcf.h"
 #include "windows.h"
 #include "depth_hist.h"
+#include "region_stats.h"
 #include "callable.h"
 #include "local_site.h"
 
@@ -4976,6 +4977,258 @@ static void launch_depth_hist(const SiteArgs<Off>& A, const DhBufs& B, hipStream
     sid_depth_hist_pack_kernel<<<1, SCAN_TB, 0, st>>>(B.cnt, B.bins, B.rows, SID_DH_BINS, B.eager, B.out);
 }
 
+// ----------------------------------------------------------- region rows --
+// The region rows (sid_engine_set_region_stats; region_stats.h): per interval
+// of the region set the chunk's sites, their summed depth, het records and hom
+// records.  The stage reads what the region stage and the depth histogram read
+// together -- sv_site on the unfiltered tables, sv_head for the search,
+// sv_label, sv_depth -- and runs beside the histogram, in front of the marking
+// stages.  Two steps, the histogram's:
+//   bin    reg_index, reg_inside's sibling, gives every slot its interval's
+//          index in the flat table (RS_NONE: no site, or outside).  Sorted
+//          input with long intervals -- in the limit one whole-chromosome
+//          interval -- sends every site of a chunk to one bin, so nothing goes
+//          to the table a site or a wave at a time:
+//            - a wave reduces the lanes that share its first pending lane's
+//              index (a ballot, popcounts for sites, het and hom, a masked wave
+//              sum for the depth), one index a round, RS_ROUNDS rounds at most;
+//              the lanes still pending after them add a lane each, so a wave of
+//              64 distinct intervals stays bounded;
+//            - the wave carries the sums of its current index in registers
+//              across the groups it walks and adds them to the table only when
+//              the index changes and at its end;
+//            - a block therefore takes a contiguous run of 512-slot groups, not
+//              a grid stride, and at its end the eight waves' carries meet in
+//              LDS, where equal indices are summed before they go out.
+//          A whole-chromosome interval costs one set of atomics a block.  The
+//          add that finds a bin's site counter at 0 appends the index to the
+//          set's rows, as dh_table_add.  Integer atomics only: the rows are
+//          exact whatever the order of arrival.
+//   pack   one block: the touched bins into their rows, the bins and the count
+//          cleared (no memset a chunk), the count and the first
+//          SID_RS_EAGER_ROWS rows into the set's pinned block.
+// FORM (the environment variable SID_RS_FORM picks one, a
+// measurement switch): 0 the carry as above; 1 no carry, every wave adds its
+// rounds' sums straight to the table.
+constexpr uint32_t RS_NONE = 0xFFFFFFFFu;
+constexpr uint32_t RS_ROUNDS = 4;          // distinct indices a wave reduces before its lanes go alone
+constexpr uint32_t RS_GRID = 1024;         // blocks at most ...
+constexpr uint64_t RS_GPB_MIN = 4;         // ... each walking at least this many groups (the carry's run)
+
+// reg_inside's sibling: the index of the interval that holds the site, RS_NONE for none or no site; every lane
+// of the wave calls it
+__device__ __forceinline__ uint32_t reg_index(Reader& R, const Head& h, bool site, const sid_regtab& T)
+{
+    const uint64_t act = __ballot(site);
+    if (!act) return RS_NONE;   // (wave-uniform)
+    const int lead = __ffsll((unsigned long long)act) - 1;
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool is_lead = (int)lane == lead;
+    const uint64_t c8 = site ? reg_c8(R, h) : 0;
+    const uint64_t c8L = shfl64(c8, lead), cbL = shfl64(h.cb, lead);
+    const uint32_t clenL = (uint32_t)__shfl((int)h.clen, lead, 64);
+    const int32_t posL = __shfl(h.pos, lead, 64);
+    // the leader's chrom and its interval range
+    int32_t kL = -1;
+    uint32_t ibL = 0, ieL = 0;
+    if (T.nc <= 64) {   // (wave-uniform) a lane per chrom of the set: one round trip
+        const bool v = lane < T.nc;
+        const uint64_t m8 = v ? T.c8[lane] : 0;
+        const uint32_t ml = v ? T.clen[lane] : 0, b0 = v ? T.ibeg[lane] : 0, b1 = v ? T.ibeg[lane + 1] : 0;
+        bool hit = v && m8 == c8L && ml == clenL;
+        if (hit && clenL > 8) hit = reg_name_eq(R.text, R.limit, cbL, clenL, T.names + T.noff[lane]);
+        const uint64_t hm = __ballot(hit);
+        if (hm) {
+            kL = __ffsll((unsigned long long)hm) - 1;
+            ibL = (uint32_t)__shfl((int)b0, kL, 64);
+            ieL = (uint32_t)__shfl((int)b1, kL, 64);
+        }
+    } else {
+        int32_t k1 = -1;
+        if (is_lead) k1 = reg_chrom(R, h, c8, T);
+        kL = __shfl(k1, lead, 64);
+        if (kL >= 0) ibL = T.ibeg[kL], ieL = T.ibeg[kL + 1];
+    }
+    // the leader's interval (the first of its chrom with end >= its position) and the next one, for every lane
+    int32_t iv[4] = {INT32_MAX, INT32_MAX, INT32_MAX, INT32_MAX};
+    uint32_t idxL = 0;
+    if (kL >= 0) idxL = reg_lower_wave(T.start, T.end, ibL, ieL, posL, iv);   // (wave-uniform)
+    if (!site) return RS_NONE;
+    bool same = is_lead || (c8 == c8L && h.clen == clenL);
+    if (same && !is_lead && h.clen > 8)
+        same = kL >= 0 && reg_name_eq(R.text, R.limit, h.cb, h.clen, T.names + T.noff[kL]);
+    const int32_t k = same ? kL : reg_chrom(R, h, c8, T);
+    if (k < 0) return RS_NONE;
+    if (same && h.pos >= posL) {   // at or past the leader: its interval, the next, or a search on from there
+        // (no interval at or past the leader: iv is INT32_MAX throughout, and no position is above it)
+        if (h.pos <= iv[1]) return iv[0] < h.pos ? idxL : RS_NONE;
+        if (h.pos <= iv[3]) return iv[2] < h.pos ? idxL + 1 : RS_NONE;
+        if (idxL + 2 >= ieL) return RS_NONE;
+        const uint32_t idx = reg_lower(T.end, idxL + 2, ieL, h.pos);
+        return idx < ieL && T.start[idx] < h.pos ? idx : RS_NONE;
+    }
+    const uint32_t ib = T.ibeg[k], ie = T.ibeg[k + 1];
+    const uint32_t idx = reg_lower(T.end, ib, ie, h.pos);
+    return idx < ie && T.start[idx] < h.pos ? idx : RS_NONE;
+}
+
+template <class Off>
+struct RsArgs {
+    SiteArgs<Off> A;              // the sites; A.T the region set
+    uint64_t ng;                  // their 512-slot groups
+    uint64_t gpb;                 // ... and how many of them a block walks
+    sid_rs_bin* bins;             // per interval of A.T
+    unsigned long long* cnt;      // the rows appended
+    sid_rs_row* rows;
+    uint32_t cap;                 // (A.T.ni: every interval fits)
+};
+
+// s sites (>= 1) of summed depth d, h het and m hom records of interval j (< cap) into the table
+__device__ __forceinline__ void rs_table_add(sid_rs_bin* bins, unsigned long long* cnt, sid_rs_row* rows, uint32_t cap,
+                                             uint32_t j, uint32_t s, uint32_t h, uint32_t m, unsigned long long d)
+{
+    if (j >= cap) return;   // (never: reg_index returns an index of the table)
+    sid_rs_bin* b = bins + j;
+    const uint32_t old = atomicAdd(&b->sites, s);
+    if (h) atomicAdd(&b->het, h);
+    if (m) atomicAdd(&b->hom, m);
+    if (d) atomicAdd(&b->depth, d);
+    if (old == 0) {   // the bin's first sites of this chunk: its row
+        const unsigned long long at = atomicAdd(cnt, 1ull);
+        if (at < cap) rows[at].idx = j;
+    }
+}
+
+template <int MODE, bool OPT, int FORM, class Off>
+__global__ __launch_bounds__(FTB) void sid_region_stats_kernel(const RsArgs<Off> C)
+{
+    __shared__ uint32_t l_idx[FTB / 64], l_s[FTB / 64], l_h[FTB / 64], l_m[FTB / 64];
+    __shared__ unsigned long long l_d[FTB / 64];
+    const SiteArgs<Off>& A = C.A;
+    const uint32_t lane = threadIdx.x & 63u;
+    Reader R{A.text, A.len};
+    // the wave's carry: the sums of its current interval (wave-uniform)
+    uint32_t cur = RS_NONE, cs = 0, ch = 0, cm = 0;
+    unsigned long long cd = 0;
+    const uint64_t g0 = (uint64_t)blockIdx.x * C.gpb, g1 = min(g0 + C.gpb, C.ng);
+    for (uint64_t g = g0; g < g1; ++g) {
+        const uint64_t i = A.s0 + g * FTB + threadIdx.x;
+        uint32_t w;
+        const bool site = sv_site<MODE, OPT, 0>(A, i, &w);   // (the unselected parse, as the window stage)
+        bool rec = false, het = false;
+        uint32_t d = 0;
+        Head h{};
+        if (site) {
+            sv_label<MODE>(A, i, w, &rec, &het);
+            d = sv_depth<MODE, OPT>(A, i, w);
+            h = sv_head<MODE, OPT>(A, i, w, R);
+        }
+        const uint32_t idx = reg_index(R, h, site, A.T);
+        const bool rh = rec && het, rm = rec && !het;
+        unsigned long long left = __ballot(idx != RS_NONE);
+        for (uint32_t round = 0; left && round < RS_ROUNDS; ++round) {   // (wave-uniform)
+            const int src = __ffsll((long long)left) - 1;
+            const uint32_t iv = (uint32_t)__shfl((int)idx, src, 64);
+            const bool mine = idx == iv;
+            const unsigned long long bm = __ballot(mine);
+            const uint32_t s = (uint32_t)__popcll(bm), nh = (uint32_t)__popcll(__ballot(mine && rh)),
+                           nm = (uint32_t)__popcll(__ballot(mine && rm));
+            const uint32_t ds = wave_sum(mine ? d : 0u);   // (64 depths of at most 262140)
+            if (FORM == 0) {
+                if (iv != cur) {
+                    if (cur != RS_NONE && lane == 0) rs_table_add(C.bins, C.cnt, C.rows, C.cap, cur, cs, ch, cm, cd);
+                    cur = iv, cs = 0, ch = 0, cm = 0, cd = 0;
+                }
+                cs += s, ch += nh, cm += nm, cd += ds;
+            } else if ((int)lane == src) {
+                rs_table_add(C.bins, C.cnt, C.rows, C.cap, iv, s, nh, nm, ds);
+            }
+            left &= ~bm;
+        }
+        if ((left >> lane) & 1ull) rs_table_add(C.bins, C.cnt, C.rows, C.cap, idx, 1u, rh, rm, d);
+    }
+    if (FORM != 0) return;
+    // the block's end: the waves' carries meet, equal intervals summed
+    if (lane == 0) {
+        const uint32_t wv = threadIdx.x >> 6;
+        l_idx[wv] = cur, l_s[wv] = cs, l_h[wv] = ch, l_m[wv] = cm, l_d[wv] = cd;
+    }
+    __syncthreads();
+    if (threadIdx.x < FTB / 64) {
+        const uint32_t t = threadIdx.x, j = l_idx[t];
+        bool first = j != RS_NONE;
+        for (uint32_t q = 0; q < t; ++q) first = first && l_idx[q] != j;
+        if (first) {
+            uint32_t s = 0, nh = 0, nm = 0;
+            unsigned long long ds = 0;
+            for (uint32_t q = t; q < FTB / 64; ++q)
+                if (l_idx[q] == j) s += l_s[q], nh += l_h[q], nm += l_m[q], ds += l_d[q];
+            rs_table_add(C.bins, C.cnt, C.rows, C.cap, j, s, nh, nm, ds);
+        }
+    }
+}
+
+// (one block, as the histogram's pack: the block that has read the count is the one that clears it.  out: where
+// the count goes -- the set's pinned block, or a call's own word)
+__global__ __launch_bounds__(SCAN_TB) void sid_region_stats_pack_kernel(unsigned long long* __restrict__ cnt,
+                                                                        sid_rs_bin* __restrict__ bins,
+                                                                        sid_rs_row* __restrict__ rows, uint32_t cap,
+                                                                        char* __restrict__ eager,
+                                                                        unsigned long long* __restrict__ out)
+{
+    const uint64_t n = min((uint64_t)cnt[0], (uint64_t)cap);
+    __syncthreads();
+    if (threadIdx.x == 0) cnt[0] = 0;   // (zero again for the next chunk, as the bins)
+    if (threadIdx.x < 2) out[threadIdx.x] = threadIdx.x ? 0ull : n;
+    sid_rs_row* er = eager ? (sid_rs_row*)(eager + 16) : nullptr;
+    for (uint64_t k = threadIdx.x; k < n; k += SCAN_TB) {
+        sid_rs_row r = rows[k];
+        if (r.idx >= cap) continue;   // (never: rs_table_add stores a bin's index)
+        sid_rs_bin* b = bins + r.idx;
+        r.depth = b->depth, r.sites = b->sites, r.het = b->het, r.hom = b->hom;
+        b->depth = 0, b->sites = b->het = b->hom = 0;
+        rows[k] = r;
+        if (er && k < SID_RS_EAGER_ROWS) er[k] = r;
+    }
+}
+
+// 0: the carry; 1: every wave adds its rounds' sums to the table (SID_RS_FORM, a measurement switch)
+static int rs_form()
+{
+    static const int form = [] {
+        const char* g = std::getenv("SID_RS_FORM");
+        return g ? (std::atoi(g) != 0) : 0;
+    }();
+    return form;
+}
+
+// the stage's device buffers: sid_chunk_ws's rs_* (the engine) or a call's own
+struct RsBufs {
+    sid_rs_bin* bins;
+    unsigned long long* cnt;
+    sid_rs_row* rows;
+    char* eager;               // (or null: the caller copies the rows)
+    unsigned long long* out;   // two words for the chunk's row count: the head of `eager`, or a call's own
+};
+
+// the region rows of A's sites (A.T: the set, whose ni bins and rows B holds) into B's rows; B.bins and B.cnt
+// are all zero before and after
+template <int MODE, bool OPT, class Off>
+static void launch_region_stats(const SiteArgs<Off>& A, const RsBufs& B, hipStream_t st)
+{
+    RsArgs<Off> C{};
+    C.A = A;
+    C.ng = (A.s1 - A.s0 + FTB - 1) / FTB;
+    C.bins = B.bins, C.cnt = B.cnt, C.rows = B.rows, C.cap = A.T.ni;
+    if (C.ng && A.T.ni) {
+        C.gpb = std::max<uint64_t>((C.ng + RS_GRID - 1) / RS_GRID, RS_GPB_MIN);
+        const uint64_t grid = (C.ng + C.gpb - 1) / C.gpb;
+        if (rs_form()) sid_region_stats_kernel<MODE, OPT, 1, Off><<<(unsigned)grid, FTB, 0, st>>>(C);
+        else sid_region_stats_kernel<MODE, OPT, 0, Off><<<(unsigned)grid, FTB, 0, st>>>(C);
+    }
+    sid_region_stats_pack_kernel<<<1, SCAN_TB, 0, st>>>(B.cnt, B.bins, B.rows, A.T.ni, B.eager, B.out);
+}
+
 // --------------------------------------------------------- callable runs --
 // The callable runs (sid_dtext_callable; callable.h): the rows of a site range,
 // a row being a maximal run of consecutive sites that are all callable -- a
@@ -6063,6 +6316,55 @@ extern "C" int sid_dtext_depth_hist(sid_ctx* ctx, const sid_dtext* T, size_t beg
     return sid_dh_export(tab, rows, n);
 }
 
+// The region rows' stage over a resident shard, for the context's set: a table, a count and rows of this call's own.
+extern "C" int sid_dtext_region_stats(sid_ctx* ctx, const sid_dtext* T, size_t begin, size_t end, const uint8_t* d_code,
+                                      sid_region_row** rows, size_t* n, void* stream)
+{
+    if (!ctx || !T || !rows || !n) return SID_EINVAL;
+    *rows = nullptr, *n = 0;
+    if (end > T->nsites || begin > end || (end > begin && !d_code)) return SID_EINVAL;
+    const sid_regions* rg = ctx->regions_host;
+    if (!rg || !ctx->d_regions || sid_region_stats_valid(rg) != SID_OK || ctx->regtab.ni != rg->start.size()) return SID_EINVAL;
+    const size_t ni = rg->start.size();
+    std::vector<sid_rs_sum> tab(ni);
+    if (end == begin || ni == 0) return sid_rs_export(rg, tab, true, rows, n);
+    if (end - begin >= (1ull << 32)) return SID_EINVAL;   // (the stage's counters are a chunk's: 32 bits)
+    TCHECK(hipSetDevice(T->device));
+    hipStream_t st = (hipStream_t)stream;
+    const size_t o_rows = (ni * sizeof(sid_rs_bin) + 15) & ~(size_t)15, o_cnt = o_rows + ni * sizeof(sid_rs_row);
+    char* d_ws = nullptr;
+    int rc = SID_OK;
+    auto hip = [&](hipError_t x) {
+        if (x != hipSuccess && rc == SID_OK) rc = sid_set_hip_error(x);
+        return rc == SID_OK;
+    };
+    std::vector<sid_rs_row> ch;
+    // (the call's words behind the rows: [0] the stage's count, [2] [3] the pack's copy of it)
+    if (hip(hipMalloc(&d_ws, o_cnt + 32)) && hip(hipMemsetAsync(d_ws, 0, o_rows, st)) &&
+        hip(hipMemsetAsync(d_ws + o_cnt, 0, 32, st))) {
+        const RsBufs B{(sid_rs_bin*)d_ws, (unsigned long long*)(d_ws + o_cnt), (sid_rs_row*)(d_ws + o_rows), nullptr,
+                       (unsigned long long*)(d_ws + o_cnt + 16)};
+        SiteArgs<uint64_t> A = dtext_view(T, begin, end, const_cast<uint8_t*>(d_code));
+        A.T = ctx->regtab;
+        launch_region_stats<REG_CODE, false>(A, B, st);
+        hip(hipGetLastError());
+        unsigned long long nr = 0;
+        hip(hipMemcpyAsync(&nr, B.out, 8, hipMemcpyDeviceToHost, st));
+        hip(hipStreamSynchronize(st));
+        if (rc == SID_OK && nr > ni) rc = SID_ESTATE;
+        if (rc == SID_OK && nr) {
+            ch.resize(nr);
+            hip(hipMemcpyAsync(ch.data(), B.rows, nr * sizeof(sid_rs_row), hipMemcpyDeviceToHost, st));
+            hip(hipStreamSynchronize(st));
+        }
+    }
+    if (d_ws) (void)hipFree(d_ws);
+    if (rc != SID_OK) return rc;
+    if (!sid_rs_check(ch, ni)) return SID_ESTATE;
+    sid_rs_add(&tab, ch);
+    return sid_rs_export(rg, tab, true, rows, n);
+}
+
 // The callable stage over a resident shard: buffers of this call's own, the rows sized from the counts, the
 // context's depth bounds.
 extern "C" int sid_dtext_callable(sid_ctx* ctx, const sid_dtext* T, size_t begin, size_t end, const uint8_t* d_code,
@@ -6329,6 +6631,21 @@ static int depth_hist_stage(const SiteArgs<Off>& A, sid_chunk_ws* W, hipStream_t
     return SID_OK;
 }
 
+// The region rows' stage of one chunk, beside the histogram's: the next set's count, rows and pinned block.  A
+// set holds every interval, so there is nothing to size and no chunk runs again for it.
+template <int MODE, bool OPT, class Off>
+static int region_stats_stage(const SiteArgs<Off>& S, sid_chunk_ws* W, hipStream_t st)
+{
+    if (!W->rs_bins || !W->rs_tab || W->rs_tab->ni != W->rs_ni) return SID_ESTATE;   // (a workspace not reserved)
+    const int b = (W->rs_cur ^= 1);
+    SiteArgs<Off> A = S;
+    A.T = *W->rs_tab;
+    launch_region_stats<MODE, OPT>(A, RsBufs{W->rs_bins, W->rs_cnt[b], W->rs_rows[b], W->rs_eager[b],
+                                             (unsigned long long*)W->rs_eager[b]}, st);
+    WCHECK(hipGetLastError());
+    return SID_OK;
+}
+
 int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites)
 {
     // grow-only; hipFree waits for the device, so buffers still in use by
@@ -6360,6 +6677,20 @@ int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites)
             WCHECK(hipMalloc(&W->dh_rows[b], (size_t)SID_DH_BINS * sizeof(sid_dh_row)));
             WCHECK(hipHostMalloc((void**)&W->dh_eager[b], SID_DH_EAGER_BYTES, hipHostMallocDefault));
             std::memset(W->dh_eager[b], 0, SID_DH_EAGER_BYTES);
+        }
+    }
+    if (W->rs_on && !W->rs_bins) {   // the region rows' table and its two sets, likewise
+        if (!W->rs_tab || W->rs_tab->ni > SID_REGION_STATS_MAX) return SID_ESTATE;
+        const size_t ni = std::max<size_t>(W->rs_tab->ni, 1);
+        W->rs_ni = W->rs_tab->ni;
+        WCHECK(hipMalloc(&W->rs_bins, ni * sizeof(sid_rs_bin)));
+        WCHECK(hipMemset(W->rs_bins, 0, ni * sizeof(sid_rs_bin)));
+        for (int b = 0; b < 2; ++b) {
+            WCHECK(hipMalloc(&W->rs_cnt[b], 8));
+            WCHECK(hipMemset(W->rs_cnt[b], 0, 8));
+            WCHECK(hipMalloc(&W->rs_rows[b], ni * sizeof(sid_rs_row)));
+            WCHECK(hipHostMalloc((void**)&W->rs_eager[b], SID_RS_EAGER_BYTES, hipHostMallocDefault));
+            std::memset(W->rs_eager[b], 0, SID_RS_EAGER_BYTES);
         }
     }
     const uint64_t tiles = ((bytes + 16 + IX_TILE - 1) / IX_TILE + 1) * IX_SUB;   // 4 KiB tiles, in whole index tiles
@@ -6447,12 +6778,15 @@ void sid_chunk_release(sid_chunk_ws* W)
                     (void*)W->win_bits, W->win_key, (void*)W->win_hcnt, (void*)W->win_roff, (void*)W->win_cnt[0],
                     (void*)W->win_cnt[1], (void*)W->win_rows[0], (void*)W->win_rows[1], (void*)W->win_names[0],
                     (void*)W->win_names[1], (void*)W->refb, (void*)W->dh_bins, (void*)W->dh_cnt[0],
-                    (void*)W->dh_cnt[1], (void*)W->dh_rows[0], (void*)W->dh_rows[1]})
+                    (void*)W->dh_cnt[1], (void*)W->dh_rows[0], (void*)W->dh_rows[1], (void*)W->rs_bins,
+                    (void*)W->rs_cnt[0], (void*)W->rs_cnt[1], (void*)W->rs_rows[0], (void*)W->rs_rows[1]})
         if (p) (void)hipFree(p);
     for (void* p : {(void*)W->win_h, (void*)W->win_eager[0], (void*)W->win_eager[1], (void*)W->dh_eager[0],
-                    (void*)W->dh_eager[1]})
+                    (void*)W->dh_eager[1], (void*)W->rs_eager[0], (void*)W->rs_eager[1]})
         if (p) (void)hipHostFree(p);
     const bool dh_on = W->dh_on;
+    const bool rs_on = W->rs_on;
+    const sid_regtab* rs_tab = W->rs_tab;
     const int select = W->select;   // (the owner's options, not the buffers')
     const sid_regtab* regions = W->regions;
     const int cx_n = W->cx_n, cx_select = W->cx_select;
@@ -6465,6 +6799,7 @@ void sid_chunk_release(sid_chunk_ws* W)
     const bool vcf = W->vcf;
     *W = sid_chunk_ws{};
     W->dh_on = dh_on;
+    W->rs_on = rs_on, W->rs_tab = rs_tab;
     W->vcf = vcf;
     W->depth = depth, W->cx_depth = cx_depth, W->depth_min = depth_min, W->depth_max = depth_max;
     W->window = window;
@@ -6479,6 +6814,7 @@ void sid_chunk_bind_context(sid_chunk_ws* W, const sid_ctx* ctx)
 {
     W->select = ctx->opts.select;   // (SID_SELECT_ALL under a context: the marking stage selects)
     W->regions = ctx->has_regions ? &ctx->regtab : nullptr;
+    W->rs_tab = ctx->d_regions ? &ctx->regtab : nullptr;   // (the region rows: the set whatever selects)
     W->cx_n = ctx->cx_n;
     W->cx_on = ctx->cx_on;
     W->window = ctx->opts.window;
@@ -6622,6 +6958,10 @@ int sid_chunk_fmt_len(sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n
         const int rc = depth_hist_stage<REG_CODE, false>(S, W, st);
         if (rc != SID_OK) return rc;
     }
+    if (W->rs_on) {   // the region rows, likewise
+        const int rc = region_stats_stage<REG_CODE, false>(S, W, st);
+        if (rc != SID_OK) return rc;
+    }
     if (W->regions) {   // the sites outside the region set: dropped in the workspace's codes
         SiteArgs<sid_off_t> A = S;
         A.xm = sel_word(W->select), A.T = *W->regions;
@@ -6711,6 +7051,11 @@ int sid_chunk_local_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     if (W->dh_on) {   // the depth histogram, likewise
         const int rc = W->cls_ready ? depth_hist_stage<REG_DENSE, false>(S, W, st)
                                     : depth_hist_stage<REG_DENSE, true>(S, W, st);
+        if (rc != SID_OK) return rc;
+    }
+    if (W->rs_on) {   // the region rows, likewise
+        const int rc = W->cls_ready ? region_stats_stage<REG_DENSE, false>(S, W, st)
+                                    : region_stats_stage<REG_DENSE, true>(S, W, st);
         if (rc != SID_OK) return rc;
     }
     if (nb && ctx->has_regions) {
@@ -6928,7 +7273,7 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
     if (ntp * tile_nwv(cap) > W->site_cap / 32 + 1) return SID_EINVAL;   // (never: cap >= 64)
     const bool vcf = ctx->format == SID_FORMAT_VCF;
     if ((ctx->has_variants || ctx->cx_variants || vcf) && slots && !W->refb) return SID_ESTATE;   // (a workspace not bound)
-    if ((vcf || ctx->has_regions || ctx->has_variants || ctx->has_depth || ctx->cx_on || W->window || W->dh_on) && slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (the marking kernels' slot_tile: its exact range, as the writer's)
+    if ((vcf || ctx->has_regions || ctx->has_variants || ctx->has_depth || ctx->cx_on || W->window || W->dh_on || W->rs_on) && slots >= SID_SLOTS_MAX) return SID_EINVAL;   // (the marking kernels' slot_tile: its exact range, as the writer's)
     W->lens_ready = false;
     W->cls_ready = false;
     W->slot_cap = cap;
@@ -6946,6 +7291,10 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
         }
         if (W->dh_on) {   // (likewise)
             const int rc = depth_hist_stage<REG_TILE, false>(S, W, st);
+            if (rc != SID_OK) return rc;
+        }
+        if (W->rs_on) {   // (likewise)
+            const int rc = region_stats_stage<REG_TILE, false>(S, W, st);
             if (rc != SID_OK) return rc;
         }
         if (ctx->cx_on) launch_context_mark<REG_TILE, false>(S, W, st);   // (the empty descriptor)
@@ -6973,6 +7322,10 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
     }
     if (W->dh_on) {   // the depth histogram, likewise
         const int rc = quad ? depth_hist_stage<REG_TILE, false>(S, W, st) : depth_hist_stage<REG_TILE, true>(S, W, st);
+        if (rc != SID_OK) return rc;
+    }
+    if (W->rs_on) {   // the region rows, likewise
+        const int rc = quad ? region_stats_stage<REG_TILE, false>(S, W, st) : region_stats_stage<REG_TILE, true>(S, W, st);
         if (rc != SID_OK) return rc;
     }
     if (ctx->has_regions) {   // the slots outside the region set: the skip word, and their groups' sums again
@@ -7073,6 +7426,10 @@ int sid_chunk_lynch_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
     }
     if (W->dh_on) {   // the depth histogram, likewise
         const int rc = depth_hist_stage<REG_LYNCH, false>(S, W, st);
+        if (rc != SID_OK) return rc;
+    }
+    if (W->rs_on) {   // the region rows, likewise
+        const int rc = region_stats_stage<REG_LYNCH, false>(S, W, st);
         if (rc != SID_OK) return rc;
     }
     if (ctx->cx_on) {   // the context: counts 0 likewise (no class or no site: the empty descriptor)
