@@ -12,36 +12,15 @@
 
 void sid_call_table::push(const char* chrom, uint32_t clen, int64_t start, int64_t end, uint64_t het, bool join)
 {
-    if (!rows.empty()) {
-        sid_callable_row& l = rows.back();
-        const char* ln = names.data() + name_off.back();
-        const bool same_chrom = l.chrom_len == clen && (clen == 0 || std::memcmp(ln, chrom, clen) == 0);
-        if (join && open && same_chrom && l.end == start) {
-            l.end = end, l.het += het;
-            return;
-        }
-        if (same_chrom) {   // (the chrom's bytes once per run of its rows)
-            name_off.push_back(name_off.back());
-            rows.push_back(sid_callable_row{nullptr, clen, 0, start, end, het});
-            return;
-        }
+    const bool same = same_chrom(chrom, clen);
+    if (join && open && same && rows.back().end == start) {
+        rows.back().end = end, rows.back().het += het;
+        return;
     }
-    name_off.push_back(names.size());
-    names.append(chrom, clen);
-    rows.push_back(sid_callable_row{nullptr, clen, 0, start, end, het});
+    append(sid_callable_row{nullptr, clen, 0, start, end, het}, chrom, same);
 }
 
-void sid_call_table::finish()
-{
-    for (size_t k = 0; k < rows.size(); ++k) rows[k].chrom = names.data() + name_off[k];
-}
-
-static const char* row_chrom(const sid_call_row& r, const char* names, char (&tmp)[8])
-{
-    if (r.clen > 8) return names + r.name;
-    for (int k = 0; k < 8; ++k) tmp[k] = (char)(r.c8 >> (8 * k));
-    return tmp;
-}
+void sid_call_table::finish() { sid_row_table::finish(); }   // (its own symbol, as push)
 
 // one chunk's rows and edge bits into the table
 static void push_chunk(sid_call_table* t, const sid_call_row* rows, size_t n, const char* names, uint32_t edge)
@@ -51,7 +30,7 @@ static void push_chunk(sid_call_table* t, const sid_call_row* rows, size_t n, co
     for (size_t k = 0; k < n; ++k) {
         const sid_call_row& r = rows[k];
         const int64_t start = (int64_t)r.pos - 1;
-        t->push(row_chrom(r, names, tmp), r.clen, start, start + (int64_t)r.sites, r.het,
+        t->push(sid_row_chrom(r, names, tmp), r.clen, start, start + (int64_t)r.sites, r.het,
                 k == 0 && (edge & SID_CALL_OPEN_START));
         t->open = false;   // (a chunk's rows never join one another)
     }
@@ -63,23 +42,7 @@ void sid_call_stitch_push(sid_call_table* t, const sid_call_chunk& c)
     push_chunk(t, c.rows.data(), c.rows.size(), c.names.data(), c.edge);
 }
 
-int sid_call_export(const sid_call_table& t, sid_callable_row** out, size_t* n)
-{
-    const size_t nr = t.rows.size();
-    // one allocation: the rows, then the names (sid_callable_free frees the rows' pointer)
-    char* mem = (char*)std::malloc(std::max<size_t>(nr * sizeof(sid_callable_row) + t.names.size(), 1));
-    if (!mem) return SID_ENOMEM;
-    sid_callable_row* rows = (sid_callable_row*)mem;
-    char* nm = mem + nr * sizeof(sid_callable_row);
-    if (!t.names.empty()) std::memcpy(nm, t.names.data(), t.names.size());
-    for (size_t k = 0; k < nr; ++k) {
-        rows[k] = t.rows[k];
-        rows[k].chrom = nm + t.name_off[k];
-    }
-    *out = rows;
-    *n = nr;
-    return SID_OK;
-}
+int sid_call_export(const sid_call_table& t, sid_callable_row** out, size_t* n) { return t.export_rows(out, n); }
 
 extern "C" void sid_callable_free(sid_callable_row* rows) { std::free(rows); }
 
@@ -117,15 +80,7 @@ extern "C" int sid_callable_host(const sid_sites* s, size_t begin, size_t end, c
     if (!s || begin > end || end > s->pos.size() || s->counts.size() != 4 * s->pos.size()) return SID_EINVAL;
     if (end > begin && !code_all) return SID_EINVAL;
     sid_call_table t;
-    size_t k = 0;   // the chromosome run holding `begin`
-    {
-        size_t lo = 0, hi = s->seg_start.size();
-        while (lo + 1 < hi) {
-            const size_t mid = (lo + hi) / 2;
-            if (s->seg_start[mid] <= begin) lo = mid; else hi = mid;
-        }
-        k = lo;
-    }
+    size_t k = sid_seg_of(s->seg_start, begin);
     for (size_t i = begin; i < end; ++i) {
         while (k + 1 < s->seg_start.size() && s->seg_start[k + 1] <= i) ++k;
         const std::string& nm = s->seg_name[k];
@@ -162,19 +117,6 @@ extern "C" int sid_callable_join(const sid_callable_row* a, size_t na, int a_ope
     return sid_call_export(t, out, n);
 }
 
-// decimal digits of v at p; returns their number
-static size_t put_i64(int64_t v, char* p)
-{
-    char tmp[24];
-    size_t k = 0;
-    uint64_t u = v < 0 ? 0 - (uint64_t)v : (uint64_t)v;
-    do tmp[k++] = (char)('0' + u % 10); while (u /= 10);
-    size_t w = 0;
-    if (v < 0) p[w++] = '-';
-    while (k) p[w++] = tmp[--k];
-    return w;
-}
-
 extern "C" int sid_callable_format(const sid_callable_row* rows, size_t n, char* buf, size_t cap, size_t* len)
 {
     if (!len || (n && !rows)) return SID_EINVAL;
@@ -190,17 +132,11 @@ extern "C" int sid_callable_format(const sid_callable_row* rows, size_t n, char*
         put(r.chrom, r.chrom_len);
         size_t w = 0;
         line[w++] = '\t';
-        w += put_i64(r.start, line + w);
+        w += sid_put_i64(r.start, line + w);
         line[w++] = '\t';
-        w += put_i64(r.end, line + w);
+        w += sid_put_i64(r.end, line + w);
         line[w++] = '\t';
-        {   // (het: unsigned)
-            char tmp[24];
-            size_t j = 0;
-            uint64_t u = r.het;
-            do tmp[j++] = (char)('0' + u % 10); while (u /= 10);
-            while (j) line[w++] = tmp[--j];
-        }
+        w += sid_put_u64(r.het, line + w);
         line[w++] = '\n';
         put(line, w);
     }

@@ -2,11 +2,11 @@
 // (site ranges') row lists, their stitch in file order, the rows of the
 // host path (sid_callable_host), the join of two neighbouring row lists and the
 // BED formatter.  No HIP here: callable.cpp builds into a stand-alone host
-// program (tests/asan_callable).
+// program (tests/asan).
 //
 // A row is a maximal run of consecutive sites that are all callable (sid.h
 // Conventions), with byte-equal chrom and each pos the previous pos + 1.  The
-// device finds the runs of one chunk (textpath.hip, sid_callable_*_kernel): a
+// device finds the runs of one chunk (textpath.hip, the run rows' CallRuns): a
 // chunk's first site, if callable, always opens a row, so a run that crosses a
 // chunk edge comes back as two rows, which the stitch joins -- through chunks
 // without a site, and only when the earlier chunk's last site lies in its last
@@ -19,7 +19,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/sid.h"
+#include "rowtable.h"
 
 // One row as the device writes it and the host reads it back.
 struct sid_call_row {
@@ -51,18 +51,12 @@ struct sid_call_chunk {
     }
 };
 
-// The rows of a run: what sid_callable_host and sid_dtext_callable hand out.  The chrom pointers
-// point into `names` and are set by finish().
-struct sid_call_table {
-    std::vector<sid_callable_row> rows;
-    std::vector<uint64_t> name_off;
-    std::string names;
+// The rows of a run: what sid_callable_host and sid_dtext_callable hand out (rowtable.h).
+struct sid_call_table : sid_row_table<sid_callable_row> {
     bool open = false;   // the last site pushed lies in the last row
     void clear()
     {
-        rows.clear();
-        name_off.clear();
-        names.clear();
+        sid_row_table::clear();
         open = false;
     }
     // one more row in file order; join: its first site follows the table's last site with nothing between

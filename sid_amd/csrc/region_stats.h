@@ -2,8 +2,7 @@
 // FILE) on the host: the chunks' row lists as the device hands them back, their
 // sum in a dense table of one entry per interval, the rows of the host path
 // (sid_region_stats_host), the merge and the CSV formatter.  No HIP here:
-// region_stats.cpp builds into a stand-alone host program
-// (tests/asan_region_stats).
+// region_stats.cpp builds into a stand-alone host program (tests/asan).
 //
 // A row is one interval of the region set after its merge.  The device bins
 // the sites of one chunk by the interval's index in the flat table

@@ -260,7 +260,7 @@ struct sid_chunk_ws {
     uint4* cx_car = nullptr;
     uint8_t* cx_hk = nullptr;   // 2 x SID_CONTEXT_MAX bytes: head zone, tail zone
     struct sid_cx_desc* cx_desc = nullptr;
-    // the window stage (the owner's sid_opts.window; windows.h, textpath.hip sid_window_*_kernel), in front
+    // the window stage (the owner's sid_opts.window; windows.h, textpath.hip sid_runs_*_kernel), in front
     // of the marking stages: per 64 slots four ballots, two keys, the head count and its scan (sized with
     // the sites), and two sets of {counts, rows, name blob} used in turn -- a chunk's tile parse runs behind
     // the previous chunk's writer, before the host has read that chunk's rows.  win_cnt: [0] the chunk's

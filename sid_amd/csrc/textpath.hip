@@ -4533,29 +4533,45 @@ static void launch_context_edge(const sid_chunk_ws* W, const char* out, hipStrea
     sid_context_edge_kernel<<<2, 64, 0, st>>>(out, W->lb + 1, (uint32_t)W->cx_n, W->cx_hk, W->cx_desc);
 }
 
-// ---------------------------------------------------------------- windows --
-// The windowed summary (sid_opts.window = W; windows.h): the rows of a chunk,
-// a row being a maximal run of consecutive sites with equal (chrom, wi), wi =
-// floor((pos - 1) / W).  The stage reads what the marking stages above read --
-// the slot's site, class word / counts / code and Head, through their loaders
-// -- and runs in front of them, on the unselected labels.  Four steps:
-//   flag   per slot: holds a site, prints a record, is het (wave ballots), and
-//          whether its key differs from the previous site's of its wave (the
-//          ballot's nearest lower lane, its key by shuffle); per wave its first
-//          and last site's key.  A wave's first site waits for the link.
+// ------------------------------------------------- windows, callable runs --
+// The run rows of a range of slots, a row being a maximal run of consecutive
+// sites that a policy joins.  One stage, two policies:
+//   WinRuns   the windowed summary (sid_opts.window = W; windows.h).  Every site
+//             is in a run; a site goes on the previous site's run when their
+//             (chrom, wi) are equal, wi = floor((pos - 1) / W).  Word [1]: the
+//             sites that print a record, [2]: those that are het.
+//   CallRuns  the callable runs (sid_dtext_callable; callable.h).  Only the
+//             callable sites -- a record in the unselected output, a depth >= 1
+//             within the bounds A.dmin, A.dmax, pos >= 1 -- are in a run; a site
+//             goes on the previous site's run when that site is callable, the
+//             chroms are equal and its pos is the previous pos + 1 in 64 bits.
+//             Word [1]: the callable sites, [2]: those that are het.  GAPS: a
+//             run also ends at a site that is not in one, a key carries its
+//             site's callable bit, and the link stores the chunk's edge words
+//             (the first site's callable bit, and by an atomic max over the
+//             waves the last site's).
+// The stage reads what the marking stages above read -- the slot's site, class
+// word / counts / code and Head, through their loaders -- on the unselected
+// labels; the engine runs the windows in front of the marking stages.  Four steps:
+//   flag   per slot: holds a site, and the policy's two words (wave ballots),
+//          and whether it opens a row against the previous site of its wave
+//          (the ballot's nearest lower lane, its key by shuffle); per wave its
+//          first and last site's key.  A wave's first site waits for the link.
 //   link   one thread per wave: the nearest earlier wave with a site (slots
 //          past a tile's count, empty tiles and empty groups lie between) and
-//          its last key against this wave's first; the chunk's first site is a
-//          head.  The wave's head count, and the bytes of the heads' long names.
+//          its last key against this wave's first; the chunk's first site in a
+//          run is a head.  The wave's head count, and the bytes of the heads'
+//          long names.
 //   scan   exclusive scan of the waves' head counts: their first row's index,
-//          and the chunk's rows (win_cnt[0], read back with the byte count).
+//          and the chunk's rows (cnt[0], read back with the byte count).
 //   fill   a lane per head: its row's key, the chrom's bytes over 8 copied out
-//          of the text, and the popcounts of the three ballots masked to its
-//          run's lanes added to the row; lane 0 adds the lanes in front of the
-//          wave's first head to the row before.  A run of many waves costs three
-//          atomic adds a wave, not one a site.  Rows from `cap` on and names
-//          past `ncap` are dropped: the caller sees the counts and runs the
-//          chunk again with larger buffers.
+//          of the text, and the popcounts of the ballots masked to its run's
+//          lanes -- from the head up to, not including, the next break -- added
+//          to the row; lane 0 adds the lanes in front of the wave's first break
+//          to the row before.  A run of many waves costs the policy's adds a
+//          wave (three, two), not one a site.  Rows from `cap` on and names
+//          past `ncap` are dropped: the caller sees the counts and sizes both
+//          from them (the engine runs the chunk again with larger buffers).
 // Chroms over 8 bytes compare on their bytes in the text (as reg_name_eq).
 struct WinKey {
     uint64_t c8;
@@ -4564,37 +4580,42 @@ struct WinKey {
     uint32_t clen;
     uint32_t pad;
 };
-static_assert(sizeof(WinKey) == 32, "two keys a wave");
+struct CallKey {
+    uint64_t c8;
+    uint64_t cb;        // clen > 8: the chrom's offset in the text
+    uint32_t clen;
+    int32_t pos;
+    uint32_t callable;
+    uint32_t pad;
+};
+static_assert(sizeof(WinKey) == 32 && sizeof(CallKey) == 32, "two keys a wave");
 
-template <class Off>
-struct WinArgs {
-    SiteArgs<Off> A;              // the sites
-    int64_t W;
-    unsigned long long* bits;     // per wave of slots: [0] sites [1] records [2] het records [3] heads
-    WinKey* key;                  // per wave: [0] its first site's key, [1] its last site's
+struct NoArg {};
+
+template <class P, class Off>
+struct RunArgs {
+    SiteArgs<Off> A;              // the sites (CallRuns: A.dmin, A.dmax are the depth bounds)
+    [[no_unique_address]] typename P::Arg arg;   // WinRuns: W
+    unsigned long long* bits;     // per wave of slots: [0] sites [1] [2] the policy's words [3] heads
+    typename P::Key* key;         // per wave: [0] its first site's key, [1] its last site's
     uint32_t* hcnt;               // per wave: its heads
     const uint64_t* roff;         // ... and its first head's row
-    unsigned long long* cnt;      // [0] rows [1] name bytes [2] the fill's name cursor
-    sid_win_row* rows;
+    unsigned long long* cnt;      // [0] rows [1] name bytes [2] the fill's name cursor; GAPS: [3] the last wave with
+                                  // a site and its last site's callable bit [4] the first site's callable bit
+    typename P::Row* rows;
     uint32_t cap;
     char* names;
     uint32_t ncap;
 };
 
 // bytes [8, clen) of two chroms in the text
-__device__ __noinline__ bool win_name_eq(const char* text, uint64_t len, uint64_t a, uint64_t b, uint32_t clen)
+__device__ __noinline__ bool run_name_eq(const char* text, uint64_t len, uint64_t a, uint64_t b, uint32_t clen)
 {
     if (a == b) return true;
     Reader Ra{text, len}, Rb{text, len};
     for (uint32_t j = 8; j < clen; ++j)
         if (Ra.at(a + j) != Rb.at(b + j)) return false;
     return true;
-}
-
-__device__ __forceinline__ bool win_key_eq(const char* text, uint64_t len, const WinKey& a, const WinKey& b)
-{
-    if (a.c8 != b.c8 || a.clen != b.clen || a.wi != b.wi) return false;
-    return a.clen <= 8 || win_name_eq(text, len, a.cb, b.cb, a.clen);
 }
 
 __device__ __forceinline__ int64_t win_index(int32_t pos, int64_t W)
@@ -4605,22 +4626,138 @@ __device__ __forceinline__ int64_t win_index(int32_t pos, int64_t W)
     return -((-p + W - 1) / W);
 }
 
-template <int MODE, bool OPT, class Off>
-__device__ __forceinline__ WinKey win_key(const SiteArgs<Off>& A, uint64_t i, uint32_t w, Reader& R, int64_t W)
-{
-    const Head h = sv_head<MODE, OPT>(A, i, w, R);
-    WinKey k;
-    k.c8 = reg_c8(R, h);
-    k.wi = win_index(h.pos, W);
-    k.cb = h.clen > 8 ? h.cb : 0;
-    k.clen = h.clen;
-    k.pad = 0;
-    return k;
-}
+// A policy: the key and row types, the extra argument, the cnt words the count clears, and
+//   key      a slot's key from its Head
+//   site     a site's key and its three bits: is in a run, counts into word [1], and if so into word [2]
+//   shfl     lane src's key
+//   in       whether a key's site is in a run
+//   follows  whether site b, which follows site a with no site between, goes on a's run (both in one)
+//   store    a head's row
+//   add      the popcounts of the ballots under m onto a row (HEAD: the head's own add)
+struct WinRuns {
+    using Key = WinKey;
+    using Row = sid_win_row;
+    using Arg = int64_t;
+    static constexpr int CNT = 3;   // (sid_chunk_ws::win_cnt has 4 words)
+    static constexpr bool GAPS = false;
+    template <int MODE, bool OPT, class Off>
+    static __device__ __forceinline__ Key key(const SiteArgs<Off>& A, uint64_t i, uint32_t w, Reader& R, int64_t W)
+    {
+        const Head h = sv_head<MODE, OPT>(A, i, w, R);
+        Key k;
+        k.c8 = reg_c8(R, h);
+        k.wi = win_index(h.pos, W);
+        k.cb = h.clen > 8 ? h.cb : 0;
+        k.clen = h.clen;
+        k.pad = 0;
+        return k;
+    }
+    template <int MODE, bool OPT, class Off>
+    static __device__ __forceinline__ Key site(const SiteArgs<Off>& A, uint64_t i, uint32_t w, Reader& R, int64_t W,
+                                               bool* in, bool* b1, bool* b2)
+    {
+        sv_label<MODE>(A, i, w, b1, b2);
+        *in = true;
+        return key<MODE, OPT>(A, i, w, R, W);
+    }
+    static __device__ __forceinline__ Key shfl(const Key& k, int src)
+    {
+        Key p;
+        p.c8 = shfl64(k.c8, src);
+        p.wi = (int64_t)shfl64((uint64_t)k.wi, src);
+        p.cb = shfl64(k.cb, src);
+        p.clen = (uint32_t)__shfl((int)k.clen, src, 64);
+        return p;
+    }
+    static __device__ __forceinline__ uint32_t in(const Key&) { return 1u; }
+    static __device__ __forceinline__ bool follows(const char* text, uint64_t len, const Key& a, const Key& b)
+    {
+        if (b.c8 != a.c8 || b.clen != a.clen || b.wi != a.wi) return false;
+        return b.clen <= 8 || run_name_eq(text, len, b.cb, a.cb, b.clen);
+    }
+    static __device__ __forceinline__ void store(Row* row, const Key& k, uint32_t name)
+    {
+        row->wi = k.wi;
+        row->c8 = k.c8;
+        row->clen = k.clen;
+        row->name = name;
+    }
+    template <bool HEAD>
+    static __device__ __forceinline__ void add(Row* row, unsigned long long bi, unsigned long long b1,
+                                               unsigned long long b2, unsigned long long m)
+    {
+        atomicAdd(&row->sites, (uint32_t)__popcll(bi & m));
+        if (HEAD || (b1 & m)) atomicAdd(&row->records, (uint32_t)__popcll(b1 & m));
+        if (HEAD || (b2 & m)) atomicAdd(&row->het, (uint32_t)__popcll(b2 & m));
+    }
+};
 
-template <int MODE, bool OPT, class Off>
-__global__ __launch_bounds__(FTB) void sid_window_flag_kernel(const WinArgs<Off> C)
+struct CallRuns {
+    using Key = CallKey;
+    using Row = sid_call_row;
+    using Arg = NoArg;
+    static constexpr int CNT = 8;
+    static constexpr bool GAPS = true;
+    template <int MODE, bool OPT, class Off>
+    static __device__ __forceinline__ Key key(const SiteArgs<Off>& A, uint64_t i, uint32_t w, Reader& R, NoArg)
+    {
+        const Head h = sv_head<MODE, OPT>(A, i, w, R);
+        Key k;
+        k.c8 = reg_c8(R, h);
+        k.cb = h.clen > 8 ? h.cb : 0;
+        k.clen = h.clen;
+        k.pos = h.pos;
+        k.callable = 0;
+        k.pad = 0;
+        return k;
+    }
+    template <int MODE, bool OPT, class Off>
+    static __device__ __forceinline__ Key site(const SiteArgs<Off>& A, uint64_t i, uint32_t w, Reader& R, NoArg,
+                                               bool* in, bool* b1, bool* b2)
+    {
+        bool rec = false;
+        sv_label<MODE>(A, i, w, &rec, b2);
+        Key k = key<MODE, OPT>(A, i, w, R, NoArg{});
+        const uint32_t d = sv_depth<MODE, OPT>(A, i, w);
+        k.callable = rec && d >= 1u && d >= A.dmin && (A.dmax == 0 || d <= A.dmax) && k.pos >= 1;
+        *in = *b1 = k.callable != 0;
+        return k;
+    }
+    static __device__ __forceinline__ Key shfl(const Key& k, int src)
+    {
+        Key p;
+        p.c8 = shfl64(k.c8, src);
+        p.cb = shfl64(k.cb, src);
+        p.clen = (uint32_t)__shfl((int)k.clen, src, 64);
+        p.pos = __shfl(k.pos, src, 64);
+        return p;
+    }
+    static __device__ __forceinline__ uint32_t in(const Key& k) { return k.callable; }
+    static __device__ __forceinline__ bool follows(const char* text, uint64_t len, const Key& a, const Key& b)
+    {
+        if (a.c8 != b.c8 || a.clen != b.clen || (int64_t)b.pos != (int64_t)a.pos + 1) return false;
+        return a.clen <= 8 || run_name_eq(text, len, a.cb, b.cb, a.clen);
+    }
+    static __device__ __forceinline__ void store(Row* row, const Key& k, uint32_t name)
+    {
+        row->c8 = k.c8;
+        row->pos = k.pos;
+        row->clen = k.clen;
+        row->name = name;
+    }
+    template <bool HEAD>
+    static __device__ __forceinline__ void add(Row* row, unsigned long long bi, unsigned long long,
+                                               unsigned long long b2, unsigned long long m)
+    {
+        atomicAdd(&row->sites, (uint32_t)__popcll(bi & m));
+        if (b2 & m) atomicAdd(&row->het, (uint32_t)__popcll(b2 & m));
+    }
+};
+
+template <class P, int MODE, bool OPT, class Off>
+__global__ __launch_bounds__(FTB) void sid_runs_flag_kernel(const RunArgs<P, Off> C)
 {
+    using Key = typename P::Key;
     const SiteArgs<Off>& A = C.A;
     const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
     const uint64_t gw = ((uint64_t)blockIdx.x * FTB + threadIdx.x) >> 6;
@@ -4628,12 +4765,9 @@ __global__ __launch_bounds__(FTB) void sid_window_flag_kernel(const WinArgs<Off>
     Reader R{A.text, A.len};
     uint32_t w;
     const bool site = sv_site<MODE, OPT, 0>(A, i, &w);   // (the unselected parse: no skip word is stored)
-    bool rec = false, het = false;
-    WinKey k{0, 0, 0, 0, 0};
-    if (site) {
-        sv_label<MODE>(A, i, w, &rec, &het);
-        k = win_key<MODE, OPT>(A, i, w, R, C.W);
-    }
+    bool in = false, b1 = false, b2 = false;
+    Key k{};
+    if (site) k = P::template site<MODE, OPT>(A, i, w, R, C.arg, &in, &b1, &b2);
     const unsigned long long bs = __ballot(site);
     if (!bs) {   // (wave-uniform) no site: the link passes over the wave
         if (lane == 0) C.bits[4 * gw] = 0;
@@ -4642,18 +4776,16 @@ __global__ __launch_bounds__(FTB) void sid_window_flag_kernel(const WinArgs<Off>
     // the previous site of the wave: the ballot's nearest lower lane
     const unsigned long long pm = bs & ((1ull << lane) - 1ull);
     const int src = pm ? 63 - __clzll((long long)pm) : (int)lane;
-    WinKey p;
-    p.c8 = shfl64(k.c8, src);
-    p.wi = (int64_t)shfl64((uint64_t)k.wi, src);
-    p.cb = shfl64(k.cb, src);
-    p.clen = (uint32_t)__shfl((int)k.clen, src, 64);
-    const bool head = site && pm && !win_key_eq(A.text, A.len, k, p);
-    const unsigned long long br = __ballot(rec), bh = __ballot(rec && het), bd = __ballot(head);
+    bool prev_in = true;
+    if constexpr (P::GAPS) prev_in = (__ballot(in) >> src) & 1ull;
+    const Key p = P::shfl(k, src);
+    const bool head = in && pm && (!prev_in || !P::follows(A.text, A.len, p, k));
+    const unsigned long long w1 = __ballot(b1), w2 = __ballot(b1 && b2), bd = __ballot(head);
     const uint32_t nb = wave_sum(head && k.clen > 8 ? k.clen : 0u);
     if (lane == 0) {
         C.bits[4 * gw] = bs;
-        C.bits[4 * gw + 1] = br;
-        C.bits[4 * gw + 2] = bh;
+        C.bits[4 * gw + 1] = w1;
+        C.bits[4 * gw + 2] = w2;
         C.bits[4 * gw + 3] = bd;
         if (nb) atomicAdd(C.cnt + 1, (unsigned long long)nb);
     }
@@ -4661,11 +4793,13 @@ __global__ __launch_bounds__(FTB) void sid_window_flag_kernel(const WinArgs<Off>
     if (site && !(bs >> lane >> 1)) C.key[2 * gw + 1] = k;
 }
 
-__global__ __launch_bounds__(TB) void sid_window_link_kernel(const char* __restrict__ text, uint64_t len, uint64_t nw,
-                                                             unsigned long long* __restrict__ bits,
-                                                             const WinKey* __restrict__ key,
-                                                             uint32_t* __restrict__ hcnt, unsigned long long* cnt)
+template <class P>
+__global__ __launch_bounds__(TB) void sid_runs_link_kernel(const char* __restrict__ text, uint64_t len, uint64_t nw,
+                                                           unsigned long long* __restrict__ bits,
+                                                           const typename P::Key* __restrict__ key,
+                                                           uint32_t* __restrict__ hcnt, unsigned long long* cnt)
 {
+    using Key = typename P::Key;
     const uint64_t g = (uint64_t)blockIdx.x * TB + threadIdx.x;
     if (g >= nw) return;
     const unsigned long long bs = bits[4 * g];
@@ -4674,24 +4808,30 @@ __global__ __launch_bounds__(TB) void sid_window_link_kernel(const char* __restr
         unsigned long long hd = bits[4 * g + 3];
         uint64_t v = g;
         while (v > 0 && bits[4 * (v - 1)] == 0) --v;   // (the sites' ballots: no thread writes them here)
-        const WinKey a = key[2 * g];
-        bool head = true;   // the chunk's first site
-        if (v > 0) {
-            const WinKey b = key[2 * (v - 1) + 1];
-            head = !win_key_eq(text, len, a, b);
+        const Key a = key[2 * g];
+        if constexpr (P::GAPS) {   // the chunk's edge words
+            if (v == 0) cnt[4] = P::in(a);   // the chunk's first site
+            atomicMax(cnt + 3, (unsigned long long)((g + 1) << 1) | (unsigned long long)(P::in(key[2 * g + 1]) & 1u));
         }
-        if (head) {
-            hd |= bs & (~bs + 1ull);
-            bits[4 * g + 3] = hd;
-            if (a.clen > 8) atomicAdd(cnt + 1, (unsigned long long)a.clen);
+        if (P::in(a)) {
+            bool head = true;   // the chunk's first site
+            if (v > 0) {
+                const Key b = key[2 * (v - 1) + 1];
+                head = !P::in(b) || !P::follows(text, len, b, a);
+            }
+            if (head) {
+                hd |= bs & (~bs + 1ull);
+                bits[4 * g + 3] = hd;
+                if (a.clen > 8) atomicAdd(cnt + 1, (unsigned long long)a.clen);
+            }
         }
         n = (uint32_t)__popcll(hd);
     }
     hcnt[g] = n;
 }
 
-template <int MODE, bool OPT, class Off>
-__global__ __launch_bounds__(FTB) void sid_window_fill_kernel(const WinArgs<Off> C)
+template <class P, int MODE, bool OPT, class Off>
+__global__ __launch_bounds__(FTB) void sid_runs_fill_kernel(const RunArgs<P, Off> C)
 {
     const SiteArgs<Off>& A = C.A;
     const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
@@ -4699,21 +4839,23 @@ __global__ __launch_bounds__(FTB) void sid_window_fill_kernel(const WinArgs<Off>
     const uint32_t lane = threadIdx.x & 63u;
     const unsigned long long bs = C.bits[4 * gw];
     if (!bs) return;   // (wave-uniform)
-    const unsigned long long br = C.bits[4 * gw + 1], bh = C.bits[4 * gw + 2], hd = C.bits[4 * gw + 3];
+    const unsigned long long b1 = C.bits[4 * gw + 1], b2 = C.bits[4 * gw + 2], hd = C.bits[4 * gw + 3];
+    const unsigned long long bi = P::GAPS ? b1 : bs;                  // the sites in runs
+    const unsigned long long brk = P::GAPS ? hd | (bs & ~b1) : hd;    // where a run ends: a head, or a site in none
     const uint64_t r0 = C.roff[gw];
     const unsigned long long below = (1ull << lane) - 1ull;
     if ((hd >> lane) & 1ull) {
         const uint64_t r = r0 + (uint64_t)__popcll(hd & below);
-        // the run's lanes: from this one to the next head's
-        const unsigned long long up = hd >> lane >> 1;
+        // the run's lanes: from this one to the next break's
+        const unsigned long long up = brk >> lane >> 1;
         unsigned long long m = ~below;
-        if (up) m &= (1ull << (lane + (uint32_t)__ffsll(up))) - 1ull;   // (the next head's lane <= 63)
+        if (up) m &= (1ull << (lane + (uint32_t)__ffsll(up))) - 1ull;   // (the next break's lane <= 63)
         if (r < C.cap) {
             Reader R{A.text, A.len};
             uint32_t w;
             (void)sv_site<MODE, OPT, 0>(A, i, &w);
-            const WinKey k = win_key<MODE, OPT>(A, i, w, R, C.W);
-            sid_win_row* row = C.rows + r;
+            const typename P::Key k = P::template key<MODE, OPT>(A, i, w, R, C.arg);
+            typename P::Row* row = C.rows + r;
             uint32_t name = 0;
             if (k.clen > 8) {
                 const unsigned long long at = atomicAdd(C.cnt + 2, (unsigned long long)k.clen);
@@ -4721,23 +4863,13 @@ __global__ __launch_bounds__(FTB) void sid_window_fill_kernel(const WinArgs<Off>
                 if (at + k.clen <= C.ncap)
                     for (uint32_t j = 0; j < k.clen; ++j) C.names[at + j] = (char)R.at(k.cb + j);
             }
-            row->wi = k.wi;
-            row->c8 = k.c8;
-            row->clen = k.clen;
-            row->name = name;
-            atomicAdd(&row->sites, (uint32_t)__popcll(bs & m));
-            atomicAdd(&row->records, (uint32_t)__popcll(br & m));
-            atomicAdd(&row->het, (uint32_t)__popcll(bh & m));
+            P::store(row, k, name);
+            P::template add<true>(row, bi, b1, b2, m);
         }
     }
-    if (lane == 0) {   // the sites in front of the wave's first head: the run of the row before
-        const unsigned long long m = hd ? (hd & (~hd + 1ull)) - 1ull : ~0ull;
-        if ((bs & m) && r0 > 0 && r0 - 1 < C.cap) {
-            sid_win_row* row = C.rows + (r0 - 1);
-            atomicAdd(&row->sites, (uint32_t)__popcll(bs & m));
-            if (br & m) atomicAdd(&row->records, (uint32_t)__popcll(br & m));
-            if (bh & m) atomicAdd(&row->het, (uint32_t)__popcll(bh & m));
-        }
+    if (lane == 0) {   // the sites in runs in front of the wave's first break: the run of the row before
+        const unsigned long long m = brk ? (brk & (~brk + 1ull)) - 1ull : ~0ull;
+        if ((bi & m) && r0 > 0 && r0 - 1 < C.cap) P::template add<false>(C.rows + (r0 - 1), bi, b1, b2, m);
     }
 }
 
@@ -4770,13 +4902,14 @@ __global__ __launch_bounds__(64) void sid_window_cnt_kernel(const unsigned long 
 }
 
 // the stage's device buffers for `slots` slots: sid_chunk_ws's win_* (the engine) or a call's own
-struct WinBufs {
+template <class P>
+struct RunBufs {
     unsigned long long* bits;
-    WinKey* key;
+    typename P::Key* key;
     uint32_t* hcnt;     // followed by the scan's workspace
     uint64_t* roff;
     unsigned long long* cnt;
-    sid_win_row* rows;
+    typename P::Row* rows;
     uint32_t cap;
     char* names;
     uint32_t ncap;
@@ -4785,29 +4918,29 @@ static uint64_t win_waves(uint64_t slots) { return (slots + FTB - 1) / FTB * (FT
 static size_t win_hcnt_bytes(uint64_t nw) { return ((std::max<uint64_t>(nw, 1) * 4 + 7) & ~(size_t)7) + scan_ws_bytes(nw); }
 
 // flag, link and scan for A's slots: afterwards cnt[0] = the rows, cnt[1] = their long names' bytes
-template <int MODE, bool OPT, class Off>
-static void launch_window_count(WinArgs<Off>& C, const WinBufs& B, hipStream_t st)
+template <int MODE, bool OPT, class P, class Off>
+static void launch_runs_count(RunArgs<P, Off>& C, const RunBufs<P>& B, hipStream_t st)
 {
     C.bits = B.bits, C.key = B.key, C.hcnt = B.hcnt, C.roff = B.roff, C.cnt = B.cnt;
     C.rows = B.rows, C.cap = B.cap, C.names = B.names, C.ncap = B.ncap;
     const uint64_t nb = (C.A.s1 - C.A.s0 + FTB - 1) / FTB, nw = nb * (FTB / 64);
-    (void)hipMemsetAsync(B.cnt, 0, 3 * 8, st);
+    (void)hipMemsetAsync(B.cnt, 0, P::CNT * 8, st);
     if (!nb) return;
-    sid_window_flag_kernel<MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(C);
-    sid_window_link_kernel<<<(unsigned)((nw + TB - 1) / TB), TB, 0, st>>>(C.A.text, C.A.len, nw, B.bits, B.key, B.hcnt,
-                                                                          B.cnt);
+    sid_runs_flag_kernel<P, MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(C);
+    sid_runs_link_kernel<P><<<(unsigned)((nw + TB - 1) / TB), TB, 0, st>>>(C.A.text, C.A.len, nw, B.bits, B.key, B.hcnt,
+                                                                           B.cnt);
     launch_scan(B.hcnt, nw, B.roff, (uint64_t*)B.cnt, nullptr,
                 (uint64_t*)((char*)B.hcnt + ((nw * 4 + 7) & ~(size_t)7)), st);
 }
-// the rows (the first B.cap of them) after launch_window_count
-template <int MODE, bool OPT, class Off>
-static void launch_window_fill(WinArgs<Off>& C, const WinBufs& B, hipStream_t st)
+// the rows (the first B.cap of them) after launch_runs_count
+template <int MODE, bool OPT, class P, class Off>
+static void launch_runs_fill(RunArgs<P, Off>& C, const RunBufs<P>& B, hipStream_t st)
 {
     C.rows = B.rows, C.cap = B.cap, C.names = B.names, C.ncap = B.ncap;
     const uint64_t nb = (C.A.s1 - C.A.s0 + FTB - 1) / FTB;
     if (!nb || !B.cap) return;
-    (void)hipMemsetAsync(B.rows, 0, (size_t)B.cap * sizeof(sid_win_row), st);
-    sid_window_fill_kernel<MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(C);
+    (void)hipMemsetAsync(B.rows, 0, (size_t)B.cap * sizeof(typename P::Row), st);
+    sid_runs_fill_kernel<P, MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(C);
 }
 
 // -------------------------------------------------------- depth histogram --
@@ -5227,249 +5360,6 @@ static void launch_region_stats(const SiteArgs<Off>& A, const RsBufs& B, hipStre
         else sid_region_stats_kernel<MODE, OPT, 0, Off><<<(unsigned)grid, FTB, 0, st>>>(C);
     }
     sid_region_stats_pack_kernel<<<1, SCAN_TB, 0, st>>>(B.cnt, B.bins, B.rows, A.T.ni, B.eager, B.out);
-}
-
-// --------------------------------------------------------- callable runs --
-// The callable runs (sid_dtext_callable; callable.h): the rows of a site range,
-// a row being a maximal run of consecutive sites that are all callable -- a
-// record in the unselected output, a depth >= 1 within the bounds, pos >= 1 --
-// with equal chrom and each pos the previous pos + 1.  The stage reads what the
-// window stage reads, through the same loaders (sv_site, sv_label, sv_depth,
-// sv_head; templated on the layout as that stage is, instantiated for the
-// resident shard's), and has its steps:
-//   flag   per slot: holds a site, is callable, is callable and het (wave
-//          ballots), and whether it opens a row against the previous site of
-//          its wave (the ballot's nearest lower lane, its key by shuffle): the
-//          previous site not callable, another chrom, or pos != its pos + 1 in
-//          64 bits; per wave its first and last site's key with that site's
-//          callable bit.  A wave's first site waits for the link.
-//   link   one thread per wave: the nearest earlier wave with a site and its
-//          last key against this wave's first, if that is callable; the chunk's
-//          first site, if callable, is a head.  The wave's head count, the
-//          bytes of the heads' long names, and the chunk's edge words: the
-//          first site's callable bit, and (an atomic max over the waves) the
-//          last site's.
-//   scan   exclusive scan of the waves' head counts.
-//   fill   a lane per head: its row's chrom and first pos, and the popcounts
-//          of the callable and het ballots masked to its run's lanes -- from
-//          the head up to, not including, the next lane that is a head or a
-//          site that is not callable -- added to the row; lane 0 adds the
-//          callable lanes in front of the wave's first such break to the row
-//          before.  A run of many waves costs two atomic adds a wave.  Rows
-//          from `cap` on and names past `ncap` are dropped: the caller sizes
-//          both from the counts before the fill.
-struct CallKey {
-    uint64_t c8;
-    uint64_t cb;        // clen > 8: the chrom's offset in the text
-    uint32_t clen;
-    int32_t pos;
-    uint32_t callable;
-    uint32_t pad;
-};
-static_assert(sizeof(CallKey) == 32, "two keys a wave");
-
-template <class Off>
-struct CallArgs {
-    SiteArgs<Off> A;              // the sites (A.dmin, A.dmax: the depth bounds)
-    unsigned long long* bits;     // per wave of slots: [0] sites [1] callable [2] callable and het [3] heads
-    CallKey* key;                 // per wave: [0] its first site's key, [1] its last site's
-    uint32_t* hcnt;               // per wave: its heads
-    const uint64_t* roff;         // ... and its first head's row
-    unsigned long long* cnt;      // [0] rows [1] name bytes [2] the fill's name cursor [3] the last wave with a
-                                  // site and its last site's callable bit [4] the first site's callable bit
-    sid_call_row* rows;
-    uint32_t cap;
-    char* names;
-    uint32_t ncap;
-};
-
-// whether site b, which follows site a with no site between, goes on a's run (both callable)
-__device__ __forceinline__ bool call_follows(const char* text, uint64_t len, const CallKey& a, const CallKey& b)
-{
-    if (a.c8 != b.c8 || a.clen != b.clen || (int64_t)b.pos != (int64_t)a.pos + 1) return false;
-    return a.clen <= 8 || win_name_eq(text, len, a.cb, b.cb, a.clen);
-}
-
-template <int MODE, bool OPT, class Off>
-__device__ __forceinline__ CallKey call_key(const SiteArgs<Off>& A, uint64_t i, uint32_t w, Reader& R)
-{
-    const Head h = sv_head<MODE, OPT>(A, i, w, R);
-    CallKey k;
-    k.c8 = reg_c8(R, h);
-    k.cb = h.clen > 8 ? h.cb : 0;
-    k.clen = h.clen;
-    k.pos = h.pos;
-    k.callable = 0;
-    k.pad = 0;
-    return k;
-}
-
-template <int MODE, bool OPT, class Off>
-__global__ __launch_bounds__(FTB) void sid_callable_flag_kernel(const CallArgs<Off> C)
-{
-    const SiteArgs<Off>& A = C.A;
-    const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
-    const uint64_t gw = ((uint64_t)blockIdx.x * FTB + threadIdx.x) >> 6;
-    const uint32_t lane = threadIdx.x & 63u;
-    Reader R{A.text, A.len};
-    uint32_t w;
-    const bool site = sv_site<MODE, OPT, 0>(A, i, &w);   // (the unselected parse, as the window stage)
-    bool rec = false, het = false;
-    CallKey k{0, 0, 0, 0, 0, 0};
-    if (site) {
-        sv_label<MODE>(A, i, w, &rec, &het);
-        k = call_key<MODE, OPT>(A, i, w, R);
-        const uint32_t d = sv_depth<MODE, OPT>(A, i, w);
-        k.callable = rec && d >= 1u && d >= A.dmin && (A.dmax == 0 || d <= A.dmax) && k.pos >= 1;
-    }
-    const bool ok = k.callable != 0;
-    const unsigned long long bs = __ballot(site);
-    if (!bs) {   // (wave-uniform) no site: the link passes over the wave
-        if (lane == 0) C.bits[4 * gw] = 0;
-        return;
-    }
-    const unsigned long long bc = __ballot(ok), bh = __ballot(ok && het);
-    // the previous site of the wave: the ballot's nearest lower lane
-    const unsigned long long pm = bs & ((1ull << lane) - 1ull);
-    const int src = pm ? 63 - __clzll((long long)pm) : (int)lane;
-    CallKey p;
-    p.c8 = shfl64(k.c8, src);
-    p.cb = shfl64(k.cb, src);
-    p.clen = (uint32_t)__shfl((int)k.clen, src, 64);
-    p.pos = __shfl(k.pos, src, 64);
-    const bool head = ok && pm && (!((bc >> src) & 1ull) || !call_follows(A.text, A.len, p, k));
-    const unsigned long long bd = __ballot(head);
-    const uint32_t nb = wave_sum(head && k.clen > 8 ? k.clen : 0u);
-    if (lane == 0) {
-        C.bits[4 * gw] = bs;
-        C.bits[4 * gw + 1] = bc;
-        C.bits[4 * gw + 2] = bh;
-        C.bits[4 * gw + 3] = bd;
-        if (nb) atomicAdd(C.cnt + 1, (unsigned long long)nb);
-    }
-    if (site && !pm) C.key[2 * gw] = k;
-    if (site && !(bs >> lane >> 1)) C.key[2 * gw + 1] = k;
-}
-
-__global__ __launch_bounds__(TB) void sid_callable_link_kernel(const char* __restrict__ text, uint64_t len, uint64_t nw,
-                                                               unsigned long long* __restrict__ bits,
-                                                               const CallKey* __restrict__ key,
-                                                               uint32_t* __restrict__ hcnt, unsigned long long* cnt)
-{
-    const uint64_t g = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (g >= nw) return;
-    const unsigned long long bs = bits[4 * g];
-    uint32_t n = 0;
-    if (bs) {
-        unsigned long long hd = bits[4 * g + 3];
-        uint64_t v = g;
-        while (v > 0 && bits[4 * (v - 1)] == 0) --v;   // (the sites' ballots: no thread writes them here)
-        const CallKey a = key[2 * g];
-        if (v == 0) cnt[4] = a.callable;   // the chunk's first site
-        atomicMax(cnt + 3, (unsigned long long)((g + 1) << 1) | (unsigned long long)(key[2 * g + 1].callable & 1u));
-        if (a.callable) {
-            bool head = true;
-            if (v > 0) {
-                const CallKey b = key[2 * (v - 1) + 1];
-                head = !b.callable || !call_follows(text, len, b, a);
-            }
-            if (head) {
-                hd |= bs & (~bs + 1ull);
-                bits[4 * g + 3] = hd;
-                if (a.clen > 8) atomicAdd(cnt + 1, (unsigned long long)a.clen);
-            }
-        }
-        n = (uint32_t)__popcll(hd);
-    }
-    hcnt[g] = n;
-}
-
-template <int MODE, bool OPT, class Off>
-__global__ __launch_bounds__(FTB) void sid_callable_fill_kernel(const CallArgs<Off> C)
-{
-    const SiteArgs<Off>& A = C.A;
-    const uint64_t i = A.s0 + (uint64_t)blockIdx.x * FTB + threadIdx.x;
-    const uint64_t gw = ((uint64_t)blockIdx.x * FTB + threadIdx.x) >> 6;
-    const uint32_t lane = threadIdx.x & 63u;
-    const unsigned long long bs = C.bits[4 * gw];
-    if (!bs) return;   // (wave-uniform)
-    const unsigned long long bc = C.bits[4 * gw + 1], bh = C.bits[4 * gw + 2], hd = C.bits[4 * gw + 3];
-    const unsigned long long brk = hd | (bs & ~bc);   // where a run ends: a head, or a site that is not callable
-    const uint64_t r0 = C.roff[gw];
-    const unsigned long long below = (1ull << lane) - 1ull;
-    if ((hd >> lane) & 1ull) {
-        const uint64_t r = r0 + (uint64_t)__popcll(hd & below);
-        const unsigned long long up = brk >> lane >> 1;
-        unsigned long long m = ~below;
-        if (up) m &= (1ull << (lane + (uint32_t)__ffsll(up))) - 1ull;   // (the next break's lane <= 63)
-        if (r < C.cap) {
-            Reader R{A.text, A.len};
-            uint32_t w;
-            (void)sv_site<MODE, OPT, 0>(A, i, &w);
-            const CallKey k = call_key<MODE, OPT>(A, i, w, R);
-            sid_call_row* row = C.rows + r;
-            uint32_t name = 0;
-            if (k.clen > 8) {
-                const unsigned long long at = atomicAdd(C.cnt + 2, (unsigned long long)k.clen);
-                name = (uint32_t)min(at, (unsigned long long)0xFFFFFFFFu);
-                if (at + k.clen <= C.ncap)
-                    for (uint32_t j = 0; j < k.clen; ++j) C.names[at + j] = (char)R.at(k.cb + j);
-            }
-            row->c8 = k.c8;
-            row->pos = k.pos;
-            row->clen = k.clen;
-            row->name = name;
-            atomicAdd(&row->sites, (uint32_t)__popcll(bc & m));
-            if (bh & m) atomicAdd(&row->het, (uint32_t)__popcll(bh & m));
-        }
-    }
-    if (lane == 0) {   // the callable sites in front of the wave's first break: the run of the row before
-        const unsigned long long m = brk ? (brk & (~brk + 1ull)) - 1ull : ~0ull;
-        if ((bc & m) && r0 > 0 && r0 - 1 < C.cap) {
-            sid_call_row* row = C.rows + (r0 - 1);
-            atomicAdd(&row->sites, (uint32_t)__popcll(bc & m));
-            if (bh & m) atomicAdd(&row->het, (uint32_t)__popcll(bh & m));
-        }
-    }
-}
-
-// the stage's device buffers for `slots` slots (sid_dtext_callable's own)
-struct CallBufs {
-    unsigned long long* bits;
-    CallKey* key;
-    uint32_t* hcnt;     // followed by the scan's workspace
-    uint64_t* roff;
-    unsigned long long* cnt;
-    sid_call_row* rows;
-    uint32_t cap;
-    char* names;
-    uint32_t ncap;
-};
-
-// flag, link and scan for A's slots: afterwards cnt[0] = the rows, cnt[1] = their long names' bytes
-template <int MODE, bool OPT, class Off>
-static void launch_callable_count(CallArgs<Off>& C, const CallBufs& B, hipStream_t st)
-{
-    C.bits = B.bits, C.key = B.key, C.hcnt = B.hcnt, C.roff = B.roff, C.cnt = B.cnt;
-    C.rows = B.rows, C.cap = B.cap, C.names = B.names, C.ncap = B.ncap;
-    const uint64_t nb = (C.A.s1 - C.A.s0 + FTB - 1) / FTB, nw = nb * (FTB / 64);
-    (void)hipMemsetAsync(B.cnt, 0, 8 * 8, st);
-    if (!nb) return;
-    sid_callable_flag_kernel<MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(C);
-    sid_callable_link_kernel<<<(unsigned)((nw + TB - 1) / TB), TB, 0, st>>>(C.A.text, C.A.len, nw, B.bits, B.key,
-                                                                            B.hcnt, B.cnt);
-    launch_scan(B.hcnt, nw, B.roff, (uint64_t*)B.cnt, nullptr,
-                (uint64_t*)((char*)B.hcnt + ((nw * 4 + 7) & ~(size_t)7)), st);
-}
-// the rows (the first B.cap of them) after launch_callable_count
-template <int MODE, bool OPT, class Off>
-static void launch_callable_fill(CallArgs<Off>& C, const CallBufs& B, hipStream_t st)
-{
-    C.rows = B.rows, C.cap = B.cap, C.names = B.names, C.ncap = B.ncap;
-    const uint64_t nb = (C.A.s1 - C.A.s0 + FTB - 1) / FTB;
-    if (!nb || !B.cap) return;
-    (void)hipMemsetAsync(B.rows, 0, (size_t)B.cap * sizeof(sid_call_row), st);
-    sid_callable_fill_kernel<MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(C);
 }
 
 // tails of the U classes (one thread each), then the dense codes' lengths
@@ -6211,6 +6101,52 @@ extern "C" int sid_dtext_format(sid_ctx* ctx, const sid_dtext* T, size_t begin, 
     return rc;
 }
 
+// The run-rows stage over C.A's sites (at least one) with buffers of the call's own: the count, the rows and
+// names sized from it, the fill, and both read back into ch (a sid_win_chunk or sid_call_chunk).
+template <class P, class Chunk>
+static int dtext_runs(RunArgs<P, uint64_t>& C, hipStream_t st, Chunk* ch)
+{
+    typedef typename P::Key Key;
+    typedef typename P::Row Row;
+    static_assert(P::CNT <= 8, "the call's cnt words");
+    const uint64_t nw = win_waves(C.A.s1 - C.A.s0);
+    const size_t o_key = nw * 32, o_hcnt = o_key + nw * 2 * sizeof(Key);
+    const size_t o_roff = (o_hcnt + win_hcnt_bytes(nw) + 15) & ~(size_t)15, o_cnt = o_roff + nw * 8;
+    char* d_ws = nullptr;
+    void* d_rows = nullptr;
+    char* d_names = nullptr;
+    int rc = SID_OK;
+    auto hip = [&](hipError_t x) {
+        if (x != hipSuccess && rc == SID_OK) rc = sid_set_hip_error(x);
+        return rc == SID_OK;
+    };
+    unsigned long long need[2] = {0, 0};
+    if (hip(hipMalloc(&d_ws, o_cnt + 8 * 8))) {
+        RunBufs<P> B{(unsigned long long*)d_ws, (Key*)(d_ws + o_key), (uint32_t*)(d_ws + o_hcnt),
+                     (uint64_t*)(d_ws + o_roff), (unsigned long long*)(d_ws + o_cnt), nullptr, 0, nullptr, 0};
+        launch_runs_count<REG_CODE, false>(C, B, st);
+        hip(hipGetLastError());
+        hip(hipMemcpyAsync(need, B.cnt, sizeof need, hipMemcpyDeviceToHost, st));
+        hip(hipStreamSynchronize(st));
+        if (rc == SID_OK && need[0] >= (1ull << 32)) rc = SID_ENOMEM;
+        if (rc == SID_OK && need[0] && hip(hipMalloc(&d_rows, need[0] * sizeof(Row))) &&
+            hip(hipMalloc(&d_names, std::max<size_t>(need[1], 16)))) {
+            B.rows = (Row*)d_rows, B.cap = (uint32_t)need[0];
+            B.names = d_names, B.ncap = (uint32_t)std::min<unsigned long long>(need[1], 0xFFFFFFFFull);
+            launch_runs_fill<REG_CODE, false>(C, B, st);
+            hip(hipGetLastError());
+            ch->rows.resize(need[0]);
+            ch->names.resize(need[1]);
+            hip(hipMemcpyAsync(ch->rows.data(), d_rows, need[0] * sizeof(Row), hipMemcpyDeviceToHost, st));
+            if (need[1]) hip(hipMemcpyAsync(&ch->names[0], d_names, need[1], hipMemcpyDeviceToHost, st));
+            hip(hipStreamSynchronize(st));
+        }
+    }
+    for (void* p : {(void*)d_ws, d_rows, (void*)d_names})
+        if (p) (void)hipFree(p);
+    return rc;
+}
+
 // The window stage over a resident shard (the engine's, without chunk edges): buffers of this call's own,
 // the rows sized from the counts.
 extern "C" int sid_dtext_windows(sid_ctx* ctx, const sid_dtext* T, size_t begin, size_t end, const uint8_t* d_code,
@@ -6226,45 +6162,11 @@ extern "C" int sid_dtext_windows(sid_ctx* ctx, const sid_dtext* T, size_t begin,
     tab.window = ctx->opts.window;
     const size_t m = end - begin;
     if (m == 0) return sid_win_export(tab, rows, n);
-    const uint64_t nw = win_waves(m);
-    const size_t o_key = nw * 32, o_hcnt = o_key + nw * 2 * sizeof(WinKey);
-    const size_t o_roff = (o_hcnt + win_hcnt_bytes(nw) + 15) & ~(size_t)15, o_cnt = o_roff + nw * 8;
-    char* d_ws = nullptr;
-    void* d_rows = nullptr;
-    char* d_names = nullptr;
-    int rc = SID_OK;
-    auto hip = [&](hipError_t x) {
-        if (x != hipSuccess && rc == SID_OK) rc = sid_set_hip_error(x);
-        return rc == SID_OK;
-    };
     sid_win_chunk ch;
-    unsigned long long need[2] = {0, 0};
-    if (hip(hipMalloc(&d_ws, o_cnt + 4 * 8))) {
-        WinBufs B{(unsigned long long*)d_ws, (WinKey*)(d_ws + o_key), (uint32_t*)(d_ws + o_hcnt),
-                  (uint64_t*)(d_ws + o_roff), (unsigned long long*)(d_ws + o_cnt), nullptr, 0, nullptr, 0};
-        WinArgs<uint64_t> C{};
-        C.A = dtext_view(T, begin, end, const_cast<uint8_t*>(d_code));
-        C.W = ctx->opts.window;
-        launch_window_count<REG_CODE, false>(C, B, st);
-        hip(hipGetLastError());
-        hip(hipMemcpyAsync(need, B.cnt, sizeof need, hipMemcpyDeviceToHost, st));
-        hip(hipStreamSynchronize(st));
-        if (rc == SID_OK && need[0] >= (1ull << 32)) rc = SID_ENOMEM;
-        if (rc == SID_OK && need[0] && hip(hipMalloc(&d_rows, need[0] * sizeof(sid_win_row))) &&
-            hip(hipMalloc(&d_names, std::max<size_t>(need[1], 16)))) {
-            B.rows = (sid_win_row*)d_rows, B.cap = (uint32_t)need[0];
-            B.names = d_names, B.ncap = (uint32_t)std::min<unsigned long long>(need[1], 0xFFFFFFFFull);
-            launch_window_fill<REG_CODE, false>(C, B, st);
-            hip(hipGetLastError());
-            ch.rows.resize(need[0]);
-            ch.names.resize(need[1]);
-            hip(hipMemcpyAsync(ch.rows.data(), d_rows, need[0] * sizeof(sid_win_row), hipMemcpyDeviceToHost, st));
-            if (need[1]) hip(hipMemcpyAsync(&ch.names[0], d_names, need[1], hipMemcpyDeviceToHost, st));
-            hip(hipStreamSynchronize(st));
-        }
-    }
-    for (void* p : {(void*)d_ws, d_rows, (void*)d_names})
-        if (p) (void)hipFree(p);
+    RunArgs<WinRuns, uint64_t> C{};
+    C.A = dtext_view(T, begin, end, const_cast<uint8_t*>(d_code));
+    C.arg = ctx->opts.window;
+    const int rc = dtext_runs(C, st, &ch);
     if (rc != SID_OK) return rc;
     for (const sid_win_row& r : ch.rows)
         if (r.clen > 8 && (uint64_t)r.name + r.clen > ch.names.size()) return SID_ESTATE;
@@ -6379,45 +6281,11 @@ extern "C" int sid_dtext_callable(sid_ctx* ctx, const sid_dtext* T, size_t begin
     if (m >= (1ull << 32)) return SID_EINVAL;   // (the stage's counters are a chunk's: 32 bits)
     TCHECK(hipSetDevice(T->device));
     hipStream_t st = (hipStream_t)stream;
-    const uint64_t nw = win_waves(m);
-    const size_t o_key = nw * 32, o_hcnt = o_key + nw * 2 * sizeof(CallKey);
-    const size_t o_roff = (o_hcnt + win_hcnt_bytes(nw) + 15) & ~(size_t)15, o_cnt = o_roff + nw * 8;
-    char* d_ws = nullptr;
-    void* d_rows = nullptr;
-    char* d_names = nullptr;
-    int rc = SID_OK;
-    auto hip = [&](hipError_t x) {
-        if (x != hipSuccess && rc == SID_OK) rc = sid_set_hip_error(x);
-        return rc == SID_OK;
-    };
     sid_call_chunk ch;
-    unsigned long long need[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hip(hipMalloc(&d_ws, o_cnt + 8 * 8))) {
-        CallBufs B{(unsigned long long*)d_ws, (CallKey*)(d_ws + o_key), (uint32_t*)(d_ws + o_hcnt),
-                   (uint64_t*)(d_ws + o_roff), (unsigned long long*)(d_ws + o_cnt), nullptr, 0, nullptr, 0};
-        CallArgs<uint64_t> C{};
-        C.A = dtext_view(T, begin, end, const_cast<uint8_t*>(d_code));
-        C.A.dmin = (uint32_t)ctx->depth_min, C.A.dmax = (uint32_t)ctx->depth_max;
-        launch_callable_count<REG_CODE, false>(C, B, st);
-        hip(hipGetLastError());
-        hip(hipMemcpyAsync(need, B.cnt, sizeof need, hipMemcpyDeviceToHost, st));
-        hip(hipStreamSynchronize(st));
-        if (rc == SID_OK && need[0] >= (1ull << 32)) rc = SID_ENOMEM;
-        if (rc == SID_OK && need[0] && hip(hipMalloc(&d_rows, need[0] * sizeof(sid_call_row))) &&
-            hip(hipMalloc(&d_names, std::max<size_t>(need[1], 16)))) {
-            B.rows = (sid_call_row*)d_rows, B.cap = (uint32_t)need[0];
-            B.names = d_names, B.ncap = (uint32_t)std::min<unsigned long long>(need[1], 0xFFFFFFFFull);
-            launch_callable_fill<REG_CODE, false>(C, B, st);
-            hip(hipGetLastError());
-            ch.rows.resize(need[0]);
-            ch.names.resize(need[1]);
-            hip(hipMemcpyAsync(ch.rows.data(), d_rows, need[0] * sizeof(sid_call_row), hipMemcpyDeviceToHost, st));
-            if (need[1]) hip(hipMemcpyAsync(&ch.names[0], d_names, need[1], hipMemcpyDeviceToHost, st));
-            hip(hipStreamSynchronize(st));
-        }
-    }
-    for (void* p : {(void*)d_ws, d_rows, (void*)d_names})
-        if (p) (void)hipFree(p);
+    RunArgs<CallRuns, uint64_t> C{};
+    C.A = dtext_view(T, begin, end, const_cast<uint8_t*>(d_code));
+    C.A.dmin = (uint32_t)ctx->depth_min, C.A.dmax = (uint32_t)ctx->depth_max;
+    const int rc = dtext_runs(C, st, &ch);
     if (rc != SID_OK) return rc;
     for (const sid_call_row& r : ch.rows)
         if ((r.clen > 8 && (uint64_t)r.name + r.clen > ch.names.size()) || r.pos < 1 || r.sites == 0) return SID_ESTATE;
@@ -6590,18 +6458,18 @@ static int win_fit(sid_chunk_ws* W, int b, uint64_t rows, uint64_t names)
 template <int MODE, bool OPT, class Off>
 static int window_stage(const SiteArgs<Off>& A, sid_chunk_ws* W, uint64_t text_bytes, bool size, hipStream_t st)
 {
-    WinArgs<Off> C{};
+    RunArgs<WinRuns, Off> C{};
     C.A = A;
-    C.W = W->window;
+    C.arg = W->window;
     const int b = (W->win_cur ^= 1);
     int rc = win_fit(W, b, W->win_want_rows, W->win_want_names);
     if (rc != SID_OK) return rc;
     auto bufs = [&] {
-        return WinBufs{W->win_bits, (WinKey*)W->win_key, W->win_hcnt, W->win_roff, W->win_cnt[b],
-                       W->win_rows[b], W->win_cap[b], W->win_names[b], W->win_ncap[b]};
+        return RunBufs<WinRuns>{W->win_bits, (WinKey*)W->win_key, W->win_hcnt, W->win_roff, W->win_cnt[b],
+                                W->win_rows[b], W->win_cap[b], W->win_names[b], W->win_ncap[b]};
     };
-    WinBufs B = bufs();
-    launch_window_count<MODE, OPT>(C, B, st);
+    RunBufs<WinRuns> B = bufs();
+    launch_runs_count<MODE, OPT>(C, B, st);
     if (size && (C.A.s1 - C.A.s0 > B.cap || text_bytes > B.ncap)) {
         unsigned long long* need = W->win_h;   // (pinned, stored by a kernel: no copy behind the records' copies)
         sid_window_cnt_kernel<<<1, 64, 0, st>>>(B.cnt, need);
@@ -6612,7 +6480,7 @@ static int window_stage(const SiteArgs<Off>& A, sid_chunk_ws* W, uint64_t text_b
             B = bufs();
         }
     }
-    launch_window_fill<MODE, OPT>(C, B, st);
+    launch_runs_fill<MODE, OPT>(C, B, st);
     sid_window_pack_kernel<<<1, 256, 0, st>>>(B.cnt, B.rows, B.cap, B.names, B.ncap, W->win_eager[b]);
     WCHECK(hipGetLastError());
     return SID_OK;

@@ -5,7 +5,7 @@
 //
 // A row is a maximal run of consecutive sites with byte-equal chrom and equal
 // window index wi = floor((pos - 1) / W).  The device finds the runs of one
-// chunk (textpath.hip, sid_window_*_kernel): a chunk's first site always opens
+// chunk (textpath.hip, the run rows' WinRuns): a chunk's first site always opens
 // a row, so a run that crosses a chunk edge comes back as two rows with equal
 // keys, which the stitch adds up -- through chunks without a site, and only
 // when the two rows are neighbours in file order.
@@ -16,7 +16,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/sid.h"
+#include "rowtable.h"
 
 // One row as the device writes it and the engine reads it back.
 struct sid_win_row {
@@ -42,19 +42,9 @@ struct sid_win_chunk {
     }
 };
 
-// The rows of a run: what sid_engine_windows hands out.  The chrom pointers
-// point into `names` and are set by finish().
-struct sid_win_table {
-    std::vector<sid_window> rows;
-    std::vector<uint64_t> name_off;
-    std::string names;
+// The rows of a run: what sid_engine_windows hands out (rowtable.h).
+struct sid_win_table : sid_row_table<sid_window> {
     int64_t window = 0;
-    void clear()
-    {
-        rows.clear();
-        name_off.clear();
-        names.clear();
-    }
     // one more site run in file order: merged into the last row when their keys are equal
     void push(const char* chrom, uint32_t clen, int64_t wi, uint64_t sites, uint64_t records, uint64_t het);
     void finish();

@@ -1,5 +1,6 @@
 // sid_asan — the product's host code (parse.cpp, emit.cpp, fmt.h's host build,
-// regions.cpp, context.cpp, windows.cpp, depth_hist.cpp, bgzf.cpp) under
+// regions.cpp, context.cpp, windows.cpp, depth_hist.cpp, region_stats.cpp,
+// callable.cpp, bgzf.cpp) under
 // AddressSanitizer + UndefinedBehaviorSanitizer (sanitizers on
 // the host restatement).  TEST INFRASTRUCTURE: one stand-alone program, driven
 // by tests/test_sanitized.py and tests/test_*_asan.py through
@@ -16,7 +17,8 @@
 //              over every site with synthetic code / confidences (synth_site)
 //   g6         binary f64 values: fmt.h's %g and sid_format_double, one line
 //              each
-//   bgzf, context, depth, depth_hist, regions, variants, vcf, windows
+//   bgzf, callable, context, depth, depth_hist, region_stats, regions,
+//   variants, vcf, windows
 //              a corpus of cases: mode_<name>.cpp states the format
 #include <cmath>
 #include <cstdio>
@@ -123,10 +125,12 @@ int main(int argc, char** argv)
     static const struct {
         const char* name;
         int (*run)(const std::string&);
-    } modes[] = {{"lines", mode_lines},     {"g6", mode_g6},           {"bgzf", mode_bgzf},
-                 {"context", mode_context}, {"depth", mode_depth},     {"depth_hist", mode_depth_hist},
-                 {"regions", mode_regions}, {"variants", mode_variants}, {"vcf", mode_vcf},
-                 {"windows", mode_windows}};
+    } modes[] = {{"lines", mode_lines},       {"g6", mode_g6},
+                 {"bgzf", mode_bgzf},         {"callable", mode_callable},
+                 {"context", mode_context},   {"depth", mode_depth},
+                 {"depth_hist", mode_depth_hist}, {"region_stats", mode_region_stats},
+                 {"regions", mode_regions},   {"variants", mode_variants},
+                 {"vcf", mode_vcf},           {"windows", mode_windows}};
     for (const auto& m : modes)
         if (mode == m.name) return m.run(in);
     return 2;

@@ -12,9 +12,11 @@
 #include "sid.h"
 
 int mode_bgzf(const std::string& corpus);
+int mode_callable(const std::string& corpus);
 int mode_context(const std::string& corpus);
 int mode_depth(const std::string& corpus);
 int mode_depth_hist(const std::string& corpus);
+int mode_region_stats(const std::string& corpus);
 int mode_regions(const std::string& corpus);
 int mode_variants(const std::string& corpus);
 int mode_vcf(const std::string& corpus);

@@ -1,6 +1,5 @@
-// callable_asan callable CORPUS — callable.cpp and parse.cpp under ASan + UBSan
-// (tests/test_callable_asan.py; TEST INFRASTRUCTURE, CPU only): a stand-alone
-// program with its own main, nothing preloaded.
+// sid_asan callable CORPUS — callable.cpp (and rowtable.h, parse.cpp) under
+// ASan + UBSan (tests/test_callable_asan.py; TEST INFRASTRUCTURE, CPU only).
 //
 // CORPUS is a sequence of cases.
 //   "H <min> <max> <sites> <begin> <end>", then per site a line "<chrom> <pos>
@@ -25,6 +24,7 @@
 #include <vector>
 
 #include "callable.h"
+#include "harness.h"
 #include "sites.h"
 
 static void print_rows(int rc, sid_callable_row* rows, size_t n)
@@ -56,7 +56,7 @@ struct RowList {
     }
 };
 
-static int run(const std::string& all)
+int mode_callable(const std::string& all)
 {
     size_t p = 0;
     auto next_line = [&]() {
@@ -204,20 +204,4 @@ static int run(const std::string& all)
         }
     }
     return 0;
-}
-
-int main(int argc, char** argv)
-{
-    if (argc != 3 || std::strcmp(argv[1], "callable") != 0) {
-        std::fprintf(stderr, "usage: callable_asan callable CORPUS\n");
-        return 2;
-    }
-    std::FILE* f = std::fopen(argv[2], "rb");
-    if (!f) return 2;
-    std::string all;
-    char buf[1 << 16];
-    size_t k;
-    while ((k = std::fread(buf, 1, sizeof buf, f)) > 0) all.append(buf, k);
-    std::fclose(f);
-    return run(all);
 }

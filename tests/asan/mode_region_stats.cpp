@@ -1,7 +1,6 @@
-// region_stats_asan region_stats CORPUS — region_stats.cpp, regions.cpp and
-// parse.cpp under ASan + UBSan (tests/test_region_stats_asan.py; TEST
-// INFRASTRUCTURE, CPU only): a stand-alone program with its own main, nothing
-// preloaded.
+// sid_asan region_stats CORPUS — region_stats.cpp, regions.cpp and parse.cpp
+// under ASan + UBSan (tests/test_region_stats_asan.py; TEST INFRASTRUCTURE, CPU
+// only).
 //
 // CORPUS is a sequence of cases, each opened by its region set:
 //   "B <bytes>", then <bytes> bytes of BED text and a newline:
@@ -29,6 +28,7 @@
 #include <string>
 #include <vector>
 
+#include "harness.h"
 #include "region_stats.h"
 #include "sites.h"
 
@@ -49,7 +49,7 @@ static void print_rows(int rc, sid_region_row* rows, size_t n)
     sid_region_stats_free(rows);
 }
 
-static int run(const std::string& all)
+int mode_region_stats(const std::string& all)
 {
     size_t p = 0;
     auto next_line = [&]() {
@@ -166,20 +166,4 @@ static int run(const std::string& all)
         sid_regions_free(rg);
     }
     return 0;
-}
-
-int main(int argc, char** argv)
-{
-    if (argc != 3 || std::strcmp(argv[1], "region_stats") != 0) {
-        std::fprintf(stderr, "usage: region_stats_asan region_stats CORPUS\n");
-        return 2;
-    }
-    std::FILE* f = std::fopen(argv[2], "rb");
-    if (!f) return 2;
-    std::string all;
-    char buf[1 << 16];
-    size_t k;
-    while ((k = std::fread(buf, 1, sizeof buf, f)) > 0) all.append(buf, k);
-    std::fclose(f);
-    return run(all);
 }

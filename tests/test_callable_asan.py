@@ -1,33 +1,20 @@
 """callable.cpp -- sid_callable_host, the stitch of the chunks' row lists,
 sid_callable_join and sid_callable_format -- and parse.cpp compiled with
 AddressSanitizer + UndefinedBehaviorSanitizer into a stand-alone program
-(tests/asan_callable: its own main, nothing preloaded) and run over the cases
+(tests/asan, mode callable: its own main, nothing preloaded) and run over the cases
 of tests/test_callable.py plus random site sequences under random cuts and the
 "a site a chunk" cut.  Every array it touches is an exact-size heap block.  A
 sanitizer report fails the test, and every result must equal the Python
 model's.  CPU only."""
 import itertools
-import os
-import subprocess
 
 import numpy as np
-import pytest
 
 import callable_ref as CR
 import depth_ref
 from regions_ref import text_sites
-from sanitized import run
+from sanitized import asan, run   # noqa: F401 (asan: the fixture)
 from test_callable import BOUNDS, SEQ, SEQ_CODES, SEQ_DEPTHS, quirks_text
-
-DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "asan_callable")
-
-
-@pytest.fixture(scope="module")
-def prog():
-    # (hipcc's clang, which the project's own build needs, links the sanitizer runtime into the program: no
-    # skip, a missing tool fails the test)
-    subprocess.run(["make", "-s", "-C", DIR], check=True)
-    return os.path.join(DIR, "_build", "callable_asan")
 
 
 def sequences():
@@ -132,9 +119,9 @@ def corpus():
     return out
 
 
-def test_corpus_sanitized(prog, tmp_path):
+def test_corpus_sanitized(asan, tmp_path):
     cases = corpus()
     p = tmp_path / "corpus.bin"
     p.write_bytes(b"".join(c for c, _ in cases))
-    assert run(prog, "callable", p) == b"".join(w for _, w in cases)
+    assert run(asan, "callable", p) == b"".join(w for _, w in cases)
     assert len(cases) >= 300

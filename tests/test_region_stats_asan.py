@@ -2,34 +2,21 @@
 chunks' row lists, sid_region_stats_merge and sid_region_stats_format --
 regions.cpp (the merge, the source order, sid_regions_interval) and parse.cpp
 compiled with AddressSanitizer + UndefinedBehaviorSanitizer into a stand-alone
-program (tests/asan_region_stats: its own main, nothing preloaded) and run over
+program (tests/asan, mode region_stats: its own main, nothing preloaded) and run over
 the cases of tests/test_region_stats.py plus random BED sets and site
 sequences.  Every array it touches is an exact-size heap block.  A sanitizer
 report fails the test, and every result must equal the Python model's.  CPU
 only."""
-import os
-import subprocess
-
 import numpy as np
-import pytest
 
 import depth_ref
 import region_stats_ref as RS
 from regions_ref import POS_MAX, BedError, parse_bed, text_sites
-from sanitized import run
+from sanitized import asan, run   # noqa: F401 (asan: the fixture)
 from test_region_stats import QUIRKS_BED, pl, want_intervals
 from test_windows import quirks_text
 
-DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "asan_region_stats")
 DROPPED, HET = 0x40, 0x80
-
-
-@pytest.fixture(scope="module")
-def prog():
-    # (hipcc's clang, which the project's own build needs, links the sanitizer runtime into the program: no
-    # skip, a missing tool fails the test)
-    subprocess.run(["make", "-s", "-C", DIR], check=True)
-    return os.path.join(DIR, "_build", "region_stats_asan")
 
 
 def bed_ok(bed: bytes) -> bool:
@@ -183,11 +170,11 @@ def corpus():
     return out
 
 
-def test_corpus_sanitized(prog, tmp_path):
+def test_corpus_sanitized(asan, tmp_path):
     cases = corpus()
     p = tmp_path / "corpus.bin"
     p.write_bytes(b"".join(c for c, _ in cases))
-    got = run(prog, "region_stats", p)
+    got = run(asan, "region_stats", p)
     want = b"".join(w for _, w in cases)
     if got != want:   # (name the first case that differs)
         at = 0

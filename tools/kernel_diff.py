@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Diff the gfx950 code of two builds, symbol by symbol (no GPU needed).
 
-    tools/kernel_diff.py build_parent build [object ...]
+    tools/kernel_diff.py [--rename OLD=NEW]... build_parent build [object ...]
 
-For each object (default: textpath local lynch synth) the device code object
+--rename replaces the substring OLD by NEW in the first build's (mangled)
+symbol names, so that a renamed kernel compares like the rest.  For each object (default: textpath local lynch synth) the device code object
 is unbundled from BUILD/NAME.o and disassembled; every function symbol's
 instruction text (addresses, encodings and comments stripped) is compared.
 Printed: the symbols only in one build, the symbols whose code differs, and
@@ -50,7 +51,12 @@ def disasm(obj, strict):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a != "--strict"]
+    args, renames, it = [], [], iter(sys.argv[1:])
+    for x in it:
+        if x == "--rename":
+            renames.append(next(it).split("=", 1))
+        elif x != "--strict":
+            args.append(x)
     strict = "--strict" in sys.argv[1:]
     if len(args) < 2:
         sys.exit(__doc__)
@@ -59,6 +65,8 @@ def main():
     bad = 0
     for n in names:
         A, B = disasm(os.path.join(a, n + ".o"), strict), disasm(os.path.join(b, n + ".o"), strict)
+        for old, new in renames:
+            A = {s.replace(old, new): v for s, v in A.items()}
         only_a, only_b = sorted(set(A) - set(B)), sorted(set(B) - set(A))
         diff = sorted(s for s in set(A) & set(B) if A[s] != B[s])
         same = len(set(A) & set(B)) - len(diff)
