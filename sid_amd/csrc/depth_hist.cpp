@@ -8,6 +8,7 @@
 #include <cstring>
 #include <map>
 
+#include "rowtable.h"
 #include "sites.h"
 
 bool sid_dh_sort(std::vector<sid_dh_row>* rows)
@@ -106,16 +107,6 @@ extern "C" int sid_depth_hist_merge(const sid_depth_row* a, size_t na, const sid
     return sid_dh_export(merge_rows(a, na, b, nb), out, n);
 }
 
-// decimal digits of u at p; returns their number
-static size_t put_u64(uint64_t u, char* p)
-{
-    char tmp[24];
-    size_t k = 0, w = 0;
-    do tmp[k++] = (char)('0' + u % 10); while (u /= 10);
-    while (k) p[w++] = tmp[--k];
-    return w;
-}
-
 extern "C" int sid_depth_hist_format(const sid_depth_row* rows, size_t n, int with_header, char* buf, size_t cap,
                                      size_t* len)
 {
@@ -130,10 +121,10 @@ extern "C" int sid_depth_hist_format(const sid_depth_row* rows, size_t n, int wi
     char line[5 * 24 + 8];
     for (size_t k = 0; k < n; ++k) {
         const sid_depth_row& r = rows[k];
-        size_t w = put_u64(r.depth, line);
+        size_t w = sid_put_u64(r.depth, line);
         for (uint64_t v : {r.sites, r.records, r.het, r.hom}) {
             line[w++] = ',';
-            w += put_u64(v, line + w);
+            w += sid_put_u64(v, line + w);
         }
         line[w++] = '\n';
         put(line, w);

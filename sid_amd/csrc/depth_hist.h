@@ -27,6 +27,14 @@ struct sid_dh_row {
 };
 static_assert(sizeof(sid_dh_row) == 16, "the device's row layout");
 
+// One bin of the device's per-chunk table, a depth's (all zero between two stage runs).
+struct sid_dh_bin {
+    uint32_t sites;
+    uint32_t het;
+    uint32_t hom;
+};
+static_assert(sizeof(sid_dh_bin) == 12, "the device's bin layout");
+
 constexpr uint32_t SID_DH_BINS = SID_DEPTH_MAX + 1;   // depths 0 .. 262140
 
 // a chunk's rows as read back, sorted by depth in place; false: a depth twice or outside the range

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <string>
 
+#include "rowtable.h"
 #include "sites.h"
 
 bool sid_rs_check(const std::vector<sid_rs_row>& rows, size_t ni)
@@ -155,23 +156,6 @@ extern "C" int sid_region_stats_merge(const sid_region_row* a, const sid_region_
     return SID_OK;
 }
 
-// decimal digits of u at p; returns their number
-static size_t put_u64(uint64_t u, char* p)
-{
-    char tmp[24];
-    size_t k = 0, w = 0;
-    do tmp[k++] = (char)('0' + u % 10); while (u /= 10);
-    while (k) p[w++] = tmp[--k];
-    return w;
-}
-
-static size_t put_i64(int64_t v, char* p)
-{
-    if (v >= 0) return put_u64((uint64_t)v, p);
-    *p = '-';
-    return 1 + put_u64(0 - (uint64_t)v, p + 1);
-}
-
 extern "C" int sid_region_stats_format(const sid_region_row* rows, size_t n, int with_header, char* buf, size_t cap,
                                        size_t* len)
 {
@@ -190,12 +174,12 @@ extern "C" int sid_region_stats_format(const sid_region_row* rows, size_t n, int
         put(r.chrom, r.chrom_len);
         size_t w = 0;
         line[w++] = ',';
-        w += put_i64(r.start, line + w);
+        w += sid_put_i64(r.start, line + w);
         line[w++] = ',';
-        w += put_i64(r.end, line + w);
+        w += sid_put_i64(r.end, line + w);
         for (uint64_t v : {r.sites, r.depth, r.records, r.het, r.hom}) {
             line[w++] = ',';
-            w += put_u64(v, line + w);
+            w += sid_put_u64(v, line + w);
         }
         line[w++] = '\n';
         put(line, w);

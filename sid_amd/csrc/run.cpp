@@ -1799,6 +1799,33 @@ int call_sites(sid_engine* e, Dev& d, const Loaded& L, uint64_t n)
     return sid_lookup_sites(d.ctx, (const uint16_t*)W.counts, n, W.code, W.hom, W.het, d.s_comp);
 }
 
+// The sets (sid_chunk_ws::win_cur, dh.cur, rs.cur) a chunk's stages wrote, -1 before any ran: the next chunk's
+// tile parse takes the other ones before this chunk's rows are read
+struct StageSets {
+    int win = -1, dh = -1, rs = -1;
+};
+static StageSets stage_sets(const sid_chunk_ws& W) { return StageSets{W.win_cur, W.dh.cur, W.rs.cur}; }
+
+// A chunk's rows out of set b of a bin table (the depth histogram's, the region rows'): the set's pinned block,
+// which holds `eager` rows behind its count, or beyond them a copy of their own and sync().  limit: the table's
+// bins -- a set holds them all, so no chunk runs again for it
+template <class Bin, class Row, class Sync>
+static hipError_t bins_take(const sid_bin_sets<Bin, Row>& T, int b, uint64_t limit, uint32_t eager, std::vector<Row>& c,
+                            hipStream_t st, Sync&& sync)
+{
+    const char* hb = T.eager[b];
+    const uint64_t nr = *(const uint64_t*)hb;
+    if (nr > limit) return hipErrorUnknown;
+    c.resize(nr);
+    if (nr <= eager) {
+        if (nr) std::memcpy(c.data(), hb + 16, nr * sizeof(Row));
+        return hipSuccess;
+    }
+    hipError_t x = hipMemcpyAsync(c.data(), T.rows[b], nr * sizeof(Row), hipMemcpyDeviceToHost, st);
+    if (x == hipSuccess) x = sync();
+    return x;
+}
+
 // the compute thread of device d, for one pass
 void compute(sid_engine* e, Dev& d, int pass)
 {
@@ -1829,10 +1856,10 @@ void compute(sid_engine* e, Dev& d, int pass)
     // slots a tile, the next_quad shape)
     bool next_tiled = false, next_quad = false;
     uint32_t next_lg = 0;
-    // the windowed summary: the workspace's set (sid_chunk_ws::win_cur) a chunk's stage wrote -- the next
-    // chunk's tile parse takes the other one before this chunk's rows are read
+    // ... and the sets its stages wrote
+    StageSets next_sets;
+    // the windowed summary
     const bool windows = e->opts.window > 0;
-    int next_wset = 0;
     // (the stage's last kernel stores its counts and first rows into the set's pinned block: win_eager)
     // after the sync: the set held every row and name of the chunk
     auto win_fits = [&](int b) {
@@ -1863,40 +1890,9 @@ void compute(sid_engine* e, Dev& d, int pass)
         if (x == hipSuccess) x = sync();
         return x;
     };
-    // the depth histogram likewise: the set (sid_chunk_ws::dh_cur) a chunk's stage wrote, and its rows out of
-    // the set's pinned block (sid_chunk_ws::dh_eager) or, beyond what it holds, by a copy of their own.  A set
-    // holds every depth: no chunk runs again for it
+    // the depth histogram and the region rows (bins_take)
     const bool dhist = e->depth_hist;
-    int next_dset = 0;
-    auto dh_take = [&](int b, std::vector<sid_dh_row>& c) {
-        const char* hb = W.dh_eager[b];
-        const uint64_t nr = *(const uint64_t*)hb;
-        if (nr > SID_DH_BINS) return hipErrorUnknown;
-        c.resize(nr);
-        if (nr <= SID_DH_EAGER_ROWS) {
-            if (nr) std::memcpy(c.data(), hb + 16, nr * sizeof(sid_dh_row));
-            return hipSuccess;
-        }
-        hipError_t x = hipMemcpyAsync(c.data(), W.dh_rows[b], nr * sizeof(sid_dh_row), hipMemcpyDeviceToHost, d.s_comp);
-        if (x == hipSuccess) x = sync();
-        return x;
-    };
-    // the region rows likewise (sid_chunk_ws::rs_cur, rs_eager): a set holds every interval
     const bool rstats = e->region_stats;
-    int next_rset = 0;
-    auto rs_take = [&](int b, std::vector<sid_rs_row>& c) {
-        const char* hb = W.rs_eager[b];
-        const uint64_t nr = *(const uint64_t*)hb;
-        if (nr > W.rs_ni) return hipErrorUnknown;
-        c.resize(nr);
-        if (nr <= SID_RS_EAGER_ROWS) {
-            if (nr) std::memcpy(c.data(), hb + 16, nr * sizeof(sid_rs_row));
-            return hipSuccess;
-        }
-        hipError_t x = hipMemcpyAsync(c.data(), W.rs_rows[b], nr * sizeof(sid_rs_row), hipMemcpyDeviceToHost, d.s_comp);
-        if (x == hipSuccess) x = sync();
-        return x;
-    };
     auto take = [&](Loaded& out) {
         if (have_next) {
             out = nextL;
@@ -1957,9 +1953,7 @@ void compute(sid_engine* e, Dev& d, int pass)
         bool sunk = false;       // pass 1, device sink: a scratch buffer, dropped
         hipEvent_t pe = nullptr;
         uint64_t n = 0;
-        int wset = pre_tiled ? next_wset : -1;   // the window stage's set of this chunk (none: no stage ran)
-        int dset = pre_tiled ? next_dset : -1;   // ... and the depth histogram's
-        int rset = pre_tiled ? next_rset : -1;   // ... and the region rows'
+        StageSets sets = pre_tiled ? next_sets : StageSets{};   // the stages' sets of this chunk (none: no stage ran)
         // the tile path: this chunk's records and byte count done (recorded
         // before the next chunk's tile parse is queued behind the writer: the
         // host and the records' D2H wait for this, not for that parse, which
@@ -2029,9 +2023,7 @@ void compute(sid_engine* e, Dev& d, int pass)
                     pe = d.prof_begin(P);
                     rc = sid_chunk_tile_local(d.ctx, &W, L.base, L.c0, L.c1, lg, quad, e->conf_type, d.s_comp);
                     d.prof_end(1, pe);
-                    wset = W.win_cur;
-                    dset = W.dh_cur;
-                    rset = W.rs_cur;
+                    sets = stage_sets(W);
                 }
                 if (rc == SID_OK) {
                     pe = d.prof_begin(P);
@@ -2069,9 +2061,7 @@ void compute(sid_engine* e, Dev& d, int pass)
                         d.prof_end(1, pe2);
                         if (rc2 != SID_OK) return (void)fail(e, rc2);
                         next_tiled = x == hipSuccess;
-                        next_wset = W.win_cur;
-                        next_dset = W.dh_cur;
-                        next_rset = W.rs_cur;
+                        next_sets = stage_sets(W);
                         next_lg = lg2;
                         next_quad = q2;
                     }
@@ -2080,8 +2070,8 @@ void compute(sid_engine* e, Dev& d, int pass)
                 if (x != hipSuccess) return (void)hipfail(e, x);
                 const uint64_t maxl = hs[12];
                 // (rows or names beyond the stage's set: the two-pass path sizes it; the next chunks' sets grow)
-                const bool win_over = windows && maxl <= lg && !win_fits(wset);
-                if (win_over) win_want(wset);
+                const bool win_over = windows && maxl <= lg && !win_fits(sets.win);
+                if (win_over) win_want(sets.win);
                 if (maxl <= lg && !win_over) {
                     tiled = true;
                     ++d.tiled;
@@ -2293,9 +2283,7 @@ void compute(sid_engine* e, Dev& d, int pass)
                               : sid_chunk_fmt_len(&W, L.base, L.c1, n, e->conf_type, d.s_comp);
                 d.prof_end(4, pe);
                 if (rc != SID_OK) return (void)fail(e, rc);
-                wset = W.win_cur;
-                dset = W.dh_cur;
-                rset = W.rs_cur;
+                sets = stage_sets(W);
                 pe = d.prof_begin(P);
                 rc = fused    ? sid_chunk_local_put(d.ctx, &W, L.base, L.c1, n, e->conf_type, out, d.s_comp)
                      : lfused ? sid_chunk_lynch_put(d.ctx, &W, L.base, L.c1, n, out, d.s_comp)
@@ -2376,17 +2364,17 @@ void compute(sid_engine* e, Dev& d, int pass)
         if (windows) {   // (likewise; a chunk without sites: no stage ran, no row)
             r.win.clear();
             if (out) {
-                if (wset < 0 || !win_fits(wset)) return (void)fail(e, SID_ESTATE);   // (the two-pass stage sized its set)
-                win_want(wset);
-                x = win_take(wset, r.win);
+                if (sets.win < 0 || !win_fits(sets.win)) return (void)fail(e, SID_ESTATE);   // (the two-pass stage sized its set)
+                win_want(sets.win);
+                x = win_take(sets.win, r.win);
                 if (x != hipSuccess) return (void)hipfail(e, x);
             }
         }
         if (dhist) {   // (likewise)
             r.dh.clear();
             if (out) {
-                if (dset < 0) return (void)fail(e, SID_ESTATE);
-                x = dh_take(dset, r.dh);
+                if (sets.dh < 0) return (void)fail(e, SID_ESTATE);
+                x = bins_take(W.dh, sets.dh, SID_DH_BINS, SID_DH_EAGER_ROWS, r.dh, d.s_comp, sync);
                 if (x != hipSuccess) return (void)hipfail(e, x);
                 if (!sid_dh_sort(&r.dh)) return (void)fail(e, SID_ESTATE);
             }
@@ -2394,10 +2382,10 @@ void compute(sid_engine* e, Dev& d, int pass)
         if (rstats) {   // (likewise)
             r.rs.clear();
             if (out) {
-                if (rset < 0) return (void)fail(e, SID_ESTATE);
-                x = rs_take(rset, r.rs);
+                if (sets.rs < 0) return (void)fail(e, SID_ESTATE);
+                x = bins_take(W.rs, sets.rs, W.rs.n, SID_RS_EAGER_ROWS, r.rs, d.s_comp, sync);
                 if (x != hipSuccess) return (void)hipfail(e, x);
-                if (!sid_rs_check(r.rs, W.rs_ni)) return (void)fail(e, SID_ESTATE);
+                if (!sid_rs_check(r.rs, W.rs.n)) return (void)fail(e, SID_ESTATE);
             }
         }
         release_slot();

@@ -199,6 +199,20 @@ struct sid_ctx {
 typedef uint32_t sid_off_t;
 constexpr uint64_t SID_CHUNK_MAX = (4ull << 30) - (1ull << 20);   // bytes a chunk may span
 
+// A bin table of a chunk workspace with its rows: one table of bins, all zero between two stage runs (the
+// pack kernel clears the bins it read), and two sets of {count, rows, pinned block} used in turn, as the
+// window stage's -- a chunk's tile parse runs before the host has read the previous chunk's rows
+template <class Bin, class Row>
+struct sid_bin_sets {
+    Bin* bins = nullptr;
+    unsigned long long* cnt[2] = {nullptr, nullptr};   // the chunk's rows (the bins touched)
+    Row* rows[2] = {nullptr, nullptr};
+    char* eager[2] = {nullptr, nullptr};   // pinned host memory: the set's count and first rows, stored by the
+                                           // pack kernel (SID_DH_EAGER_BYTES, SID_RS_EAGER_BYTES)
+    uint32_t n = 0;             // the bins the buffers were sized for
+    int cur = 0;                // the set the last stage wrote
+};
+
 struct sid_chunk_ws {
     uint64_t site_cap = 0, tile_cap = 0;
     sid_off_t* starts = nullptr;  // line start offsets (relative to the chunk's base)
@@ -280,32 +294,16 @@ struct sid_chunk_ws {
     uint32_t win_cap[2] = {0, 0}, win_ncap[2] = {0, 0};
     uint64_t win_want_rows = 0, win_want_names = 0;
     int win_cur = 0;            // the set the last stage wrote
-    // the depth histogram's stage (the owner's sid_engine_set_depth_hist; depth_hist.h, textpath.hip
-    // sid_depth_hist_*_kernel), beside the window stage: one table of three u32 counters per depth (sites,
-    // het, hom records; all zero between two stage runs -- the pack kernel clears the bins it read), and two
-    // sets of {count, rows, pinned block} used in turn, as the window stage's.  A set's rows hold every
-    // depth (SID_DH_BINS rows), so no chunk outgrows it
+    // the bin-rows stages (textpath.hip bin_stage, sid_bins_pack_kernel), beside the window stage: a
+    // sid_bin_sets each, whose rows hold every bin, so no chunk outgrows a set
+    //   dh  the depth histogram (the owner's sid_engine_set_depth_hist; depth_hist.h): a bin per depth
+    //   rs  the region rows (the owner's sid_engine_set_region_stats; region_stats.h): a bin per interval of
+    //       rs_tab, the owner's region set whatever selects (its context's regtab), or null
     bool dh_on = false;
-    uint32_t* dh_bins = nullptr;
-    unsigned long long* dh_cnt[2] = {nullptr, nullptr};   // the chunk's rows (the bins touched)
-    struct sid_dh_row* dh_rows[2] = {nullptr, nullptr};
-    char* dh_eager[2] = {nullptr, nullptr};    // pinned host memory: the set's count and first rows, stored by the
-                                               // pack kernel (SID_DH_EAGER_BYTES)
-    int dh_cur = 0;             // the set the last stage wrote
-    // the region rows' stage (the owner's sid_engine_set_region_stats; region_stats.h, textpath.hip
-    // sid_region_stats_*_kernel), beside the depth histogram's: one table of a bin per interval of rs_tab
-    // (sid_rs_bin; all zero between two stage runs -- the pack kernel clears the bins it read), and two sets
-    // of {count, rows, pinned block} used in turn.  A set's rows hold every interval (rs_tab->ni rows), so no
-    // chunk outgrows it.  rs_tab: the owner's region set whatever selects (its context's regtab), or null
+    sid_bin_sets<struct sid_dh_bin, struct sid_dh_row> dh;
     bool rs_on = false;
     const sid_regtab* rs_tab = nullptr;
-    struct sid_rs_bin* rs_bins = nullptr;
-    unsigned long long* rs_cnt[2] = {nullptr, nullptr};   // the chunk's rows (the bins touched)
-    struct sid_rs_row* rs_rows[2] = {nullptr, nullptr};
-    char* rs_eager[2] = {nullptr, nullptr};    // pinned host memory: the set's count and first rows, stored by the
-                                               // pack kernel (SID_RS_EAGER_BYTES)
-    uint32_t rs_ni = 0;         // the intervals the buffers were sized for
-    int rs_cur = 0;             // the set the last stage wrote
+    sid_bin_sets<struct sid_rs_bin, struct sid_rs_row> rs;
 };
 // the region rows that reach the host with every chunk's byte count (more: a copy of their own), behind two
 // words of count: 24 B a row (a 128 MiB chunk of an exome-like set touches a few thousand intervals, a

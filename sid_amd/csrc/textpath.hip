@@ -4943,28 +4943,128 @@ static void launch_runs_fill(RunArgs<P, Off>& C, const RunBufs<P>& B, hipStream_
     sid_runs_fill_kernel<P, MODE, OPT, Off><<<(unsigned)nb, FTB, 0, st>>>(C);
 }
 
+// --------------------------------------------------------------- bin rows --
+// The bin-rows stages: the depth histogram (DhBins) and the region rows
+// (RsBins), each a table of bins that a binning kernel of its own fills with
+// integer atomics.  What they share:
+//   claim  the add that finds a bin's site counter at 0 appends the bin's
+//          index to the set's rows (bin_claim): the chunk's bins, each once,
+//          in no order.
+//   pack   one block (a chunk has a few hundred rows, and the block that has
+//          read the count is the one that clears it), a thread per appended
+//          bin: the bin's columns into its row, the bin cleared -- the table
+//          is all zero again for the next chunk without a memset -- and the
+//          count and the first P::EAGER rows stored into the set's pinned
+//          block, which the host reads after the sync that brings the chunk's
+//          byte count (as win_eager; more rows: a copy from the set's device
+//          rows).  The set's count is zero before and after, as the bins are.
+// A policy P names the bin, the row, the row's index word, the pinned block's
+// rows and bytes, how a row takes its bin (take: false for an index outside the
+// table, which bin_claim never stores), and on the host the workspace's sets
+// and what a stage needs of the workspace besides them (bind).
+struct DhBins {
+    typedef sid_dh_bin Bin;
+    typedef sid_dh_row Row;
+    static constexpr uint32_t EAGER = SID_DH_EAGER_ROWS;
+    static constexpr size_t EAGER_BYTES = SID_DH_EAGER_BYTES;
+    static __device__ __forceinline__ uint32_t& index(Row& r) { return r.depth; }
+    // depth d's bin, in word arithmetic (three words a bin): d < SID_DH_BINS makes it a 24-bit multiply and a
+    // 32-bit offset, where bins + d costs a 64-bit multiply-add
+    static __device__ __forceinline__ Bin* bin(Bin* bins, uint32_t d) { return (Bin*)(&bins->sites + 3 * (size_t)d); }
+    static __device__ __forceinline__ bool take(Row& r, Bin* bins, uint32_t)
+    {
+        if (r.depth >= SID_DH_BINS) return false;
+        Bin* b = bin(bins, r.depth);
+        r.sites = b->sites, r.het = b->het, r.hom = b->hom;
+        b->sites = b->het = b->hom = 0;
+        return true;
+    }
+    static sid_bin_sets<Bin, Row>& sets(sid_chunk_ws* W) { return W->dh; }
+    template <class Off>
+    static bool bind(const sid_chunk_ws*, SiteArgs<Off>*) { return true; }
+};
+struct RsBins {
+    typedef sid_rs_bin Bin;
+    typedef sid_rs_row Row;
+    static constexpr uint32_t EAGER = SID_RS_EAGER_ROWS;
+    static constexpr size_t EAGER_BYTES = SID_RS_EAGER_BYTES;
+    static __device__ __forceinline__ uint32_t& index(Row& r) { return r.idx; }
+    static __device__ __forceinline__ bool take(Row& r, Bin* bins, uint32_t cap)
+    {
+        if (r.idx >= cap) return false;
+        Bin* b = bins + r.idx;
+        r.depth = b->depth, r.sites = b->sites, r.het = b->het, r.hom = b->hom;
+        b->depth = 0, b->sites = b->het = b->hom = 0;
+        return true;
+    }
+    static sid_bin_sets<Bin, Row>& sets(sid_chunk_ws* W) { return W->rs; }
+    // (the region set the table was sized for, into the sites' view)
+    template <class Off>
+    static bool bind(const sid_chunk_ws* W, SiteArgs<Off>* A)
+    {
+        if (!W->rs_tab || W->rs_tab->ni != W->rs.n) return false;
+        A->T = *W->rs_tab;
+        return true;
+    }
+};
+
+// behind the adds to bin j (< cap), whose site counter was `old`: its first sites of this chunk claim its row
+template <class P>
+__device__ __forceinline__ void bin_claim(uint32_t old, unsigned long long* cnt, typename P::Row* rows, uint32_t cap,
+                                          uint32_t j)
+{
+    if (old != 0) return;
+    const unsigned long long at = atomicAdd(cnt, 1ull);
+    if (at < cap) P::index(rows[at]) = j;
+}
+
+// (out: where the count goes -- the set's pinned block, or a call's own word)
+template <class P>
+__global__ __launch_bounds__(SCAN_TB) void sid_bins_pack_kernel(unsigned long long* __restrict__ cnt,
+                                                                typename P::Bin* __restrict__ bins,
+                                                                typename P::Row* __restrict__ rows, uint32_t cap,
+                                                                char* __restrict__ eager,
+                                                                unsigned long long* __restrict__ out)
+{
+    typedef typename P::Row Row;
+    const uint64_t n = min((uint64_t)cnt[0], (uint64_t)cap);
+    __syncthreads();
+    if (threadIdx.x == 0) cnt[0] = 0;   // (zero again for the next chunk, as the bins)
+    if (threadIdx.x < 2) out[threadIdx.x] = threadIdx.x ? 0ull : n;
+    Row* er = eager ? (Row*)(eager + 16) : nullptr;
+    for (uint64_t k = threadIdx.x; k < n; k += SCAN_TB) {
+        Row r = rows[k];
+        if (!P::take(r, bins, cap)) continue;
+        rows[k] = r;
+        if (er && k < P::EAGER) er[k] = r;
+    }
+}
+
+// a stage's device buffers: a sid_bin_sets of sid_chunk_ws (the engine) or a call's own
+template <class P>
+struct BinBufs {
+    typename P::Bin* bins;
+    uint32_t n;                // the bins, and the rows a set holds
+    unsigned long long* cnt;
+    typename P::Row* rows;
+    char* eager;               // (or null: the caller copies the rows)
+    unsigned long long* out;   // two words for the chunk's row count: the head of `eager`, or a call's own
+};
+
 // -------------------------------------------------------- depth histogram --
 // The depth histogram (sid_engine_set_depth_hist; depth_hist.h): per depth the
 // chunk's sites, het records and hom records.  The stage reads what the window
 // stage reads, through the same loaders -- sv_site on the unfiltered tables,
 // sv_label, and sv_depth for the bin -- and runs beside it, in front of the
-// marking stages.  Two steps:
-// (the set's count is zero before and after, as the bins are)
+// marking stages.  A bin-rows stage (above), whose binning step is:
 //   hist   a block walks 512-slot groups (grid-stride) and bins its sites of
 //          depth < DH_LDS in LDS, one 64-bit word a bin: sites, het and hom in
 //          21-bit fields (a block sees at most DH_GROUPS_MAX groups = 2^20
 //          sites), so a site costs one LDS atomic.  At the end the block adds
 //          its non-zero bins to the chunk's table with global atomics: a 30x
 //          chunk some 80 bins a block instead of 3 counters a site.  Depths
-//          from DH_LDS on are rare and go straight to the table.  The add
-//          that finds a bin's site counter at 0 appends the depth to the
-//          set's rows: the chunk's bins, each once, in no order.
-//   pack   a thread per appended depth: the bin's three counters into its row,
-//          the bin cleared -- the table is all zero again for the next chunk
-//          without a 3 MB memset -- and the count and the first
-//          SID_DH_EAGER_ROWS rows stored into the set's pinned block, which the
-//          host reads after the sync that brings the chunk's byte count (as
-//          win_eager; more rows: a copy from the set's device rows).
+//          from DH_LDS on are rare and go straight to the table (3 MB: the
+//          memset a chunk that the pack spares).
 // FORM, the way a wave's lanes reach the LDS bins (the environment
 // variable SID_DH_FORM picks one, a measurement switch):
 //   0  every lane its own LDS atomic
@@ -4982,24 +5082,21 @@ template <class Off>
 struct DhArgs {
     SiteArgs<Off> A;              // the sites
     uint64_t ng;                  // their 512-slot groups
-    uint32_t* bins;               // per depth: [0] sites [1] het records [2] hom records
+    sid_dh_bin* bins;             // per depth
     unsigned long long* cnt;      // the rows appended
     sid_dh_row* rows;
     uint32_t cap;                 // (SID_DH_BINS: every depth fits)
 };
 
 // s sites (>= 1), h het and m hom records of depth d (< SID_DH_BINS) into the table
-__device__ __forceinline__ void dh_table_add(uint32_t* bins, unsigned long long* cnt, sid_dh_row* rows, uint32_t cap,
+__device__ __forceinline__ void dh_table_add(sid_dh_bin* bins, unsigned long long* cnt, sid_dh_row* rows, uint32_t cap,
                                              uint32_t d, uint32_t s, uint32_t h, uint32_t m)
 {
-    uint32_t* b = bins + 3 * (size_t)d;
-    const uint32_t old = atomicAdd(b, s);
-    if (h) atomicAdd(b + 1, h);
-    if (m) atomicAdd(b + 2, m);
-    if (old == 0) {   // the bin's first sites of this chunk: its row
-        const unsigned long long at = atomicAdd(cnt, 1ull);
-        if (at < cap) rows[at].depth = d;
-    }
+    sid_dh_bin* b = DhBins::bin(bins, d);
+    const uint32_t old = atomicAdd(&b->sites, s);
+    if (h) atomicAdd(&b->het, h);
+    if (m) atomicAdd(&b->hom, m);
+    bin_claim<DhBins>(old, cnt, rows, cap, d);
 }
 
 template <int MODE, bool OPT, int FORM, class Off>
@@ -5048,30 +5145,6 @@ __global__ __launch_bounds__(FTB) void sid_depth_hist_kernel(const DhArgs<Off> C
     }
 }
 
-// (one block: a chunk has a few hundred rows, and the block that has read the count is the one that clears it.
-// out: where the count goes -- the set's pinned block, or a call's own word)
-__global__ __launch_bounds__(SCAN_TB) void sid_depth_hist_pack_kernel(unsigned long long* __restrict__ cnt,
-                                                                      uint32_t* __restrict__ bins,
-                                                                      sid_dh_row* __restrict__ rows, uint32_t cap,
-                                                                      char* __restrict__ eager,
-                                                                      unsigned long long* __restrict__ out)
-{
-    const uint64_t n = min((uint64_t)cnt[0], (uint64_t)cap);
-    __syncthreads();
-    if (threadIdx.x == 0) cnt[0] = 0;   // (zero again for the next chunk, as the bins)
-    if (threadIdx.x < 2) out[threadIdx.x] = threadIdx.x ? 0ull : n;
-    sid_dh_row* er = eager ? (sid_dh_row*)(eager + 16) : nullptr;
-    for (uint64_t k = threadIdx.x; k < n; k += SCAN_TB) {
-        sid_dh_row r = rows[k];
-        if (r.depth >= SID_DH_BINS) continue;   // (never: dh_table_add stores a bin's index)
-        uint32_t* b = bins + 3 * (size_t)r.depth;
-        r.sites = b[0], r.het = b[1], r.hom = b[2];
-        b[0] = b[1] = b[2] = 0;
-        rows[k] = r;
-        if (er && k < SID_DH_EAGER_ROWS) er[k] = r;
-    }
-}
-
 // 1: a wave's distinct depths one by one; 0: a lane an LDS atomic (SID_DH_FORM, a measurement switch)
 #ifndef SID_DH_FORM_DEFAULT
 #define SID_DH_FORM_DEFAULT 0
@@ -5085,29 +5158,18 @@ static int dh_form()
     return form;
 }
 
-// the stage's device buffers: sid_chunk_ws's dh_* (the engine) or a call's own
-struct DhBufs {
-    uint32_t* bins;
-    unsigned long long* cnt;
-    sid_dh_row* rows;
-    char* eager;               // (or null: the caller copies the rows)
-    unsigned long long* out;   // two words for the chunk's row count: the head of `eager`, or a call's own
-};
-
-// the histogram of A's sites into B's rows; B.bins and B.cnt are all zero before and after
+// A's sites into B's bins (SID_DH_BINS of them)
 template <int MODE, bool OPT, class Off>
-static void launch_depth_hist(const SiteArgs<Off>& A, const DhBufs& B, hipStream_t st)
+static void launch_binning(const SiteArgs<Off>& A, const BinBufs<DhBins>& B, hipStream_t st)
 {
     DhArgs<Off> C{};
     C.A = A;
     C.ng = (A.s1 - A.s0 + FTB - 1) / FTB;
-    C.bins = B.bins, C.cnt = B.cnt, C.rows = B.rows, C.cap = SID_DH_BINS;
-    if (C.ng) {
-        const uint64_t grid = std::max<uint64_t>(std::min<uint64_t>(C.ng, DH_GRID), (C.ng + DH_GROUPS_MAX - 1) / DH_GROUPS_MAX);
-        if (dh_form()) sid_depth_hist_kernel<MODE, OPT, 1, Off><<<(unsigned)grid, FTB, 0, st>>>(C);
-        else sid_depth_hist_kernel<MODE, OPT, 0, Off><<<(unsigned)grid, FTB, 0, st>>>(C);
-    }
-    sid_depth_hist_pack_kernel<<<1, SCAN_TB, 0, st>>>(B.cnt, B.bins, B.rows, SID_DH_BINS, B.eager, B.out);
+    C.bins = B.bins, C.cnt = B.cnt, C.rows = B.rows, C.cap = B.n;
+    if (!C.ng) return;
+    const uint64_t grid = std::max<uint64_t>(std::min<uint64_t>(C.ng, DH_GRID), (C.ng + DH_GROUPS_MAX - 1) / DH_GROUPS_MAX);
+    if (dh_form()) sid_depth_hist_kernel<MODE, OPT, 1, Off><<<(unsigned)grid, FTB, 0, st>>>(C);
+    else sid_depth_hist_kernel<MODE, OPT, 0, Off><<<(unsigned)grid, FTB, 0, st>>>(C);
 }
 
 // ----------------------------------------------------------- region rows --
@@ -5116,7 +5178,7 @@ static void launch_depth_hist(const SiteArgs<Off>& A, const DhBufs& B, hipStream
 // records.  The stage reads what the region stage and the depth histogram read
 // together -- sv_site on the unfiltered tables, sv_head for the search,
 // sv_label, sv_depth -- and runs beside the histogram, in front of the marking
-// stages.  Two steps, the histogram's:
+// stages.  A bin-rows stage (above), whose binning step is:
 //   bin    reg_index, reg_inside's sibling, gives every slot its interval's
 //          index in the flat table (RS_NONE: no site, or outside).  Sorted
 //          input with long intervals -- in the limit one whole-chromosome
@@ -5133,13 +5195,9 @@ static void launch_depth_hist(const SiteArgs<Off>& A, const DhBufs& B, hipStream
 //            - a block therefore takes a contiguous run of 512-slot groups, not
 //              a grid stride, and at its end the eight waves' carries meet in
 //              LDS, where equal indices are summed before they go out.
-//          A whole-chromosome interval costs one set of atomics a block.  The
-//          add that finds a bin's site counter at 0 appends the index to the
-//          set's rows, as dh_table_add.  Integer atomics only: the rows are
-//          exact whatever the order of arrival.
-//   pack   one block: the touched bins into their rows, the bins and the count
-//          cleared (no memset a chunk), the count and the first
-//          SID_RS_EAGER_ROWS rows into the set's pinned block.
+//          A whole-chromosome interval costs one set of atomics a block.
+//          Integer atomics only: the rows are exact whatever the order of
+//          arrival.
 // FORM (the environment variable SID_RS_FORM picks one, a
 // measurement switch): 0 the carry as above; 1 no carry, every wave adds its
 // rounds' sums straight to the table.
@@ -5226,10 +5284,7 @@ __device__ __forceinline__ void rs_table_add(sid_rs_bin* bins, unsigned long lon
     if (h) atomicAdd(&b->het, h);
     if (m) atomicAdd(&b->hom, m);
     if (d) atomicAdd(&b->depth, d);
-    if (old == 0) {   // the bin's first sites of this chunk: its row
-        const unsigned long long at = atomicAdd(cnt, 1ull);
-        if (at < cap) rows[at].idx = j;
-    }
+    bin_claim<RsBins>(old, cnt, rows, cap, j);
 }
 
 template <int MODE, bool OPT, int FORM, class Off>
@@ -5301,30 +5356,6 @@ __global__ __launch_bounds__(FTB) void sid_region_stats_kernel(const RsArgs<Off>
     }
 }
 
-// (one block, as the histogram's pack: the block that has read the count is the one that clears it.  out: where
-// the count goes -- the set's pinned block, or a call's own word)
-__global__ __launch_bounds__(SCAN_TB) void sid_region_stats_pack_kernel(unsigned long long* __restrict__ cnt,
-                                                                        sid_rs_bin* __restrict__ bins,
-                                                                        sid_rs_row* __restrict__ rows, uint32_t cap,
-                                                                        char* __restrict__ eager,
-                                                                        unsigned long long* __restrict__ out)
-{
-    const uint64_t n = min((uint64_t)cnt[0], (uint64_t)cap);
-    __syncthreads();
-    if (threadIdx.x == 0) cnt[0] = 0;   // (zero again for the next chunk, as the bins)
-    if (threadIdx.x < 2) out[threadIdx.x] = threadIdx.x ? 0ull : n;
-    sid_rs_row* er = eager ? (sid_rs_row*)(eager + 16) : nullptr;
-    for (uint64_t k = threadIdx.x; k < n; k += SCAN_TB) {
-        sid_rs_row r = rows[k];
-        if (r.idx >= cap) continue;   // (never: rs_table_add stores a bin's index)
-        sid_rs_bin* b = bins + r.idx;
-        r.depth = b->depth, r.sites = b->sites, r.het = b->het, r.hom = b->hom;
-        b->depth = 0, b->sites = b->het = b->hom = 0;
-        rows[k] = r;
-        if (er && k < SID_RS_EAGER_ROWS) er[k] = r;
-    }
-}
-
 // 0: the carry; 1: every wave adds its rounds' sums to the table (SID_RS_FORM, a measurement switch)
 static int rs_form()
 {
@@ -5335,31 +5366,28 @@ static int rs_form()
     return form;
 }
 
-// the stage's device buffers: sid_chunk_ws's rs_* (the engine) or a call's own
-struct RsBufs {
-    sid_rs_bin* bins;
-    unsigned long long* cnt;
-    sid_rs_row* rows;
-    char* eager;               // (or null: the caller copies the rows)
-    unsigned long long* out;   // two words for the chunk's row count: the head of `eager`, or a call's own
-};
-
-// the region rows of A's sites (A.T: the set, whose ni bins and rows B holds) into B's rows; B.bins and B.cnt
-// are all zero before and after
+// A's sites (A.T: the region set) into B's bins (A.T.ni of them)
 template <int MODE, bool OPT, class Off>
-static void launch_region_stats(const SiteArgs<Off>& A, const RsBufs& B, hipStream_t st)
+static void launch_binning(const SiteArgs<Off>& A, const BinBufs<RsBins>& B, hipStream_t st)
 {
     RsArgs<Off> C{};
     C.A = A;
     C.ng = (A.s1 - A.s0 + FTB - 1) / FTB;
-    C.bins = B.bins, C.cnt = B.cnt, C.rows = B.rows, C.cap = A.T.ni;
-    if (C.ng && A.T.ni) {
-        C.gpb = std::max<uint64_t>((C.ng + RS_GRID - 1) / RS_GRID, RS_GPB_MIN);
-        const uint64_t grid = (C.ng + C.gpb - 1) / C.gpb;
-        if (rs_form()) sid_region_stats_kernel<MODE, OPT, 1, Off><<<(unsigned)grid, FTB, 0, st>>>(C);
-        else sid_region_stats_kernel<MODE, OPT, 0, Off><<<(unsigned)grid, FTB, 0, st>>>(C);
-    }
-    sid_region_stats_pack_kernel<<<1, SCAN_TB, 0, st>>>(B.cnt, B.bins, B.rows, A.T.ni, B.eager, B.out);
+    C.bins = B.bins, C.cnt = B.cnt, C.rows = B.rows, C.cap = B.n;
+    if (!C.ng || !B.n) return;
+    C.gpb = std::max<uint64_t>((C.ng + RS_GRID - 1) / RS_GRID, RS_GPB_MIN);
+    const uint64_t grid = (C.ng + C.gpb - 1) / C.gpb;
+    if (rs_form()) sid_region_stats_kernel<MODE, OPT, 1, Off><<<(unsigned)grid, FTB, 0, st>>>(C);
+    else sid_region_stats_kernel<MODE, OPT, 0, Off><<<(unsigned)grid, FTB, 0, st>>>(C);
+}
+
+// the bin-rows stage of A's sites into B's rows: the policy's binning kernel, then the pack; B.bins and B.cnt
+// are all zero before and after
+template <int MODE, bool OPT, class P, class Off>
+static void launch_bins(const SiteArgs<Off>& A, const BinBufs<P>& B, hipStream_t st)
+{
+    launch_binning<MODE, OPT>(A, B, st);
+    sid_bins_pack_kernel<P><<<1, SCAN_TB, 0, st>>>(B.cnt, B.bins, B.rows, B.n, B.eager, B.out);
 }
 
 // tails of the U classes (one thread each), then the dense codes' lengths
@@ -6147,6 +6175,41 @@ static int dtext_runs(RunArgs<P, uint64_t>& C, hipStream_t st, Chunk* ch)
     return rc;
 }
 
+// The bin-rows stage over A's sites with a table of n bins (at least one), a count and rows of the call's own:
+// the touched bins' rows read back into ch.
+template <class P>
+static int dtext_bins(const SiteArgs<uint64_t>& A, uint32_t n, hipStream_t st, std::vector<typename P::Row>* ch)
+{
+    typedef typename P::Bin Bin;
+    typedef typename P::Row Row;
+    const size_t o_rows = ((size_t)n * sizeof(Bin) + 15) & ~(size_t)15, o_cnt = o_rows + (size_t)n * sizeof(Row);
+    char* d_ws = nullptr;
+    int rc = SID_OK;
+    auto hip = [&](hipError_t x) {
+        if (x != hipSuccess && rc == SID_OK) rc = sid_set_hip_error(x);
+        return rc == SID_OK;
+    };
+    // (the call's words behind the rows: [0] the stage's count, [2] [3] the pack's copy of it)
+    if (hip(hipMalloc(&d_ws, o_cnt + 32)) && hip(hipMemsetAsync(d_ws, 0, o_rows, st)) &&
+        hip(hipMemsetAsync(d_ws + o_cnt, 0, 32, st))) {
+        const BinBufs<P> B{(Bin*)d_ws, n, (unsigned long long*)(d_ws + o_cnt), (Row*)(d_ws + o_rows), nullptr,
+                           (unsigned long long*)(d_ws + o_cnt + 16)};
+        launch_bins<REG_CODE, false>(A, B, st);
+        hip(hipGetLastError());
+        unsigned long long nr = 0;
+        hip(hipMemcpyAsync(&nr, B.out, 8, hipMemcpyDeviceToHost, st));
+        hip(hipStreamSynchronize(st));
+        if (rc == SID_OK && nr > n) rc = SID_ESTATE;
+        if (rc == SID_OK && nr) {
+            ch->resize(nr);
+            hip(hipMemcpyAsync(ch->data(), B.rows, nr * sizeof(Row), hipMemcpyDeviceToHost, st));
+            hip(hipStreamSynchronize(st));
+        }
+    }
+    if (d_ws) (void)hipFree(d_ws);
+    return rc;
+}
+
 // The window stage over a resident shard (the engine's, without chunk edges): buffers of this call's own,
 // the rows sized from the counts.
 extern "C" int sid_dtext_windows(sid_ctx* ctx, const sid_dtext* T, size_t begin, size_t end, const uint8_t* d_code,
@@ -6185,33 +6248,9 @@ extern "C" int sid_dtext_depth_hist(sid_ctx* ctx, const sid_dtext* T, size_t beg
     if (end == begin) return sid_dh_export(tab, rows, n);
     if (end - begin >= (1ull << 32)) return SID_EINVAL;   // (the stage's counters are a chunk's: 32 bits)
     TCHECK(hipSetDevice(T->device));
-    hipStream_t st = (hipStream_t)stream;
-    const size_t o_rows = ((size_t)SID_DH_BINS * 3 * 4 + 15) & ~(size_t)15, o_cnt = o_rows + (size_t)SID_DH_BINS * sizeof(sid_dh_row);
-    char* d_ws = nullptr;
-    int rc = SID_OK;
-    auto hip = [&](hipError_t x) {
-        if (x != hipSuccess && rc == SID_OK) rc = sid_set_hip_error(x);
-        return rc == SID_OK;
-    };
     std::vector<sid_dh_row> ch;
-    // (the call's words behind the rows: [0] the stage's count, [2] [3] the pack's copy of it)
-    if (hip(hipMalloc(&d_ws, o_cnt + 32)) && hip(hipMemsetAsync(d_ws, 0, o_rows, st)) &&
-        hip(hipMemsetAsync(d_ws + o_cnt, 0, 32, st))) {
-        const DhBufs B{(uint32_t*)d_ws, (unsigned long long*)(d_ws + o_cnt), (sid_dh_row*)(d_ws + o_rows), nullptr,
-                       (unsigned long long*)(d_ws + o_cnt + 16)};
-        launch_depth_hist<REG_CODE, false>(dtext_view(T, begin, end, const_cast<uint8_t*>(d_code)), B, st);
-        hip(hipGetLastError());
-        unsigned long long nr = 0;
-        hip(hipMemcpyAsync(&nr, B.out, 8, hipMemcpyDeviceToHost, st));
-        hip(hipStreamSynchronize(st));
-        if (rc == SID_OK && nr > SID_DH_BINS) rc = SID_ESTATE;
-        if (rc == SID_OK && nr) {
-            ch.resize(nr);
-            hip(hipMemcpyAsync(ch.data(), B.rows, nr * sizeof(sid_dh_row), hipMemcpyDeviceToHost, st));
-            hip(hipStreamSynchronize(st));
-        }
-    }
-    if (d_ws) (void)hipFree(d_ws);
+    const int rc = dtext_bins<DhBins>(dtext_view(T, begin, end, const_cast<uint8_t*>(d_code)), SID_DH_BINS,
+                                      (hipStream_t)stream, &ch);
     if (rc != SID_OK) return rc;
     if (!sid_dh_sort(&ch)) return SID_ESTATE;
     sid_dh_add(&tab, ch);
@@ -6232,35 +6271,10 @@ extern "C" int sid_dtext_region_stats(sid_ctx* ctx, const sid_dtext* T, size_t b
     if (end == begin || ni == 0) return sid_rs_export(rg, tab, true, rows, n);
     if (end - begin >= (1ull << 32)) return SID_EINVAL;   // (the stage's counters are a chunk's: 32 bits)
     TCHECK(hipSetDevice(T->device));
-    hipStream_t st = (hipStream_t)stream;
-    const size_t o_rows = (ni * sizeof(sid_rs_bin) + 15) & ~(size_t)15, o_cnt = o_rows + ni * sizeof(sid_rs_row);
-    char* d_ws = nullptr;
-    int rc = SID_OK;
-    auto hip = [&](hipError_t x) {
-        if (x != hipSuccess && rc == SID_OK) rc = sid_set_hip_error(x);
-        return rc == SID_OK;
-    };
+    SiteArgs<uint64_t> A = dtext_view(T, begin, end, const_cast<uint8_t*>(d_code));
+    A.T = ctx->regtab;
     std::vector<sid_rs_row> ch;
-    // (the call's words behind the rows: [0] the stage's count, [2] [3] the pack's copy of it)
-    if (hip(hipMalloc(&d_ws, o_cnt + 32)) && hip(hipMemsetAsync(d_ws, 0, o_rows, st)) &&
-        hip(hipMemsetAsync(d_ws + o_cnt, 0, 32, st))) {
-        const RsBufs B{(sid_rs_bin*)d_ws, (unsigned long long*)(d_ws + o_cnt), (sid_rs_row*)(d_ws + o_rows), nullptr,
-                       (unsigned long long*)(d_ws + o_cnt + 16)};
-        SiteArgs<uint64_t> A = dtext_view(T, begin, end, const_cast<uint8_t*>(d_code));
-        A.T = ctx->regtab;
-        launch_region_stats<REG_CODE, false>(A, B, st);
-        hip(hipGetLastError());
-        unsigned long long nr = 0;
-        hip(hipMemcpyAsync(&nr, B.out, 8, hipMemcpyDeviceToHost, st));
-        hip(hipStreamSynchronize(st));
-        if (rc == SID_OK && nr > ni) rc = SID_ESTATE;
-        if (rc == SID_OK && nr) {
-            ch.resize(nr);
-            hip(hipMemcpyAsync(ch.data(), B.rows, nr * sizeof(sid_rs_row), hipMemcpyDeviceToHost, st));
-            hip(hipStreamSynchronize(st));
-        }
-    }
-    if (d_ws) (void)hipFree(d_ws);
+    const int rc = dtext_bins<RsBins>(A, ctx->regtab.ni, (hipStream_t)stream, &ch);
     if (rc != SID_OK) return rc;
     if (!sid_rs_check(ch, ni)) return SID_ESTATE;
     sid_rs_add(&tab, ch);
@@ -6486,32 +6500,46 @@ static int window_stage(const SiteArgs<Off>& A, sid_chunk_ws* W, uint64_t text_b
     return SID_OK;
 }
 
-// The depth histogram's stage of one chunk, beside the window stage: the next set's count, rows and pinned
-// block.  A set holds every depth, so there is nothing to size and no chunk runs again for it.
-template <int MODE, bool OPT, class Off>
-static int depth_hist_stage(const SiteArgs<Off>& A, sid_chunk_ws* W, hipStream_t st)
+// A bin-rows stage of one chunk (P: DhBins, RsBins), beside the window stage: the next set's count, rows and
+// pinned block.  A set holds every bin, so there is nothing to size and no chunk runs again for it.
+template <class P, int MODE, bool OPT, class Off>
+static int bin_stage(const SiteArgs<Off>& S, sid_chunk_ws* W, hipStream_t st)
 {
-    if (!W->dh_bins) return SID_ESTATE;   // (a workspace not reserved)
-    const int b = (W->dh_cur ^= 1);
-    launch_depth_hist<MODE, OPT>(A, DhBufs{W->dh_bins, W->dh_cnt[b], W->dh_rows[b], W->dh_eager[b],
-                                              (unsigned long long*)W->dh_eager[b]}, st);
+    auto& T = P::sets(W);
+    SiteArgs<Off> A = S;
+    if (!T.bins || !P::bind(W, &A)) return SID_ESTATE;   // (a workspace not reserved)
+    const int b = (T.cur ^= 1);
+    launch_bins<MODE, OPT>(A, BinBufs<P>{T.bins, T.n, T.cnt[b], T.rows[b], T.eager[b], (unsigned long long*)T.eager[b]},
+                           st);
     WCHECK(hipGetLastError());
     return SID_OK;
 }
 
-// The region rows' stage of one chunk, beside the histogram's: the next set's count, rows and pinned block.  A
-// set holds every interval, so there is nothing to size and no chunk runs again for it.
-template <int MODE, bool OPT, class Off>
-static int region_stats_stage(const SiteArgs<Off>& S, sid_chunk_ws* W, hipStream_t st)
+// a table of n bins (allocated for one at least) and its two sets, all zero
+template <class P>
+static int bin_sets_reserve(sid_bin_sets<typename P::Bin, typename P::Row>* T, uint32_t n)
 {
-    if (!W->rs_bins || !W->rs_tab || W->rs_tab->ni != W->rs_ni) return SID_ESTATE;   // (a workspace not reserved)
-    const int b = (W->rs_cur ^= 1);
-    SiteArgs<Off> A = S;
-    A.T = *W->rs_tab;
-    launch_region_stats<MODE, OPT>(A, RsBufs{W->rs_bins, W->rs_cnt[b], W->rs_rows[b], W->rs_eager[b],
-                                             (unsigned long long*)W->rs_eager[b]}, st);
-    WCHECK(hipGetLastError());
+    const size_t m = std::max<size_t>(n, 1);
+    T->n = n;
+    WCHECK(hipMalloc(&T->bins, m * sizeof(typename P::Bin)));
+    WCHECK(hipMemset(T->bins, 0, m * sizeof(typename P::Bin)));
+    for (int b = 0; b < 2; ++b) {
+        WCHECK(hipMalloc(&T->cnt[b], 8));
+        WCHECK(hipMemset(T->cnt[b], 0, 8));
+        WCHECK(hipMalloc(&T->rows[b], m * sizeof(typename P::Row)));
+        WCHECK(hipHostMalloc((void**)&T->eager[b], P::EAGER_BYTES, hipHostMallocDefault));
+        std::memset(T->eager[b], 0, P::EAGER_BYTES);
+    }
     return SID_OK;
+}
+
+template <class Bin, class Row>
+static void bin_sets_release(sid_bin_sets<Bin, Row>* T)
+{
+    for (void* p : {(void*)T->bins, (void*)T->cnt[0], (void*)T->cnt[1], (void*)T->rows[0], (void*)T->rows[1]})
+        if (p) (void)hipFree(p);
+    for (char* p : T->eager)
+        if (p) (void)hipHostFree(p);
 }
 
 int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites)
@@ -6536,30 +6564,14 @@ int sid_chunk_reserve(sid_chunk_ws* W, uint64_t bytes, uint64_t sites)
             if (rc != SID_OK) return rc;
         }
     }
-    if (W->dh_on && !W->dh_bins) {   // the depth histogram's table and its two sets of count, rows and pinned block
-        WCHECK(hipMalloc(&W->dh_bins, (size_t)SID_DH_BINS * 3 * 4));
-        WCHECK(hipMemset(W->dh_bins, 0, (size_t)SID_DH_BINS * 3 * 4));
-        for (int b = 0; b < 2; ++b) {
-            WCHECK(hipMalloc(&W->dh_cnt[b], 8));
-            WCHECK(hipMemset(W->dh_cnt[b], 0, 8));
-            WCHECK(hipMalloc(&W->dh_rows[b], (size_t)SID_DH_BINS * sizeof(sid_dh_row)));
-            WCHECK(hipHostMalloc((void**)&W->dh_eager[b], SID_DH_EAGER_BYTES, hipHostMallocDefault));
-            std::memset(W->dh_eager[b], 0, SID_DH_EAGER_BYTES);
-        }
+    if (W->dh_on && !W->dh.bins) {   // the depth histogram's table and its two sets of count, rows and pinned block
+        const int rc = bin_sets_reserve<DhBins>(&W->dh, SID_DH_BINS);
+        if (rc != SID_OK) return rc;
     }
-    if (W->rs_on && !W->rs_bins) {   // the region rows' table and its two sets, likewise
+    if (W->rs_on && !W->rs.bins) {   // the region rows' likewise, a bin per interval
         if (!W->rs_tab || W->rs_tab->ni > SID_REGION_STATS_MAX) return SID_ESTATE;
-        const size_t ni = std::max<size_t>(W->rs_tab->ni, 1);
-        W->rs_ni = W->rs_tab->ni;
-        WCHECK(hipMalloc(&W->rs_bins, ni * sizeof(sid_rs_bin)));
-        WCHECK(hipMemset(W->rs_bins, 0, ni * sizeof(sid_rs_bin)));
-        for (int b = 0; b < 2; ++b) {
-            WCHECK(hipMalloc(&W->rs_cnt[b], 8));
-            WCHECK(hipMemset(W->rs_cnt[b], 0, 8));
-            WCHECK(hipMalloc(&W->rs_rows[b], ni * sizeof(sid_rs_row)));
-            WCHECK(hipHostMalloc((void**)&W->rs_eager[b], SID_RS_EAGER_BYTES, hipHostMallocDefault));
-            std::memset(W->rs_eager[b], 0, SID_RS_EAGER_BYTES);
-        }
+        const int rc = bin_sets_reserve<RsBins>(&W->rs, W->rs_tab->ni);
+        if (rc != SID_OK) return rc;
     }
     const uint64_t tiles = ((bytes + 16 + IX_TILE - 1) / IX_TILE + 1) * IX_SUB;   // 4 KiB tiles, in whole index tiles
     if (tiles > W->tile_cap) {
@@ -6645,13 +6657,12 @@ void sid_chunk_release(sid_chunk_ws* W)
                     (void*)W->cx_bits, (void*)W->cx_sum, (void*)W->cx_car, (void*)W->cx_hk, (void*)W->cx_desc,
                     (void*)W->win_bits, W->win_key, (void*)W->win_hcnt, (void*)W->win_roff, (void*)W->win_cnt[0],
                     (void*)W->win_cnt[1], (void*)W->win_rows[0], (void*)W->win_rows[1], (void*)W->win_names[0],
-                    (void*)W->win_names[1], (void*)W->refb, (void*)W->dh_bins, (void*)W->dh_cnt[0],
-                    (void*)W->dh_cnt[1], (void*)W->dh_rows[0], (void*)W->dh_rows[1], (void*)W->rs_bins,
-                    (void*)W->rs_cnt[0], (void*)W->rs_cnt[1], (void*)W->rs_rows[0], (void*)W->rs_rows[1]})
+                    (void*)W->win_names[1], (void*)W->refb})
         if (p) (void)hipFree(p);
-    for (void* p : {(void*)W->win_h, (void*)W->win_eager[0], (void*)W->win_eager[1], (void*)W->dh_eager[0],
-                    (void*)W->dh_eager[1], (void*)W->rs_eager[0], (void*)W->rs_eager[1]})
+    for (void* p : {(void*)W->win_h, (void*)W->win_eager[0], (void*)W->win_eager[1]})
         if (p) (void)hipHostFree(p);
+    bin_sets_release(&W->dh);
+    bin_sets_release(&W->rs);
     const bool dh_on = W->dh_on;
     const bool rs_on = W->rs_on;
     const sid_regtab* rs_tab = W->rs_tab;
@@ -6823,11 +6834,11 @@ int sid_chunk_fmt_len(sid_chunk_ws* W, const char* base, uint64_t c1, uint64_t n
         if (rc != SID_OK) return rc;
     }
     if (W->dh_on) {   // the depth histogram, likewise
-        const int rc = depth_hist_stage<REG_CODE, false>(S, W, st);
+        const int rc = bin_stage<DhBins, REG_CODE, false>(S, W, st);
         if (rc != SID_OK) return rc;
     }
     if (W->rs_on) {   // the region rows, likewise
-        const int rc = region_stats_stage<REG_CODE, false>(S, W, st);
+        const int rc = bin_stage<RsBins, REG_CODE, false>(S, W, st);
         if (rc != SID_OK) return rc;
     }
     if (W->regions) {   // the sites outside the region set: dropped in the workspace's codes
@@ -6917,13 +6928,13 @@ int sid_chunk_local_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
         if (rc != SID_OK) return rc;
     }
     if (W->dh_on) {   // the depth histogram, likewise
-        const int rc = W->cls_ready ? depth_hist_stage<REG_DENSE, false>(S, W, st)
-                                    : depth_hist_stage<REG_DENSE, true>(S, W, st);
+        const int rc = W->cls_ready ? bin_stage<DhBins, REG_DENSE, false>(S, W, st)
+                                    : bin_stage<DhBins, REG_DENSE, true>(S, W, st);
         if (rc != SID_OK) return rc;
     }
     if (W->rs_on) {   // the region rows, likewise
-        const int rc = W->cls_ready ? region_stats_stage<REG_DENSE, false>(S, W, st)
-                                    : region_stats_stage<REG_DENSE, true>(S, W, st);
+        const int rc = W->cls_ready ? bin_stage<RsBins, REG_DENSE, false>(S, W, st)
+                                    : bin_stage<RsBins, REG_DENSE, true>(S, W, st);
         if (rc != SID_OK) return rc;
     }
     if (nb && ctx->has_regions) {
@@ -7158,11 +7169,11 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
             if (rc != SID_OK) return rc;
         }
         if (W->dh_on) {   // (likewise)
-            const int rc = depth_hist_stage<REG_TILE, false>(S, W, st);
+            const int rc = bin_stage<DhBins, REG_TILE, false>(S, W, st);
             if (rc != SID_OK) return rc;
         }
         if (W->rs_on) {   // (likewise)
-            const int rc = region_stats_stage<REG_TILE, false>(S, W, st);
+            const int rc = bin_stage<RsBins, REG_TILE, false>(S, W, st);
             if (rc != SID_OK) return rc;
         }
         if (ctx->cx_on) launch_context_mark<REG_TILE, false>(S, W, st);   // (the empty descriptor)
@@ -7189,11 +7200,11 @@ int sid_chunk_tile_local(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64
         if (rc != SID_OK) return rc;
     }
     if (W->dh_on) {   // the depth histogram, likewise
-        const int rc = quad ? depth_hist_stage<REG_TILE, false>(S, W, st) : depth_hist_stage<REG_TILE, true>(S, W, st);
+        const int rc = quad ? bin_stage<DhBins, REG_TILE, false>(S, W, st) : bin_stage<DhBins, REG_TILE, true>(S, W, st);
         if (rc != SID_OK) return rc;
     }
     if (W->rs_on) {   // the region rows, likewise
-        const int rc = quad ? region_stats_stage<REG_TILE, false>(S, W, st) : region_stats_stage<REG_TILE, true>(S, W, st);
+        const int rc = quad ? bin_stage<RsBins, REG_TILE, false>(S, W, st) : bin_stage<RsBins, REG_TILE, true>(S, W, st);
         if (rc != SID_OK) return rc;
     }
     if (ctx->has_regions) {   // the slots outside the region set: the skip word, and their groups' sums again
@@ -7293,11 +7304,11 @@ int sid_chunk_lynch_len(sid_ctx* ctx, sid_chunk_ws* W, const char* base, uint64_
         if (rc != SID_OK) return rc;
     }
     if (W->dh_on) {   // the depth histogram, likewise
-        const int rc = depth_hist_stage<REG_LYNCH, false>(S, W, st);
+        const int rc = bin_stage<DhBins, REG_LYNCH, false>(S, W, st);
         if (rc != SID_OK) return rc;
     }
     if (W->rs_on) {   // the region rows, likewise
-        const int rc = region_stats_stage<REG_LYNCH, false>(S, W, st);
+        const int rc = bin_stage<RsBins, REG_LYNCH, false>(S, W, st);
         if (rc != SID_OK) return rc;
     }
     if (ctx->cx_on) {   // the context: counts 0 likewise (no class or no site: the empty descriptor)

@@ -15,7 +15,9 @@ import os
 import pytest
 
 import bgzf_ref
+import depth_hist_ref as DH
 import region_stats_ref as RS
+import windows_ref as WR
 from regions_ref import bed_runs, text_sites
 from test_select_gpu import BASES, line, run
 from test_windows import quirks_text
@@ -325,6 +327,46 @@ def test_state_and_reuse(sid, inputs):
     assert out == inputs.plain("mix", "local", chunk_bytes=20_000, select="het")[0]
     check_rows(inputs, "mix", "local", eng.region_stats())
     eng.close()
+
+
+def test_every_row_set_past_its_pinned_block(sid, oracle):
+    """The region rows, the depth histogram and the windows together, each with more rows a chunk than its pinned
+    block holds (256, 384 and 64), on the tile path, where the next chunk's stages run before this chunk's rows
+    are read: 5,000 sites at even positions, site i of depth 1 + i % 500 (lines of up to 1 KB, so a 512 KiB chunk
+    has more than 500 consecutive sites), an interval a site, a window a site."""
+    def bases(i):
+        d = 1 + i % 500
+        return b"." * (d - d // 2) + b"G" * (d // 2) if i % 7 == 0 else b"." * d
+    n = 5000
+    text = b"".join(line(b"chrO", 2 * i, False, bases(i)) for i in range(1, n + 1))
+    kw = dict(chunk_bytes=1 << 19)
+    opts = {"win": dict(window=2), "dh": dict(depth_hist=True), "rs": dict(region_stats=True)}
+
+    def engine_rows(**on):
+        r = sid.Regions(ones_bed(n))
+        eng = sid.Engine(regions=r, **kw, **on)
+        r.close()
+        eng.source_text(text)
+        out, st = eng.run()
+        rows = {"win": eng.windows() if "window" in on else None,
+                "dh": eng.depth_hist() if "depth_hist" in on else None,
+                "rs": eng.region_stats() if "region_stats" in on else None}
+        eng.close()
+        return out, st, rows
+
+    sites, codes = WR.site_codes(sid, oracle, text, "local")
+    ds = DH.depths(sid.parse_text(text).counts)
+    r = sid.Regions(ones_bed(n))
+    want = {"win": WR.rows(sites, codes, 2), "dh": DH.rows(ds, codes), "rs": RS.rows(RS.intervals(r), sites, codes, ds)}
+    r.close()
+    assert len(want["win"]) == n and len(want["dh"]) == 500 and len(want["rs"]) == n
+    out, st, rows = engine_rows(**opts["win"], **opts["dh"], **opts["rs"])
+    assert st.chunks >= 3 and st.chunks_tiled > 0, (st.chunks, st.chunks_tiled)
+    for k in opts:
+        assert rows[k] == want[k], (k, len(rows[k]), len(want[k]),
+                                    next(((a, b) for a, b in zip(rows[k], want[k]) if a != b), None))
+        assert engine_rows(**opts[k])[2][k] == rows[k], k   # the option alone
+    assert out == engine_rows()[0]
 
 
 def test_failing_run(sid, inputs):
