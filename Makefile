@@ -12,7 +12,7 @@ HOSTFLAGS ?= -O3 -std=c++17 -fPIC -Wall -Iinclude
 HIPFLAGS += $(EXTRA)
 
 KERNELS := local synth lynch textpath inflate
-HOSTSRC := capi lynch_host parse emit regions context windows depth_hist region_stats callable bgzf run
+HOSTSRC := capi lynch_host parse emit regions context windows depth_hist region_stats callable bgzf strip run
 OBJS := $(KERNELS:%=$(BUILD)/%.o) $(HOSTSRC:%=$(BUILD)/%.o)
 HDRS := include/sid.h $(wildcard $(SRC)/*.h)
 
@@ -23,7 +23,7 @@ $(BUILD)/%.o: $(SRC)/%.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # host-only translation units: compiled by hipcc as HIP (they include the HIP
-# runtime headers); parse/emit/regions/context/windows/depth_hist/region_stats/callable use no HIP at all
+# runtime headers); parse/emit/regions/context/windows/depth_hist/region_stats/callable/strip use no HIP at all
 $(BUILD)/%.o: $(SRC)/%.cpp $(HDRS)
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -47,6 +47,7 @@ clean:
 probes: $(BUILD)/libsid.so
 	$(HIPCC) -O3 -march=x86-64-v3 -o tools/debug/host_bw_probe tools/debug/host_bw_probe.cpp -lpthread
 	$(HIPCC) -O3 -o tools/debug/pcie_probe tools/debug/pcie_probe.cpp -lpthread
+	$(HIPCC) -O3 -std=c++17 -Iinclude -I$(SRC) -o tools/debug/strip_probe tools/debug/strip_probe.cpp $(SRC)/strip.cpp -lpthread
 	$(HIPCC) -O2 -Iinclude tools/debug/startup_probe.cpp -L$(BUILD) -lsid -Wl,-rpath,'$$ORIGIN' -o $(BUILD)/startup_probe
 	$(HIPCC) -O2 -Iinclude tools/debug/exit_probe.cpp -L$(BUILD) -lsid -Wl,-rpath,'$$ORIGIN' -o $(BUILD)/exit_probe
 

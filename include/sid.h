@@ -628,6 +628,30 @@ const uint8_t* sid_sites_refs(const sid_sites* s);      /* host, n              
 size_t sid_sites_chrom_segments(const sid_sites* s);
 const char* sid_sites_chrom_name(const sid_sites* s, size_t k, uint64_t* start);
 
+/* ------------------------------------------------------ line stripper ------
+ * A copy of a pileup text without the columns that only -m quality reads: of
+ * every line, the bytes from the end of its 5th token (tokens on runs of ' ' /
+ * '\t', leading ones skipped, as the reference's strtok_r) up to, not
+ * including, its newline are dropped.  A line is copied whole when it has
+ * fewer than five tokens, no final newline, or a byte below 0x20 other than
+ * '\t' in front of the cut.  For -m local, likelihood_ratio and bayes the
+ * stripped text gives the output, warnings and errors of the original.
+ *
+ * sid_strip_lines: in[0, n) into out (cap >= n, no overlap); returns the bytes
+ *   written ((size_t)-1: cap < n or a NULL buffer) and in *lines (may be NULL)
+ *   the lines copied, an unterminated last one included.  The widest variant
+ *   the CPU runs; all variants write the same bytes.
+ * sid_strip_lines_impl: one variant (1 scalar, 2 AVX2, 3 AVX-512; 0 as
+ *   above); (size_t)-1 when this CPU does not run it.  sid_strip_impl: the
+ *   variant 0 stands for.
+ * sid_strip_map: the offset in in[0, n) of the byte that sid_strip_lines
+ *   writes at out_off (a stripped line's newline: the input line's newline;
+ *   out_off at or past the output's end: n). */
+size_t sid_strip_lines(const char* in, size_t n, char* out, size_t cap, uint64_t* lines);
+size_t sid_strip_lines_impl(int impl, const char* in, size_t n, char* out, size_t cap, uint64_t* lines);
+int sid_strip_impl(void);
+size_t sid_strip_map(const char* in, size_t n, size_t out_off);
+
 /* ------------------------------------------------------ CSV emitter --------
  * Formats records [begin, end) exactly like operator<<(OutputRecord)
  * (call.hpp:29-38: chrom,pos,label,gt,%g,%g,conf_type) into buf; sites with
@@ -817,6 +841,17 @@ typedef struct {
                                the second pass copies into it instead of the
                                pinned ring.  Chunks beyond it take the HBM hold.
                                0 = off.  Ignored with device_sink 1             */
+    int strip;              /* host text that is pinned already, an option set
+                               that reads no quality column: strip crews (host
+                               threads, host_threads of them per device when set,
+                               else the process's CPUs less two, at most 14) drop
+                               the quality columns (sid_strip_lines) into pinned
+                               staging ahead of the upload, and the upload moves
+                               what they finished in time stripped, the rest as
+                               it is.  0 = on (SID_STRIP=0 in the environment:
+                               off), -1 = off; for tests, 1 = the upload waits
+                               for the crew on every chunk, 2 = on every other
+                               chunk (the others go as they are)               */
 } sid_engine_cfg;
 typedef struct {
     uint64_t sites;              /* non-empty lines parsed                           */
@@ -939,6 +974,12 @@ int sid_engine_source_synth(sid_engine* e, uint64_t seed, double mean_depth, uin
  * status (SID_EEMPTY, SID_EBADFUNC); emit writes `header` (unless NULL) and
  * the records through write(). */
 int sid_engine_ingest(sid_engine* e, sid_run_stats* stats);
+/* What the strip crews (sid_engine_cfg.strip) did in the last ingest: the
+ * chunks uploaded with bytes of theirs stripped, and the input bytes not
+ * uploaded for it (sid_run_stats.h2d_bytes = bytes_in - *strip_bytes, h2d_bytes
+ * staying the bytes the copies moved).  Both 0 without crews.  sid_run_stats
+ * has no field for them (its layout stands).  Either pointer may be NULL. */
+int sid_engine_strip_stats(const sid_engine* e, uint64_t* chunks_stripped, uint64_t* strip_bytes);
 int sid_engine_estimate(sid_engine* e, const sid_estimate* given, sid_estimate* out);
 int sid_engine_emit(sid_engine* e, const char* header, sid_write_fn write, void* user, sid_run_stats* stats);
 int sid_engine_run(sid_engine* e, const char* header, sid_write_fn write, void* user, sid_run_stats* stats);

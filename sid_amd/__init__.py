@@ -78,7 +78,7 @@ class EngineCfg(C.Structure):
     _fields_ = [("devices", C.c_int), ("first_device", C.c_int), ("chunk_bytes", C.c_uint64),
                 ("slots", C.c_int), ("hold_bytes", C.c_uint64), ("retain_bytes", C.c_uint64),
                 ("host_threads", C.c_int), ("verbose", C.c_int), ("device_sink", C.c_int), ("lanes", C.c_int),
-                ("host_hold_bytes", C.c_uint64)]
+                ("host_hold_bytes", C.c_uint64), ("strip", C.c_int)]
 
 
 class RunStats(C.Structure):
@@ -94,6 +94,10 @@ class RunStats(C.Structure):
     # the rows of the depth histogram (Engine(depth_hist=True)): no field of sid_run_stats, whose layout
     # stands -- Engine.emit sets it on the instance from sid_engine_depth_hist's count
     depth_rows = 0
+    # what the strip crews did (Engine(strip=...)): likewise no fields -- Engine.ingest sets them on the
+    # instance from sid_engine_strip_stats
+    chunks_stripped = 0
+    strip_bytes = 0
 
 
 class Window(C.Structure):
@@ -146,6 +150,11 @@ SIGNATURES = [
     ("sid_version", C.c_char_p, []),
     ("sid_opts_default", None, [C.POINTER(Opts)]),
     ("sid_select_mark", _I, [_P, _SZ, _I]),
+    ("sid_strip_lines", _SZ, [_P, _SZ, _P, _SZ, C.POINTER(_U64)]),
+    ("sid_strip_lines_impl", _SZ, [_I, _P, _SZ, _P, _SZ, C.POINTER(_U64)]),
+    ("sid_strip_impl", _I, []),
+    ("sid_engine_strip_stats", _I, [_P, C.POINTER(_U64), C.POINTER(_U64)]),
+    ("sid_strip_map", _SZ, [_P, _SZ, _SZ]),
     ("sid_context_mark", _I, [_P, _P, _SZ, _I]),
     ("sid_windows_host", _I, [_P, _SZ, _SZ, _P, _I, C.POINTER(C.POINTER(Window)), C.POINTER(C.c_size_t)]),
     ("sid_windows_free", None, [C.POINTER(Window)]),
@@ -1164,6 +1173,35 @@ class Context:
 
 HEADER = b"chrom,pos,label,gt,hom_conf,het_conf,conf_type\n"
 
+STRIP_AUTO, STRIP_SCALAR, STRIP_AVX2, STRIP_AVX512 = 0, 1, 2, 3
+
+
+def strip_lines(text: bytes, impl: int = STRIP_AUTO, align: int = 0):
+    """sid_strip_lines_impl: (the text without its quality columns, its lines),
+    or None when this CPU does not run the variant.  align: the input's first
+    byte sits that many bytes past a 64-B boundary."""
+    n = len(text)
+    raw = C.create_string_buffer(n + 128)
+    base = C.addressof(raw)
+    src = (base + 63) // 64 * 64 + align % 64
+    C.memmove(src, text, n)
+    out = C.create_string_buffer(max(n, 1))
+    lines = C.c_uint64(0)
+    m = lib().sid_strip_lines_impl(impl, src, n, out, n, C.byref(lines))
+    if m == C.c_size_t(-1).value:
+        return None
+    return out.raw[:m], lines.value
+
+
+def strip_impl() -> int:
+    """The variant STRIP_AUTO stands for on this CPU."""
+    return lib().sid_strip_impl()
+
+
+def strip_map(text: bytes, out_off: int) -> int:
+    """sid_strip_map: the input offset of the stripped text's byte out_off."""
+    return lib().sid_strip_map(text, len(text), out_off)
+
 
 class Engine:
     """The streaming engine (sid_engine_*): pileup text in, CSV out, in
@@ -1171,7 +1209,7 @@ class Engine:
 
     def __init__(self, method="local", devices=1, first_device=0, chunk_bytes=0, slots=0, hold_bytes=0,
                  retain_bytes=0, host_threads=0, verbose=False, device_sink=False, lanes=0, host_hold_bytes=0,
-                 min_depth=0, max_depth=0, format="csv", depth_hist=False, region_stats=False, **opts):
+                 min_depth=0, max_depth=0, format="csv", depth_hist=False, region_stats=False, strip=0, **opts):
         fmt = _format(format)
         self.opts = make_opts(method=method, **opts)
         cfg = EngineCfg()
@@ -1180,6 +1218,7 @@ class Engine:
         cfg.hold_bytes, cfg.retain_bytes, cfg.host_threads = hold_bytes, retain_bytes, host_threads
         cfg.verbose, cfg.device_sink, cfg.lanes = int(bool(verbose)), int(device_sink), lanes
         cfg.host_hold_bytes = host_hold_bytes
+        cfg.strip = int(strip)
         self.cfg = cfg
         h = C.c_void_p()
         check(lib().sid_engine_create(C.byref(self.opts), C.byref(cfg), C.byref(h)), "sid_engine_create")
@@ -1293,6 +1332,9 @@ class Engine:
     def ingest(self) -> RunStats:
         st = RunStats()
         rc = lib().sid_engine_ingest(self.h, C.byref(st))
+        chunks, nbytes = C.c_uint64(0), C.c_uint64(0)
+        check(lib().sid_engine_strip_stats(self.h, C.byref(chunks), C.byref(nbytes)), "sid_engine_strip_stats")
+        st.chunks_stripped, st.strip_bytes = chunks.value, nbytes.value
         if rc != 0:
             err = SidError(rc, "sid_engine_ingest")
             err.offset = st.err_offset

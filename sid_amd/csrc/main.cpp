@@ -843,6 +843,8 @@ int main(int argc, char** argv)
         int rc = sid_engine_ingest(eng, &st);
         if (rc == SID_EBGZF) bgzf_error(st.err_offset, false);
         if (rc != SID_OK) on_parse_error(rc);
+        uint64_t chunks_stripped = 0, strip_bytes = 0;   // (no fields of sid_run_stats: sid_engine_strip_stats)
+        (void)sid_engine_strip_stats(eng, &chunks_stripped, &strip_bytes);
         const double t1 = now();
         rc = sid_engine_estimate(eng, nullptr, &st.estimate);
         if (rc == SID_EEMPTY) {
@@ -904,7 +906,8 @@ int main(int argc, char** argv)
                          "\"bytes_out\": %llu, \"ingest_s\": %.6f, \"chunks_registered\": %llu, "
                          "\"register_s\": %.6f, \"h2d_s\": %.6f, \"h2d_bytes\": %llu, \"chunks_tiled\": %llu, "
                          "\"tile_overflows\": %llu, \"tile_overflows_queued\": %llu, \"bgzf_bytes\": %llu, "
-                         "\"bgzf_blocks\": %llu, \"window_rows\": %llu, \"depth_rows\": %llu, %s\"placement\": [%s], "
+                         "\"bgzf_blocks\": %llu, \"window_rows\": %llu, \"depth_rows\": %llu, \"chunks_stripped\": %llu, "
+                         "\"strip_bytes\": %llu, %s\"placement\": [%s], "
                          "\"main_entry_unix\": %.6f, \"main_exit_unix\": %.6f}\n",
                          (unsigned long long)st.sites, D, T, tc - t0, t1 - t0, t2 - t1, t3 - t2, t3 - t0,
                          st.sites / std::max(1e-9, t3 - t0), (unsigned long long)st.chunks,
@@ -915,7 +918,8 @@ int main(int argc, char** argv)
                          (unsigned long long)st.chunks_tiled, (unsigned long long)st.tile_overflows,
                          (unsigned long long)st.tile_overflows_queued, (unsigned long long)st.bgzf_bytes,
                          (unsigned long long)st.bgzf_blocks, (unsigned long long)st.window_rows,
-                         (unsigned long long)depth_rows, region_stats_json(region_rows, region_sites).c_str(),
+                         (unsigned long long)depth_rows, (unsigned long long)chunks_stripped,
+                         (unsigned long long)strip_bytes, region_stats_json(region_rows, region_sites).c_str(),
                          place.c_str(),
                          t_entry,
                          unix_now());

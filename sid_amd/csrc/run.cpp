@@ -55,6 +55,7 @@
 #include "depth_hist.h"
 #include "region_stats.h"
 #include "sid_internal.h"
+#include "strip.h"
 #include "synth.h"
 
 namespace {
@@ -256,6 +257,14 @@ struct ChunkRec {
     std::vector<sid_dh_row> dh;
     // the region rows (sid_engine_set_region_stats): the chunk's touched intervals, checked, read back likewise
     std::vector<sid_rs_row> rs;
+    // the strip crew (sid_engine_cfg.strip): the pieces the upload put together, in device order -- `dev`
+    // bytes on the device that stand for `raw` input bytes (stripped: by sid_strip_lines, else the same
+    // bytes); empty: the chunk went up as it is.  Read only to map a parse error's offset back
+    struct StripSeg {
+        uint64_t dev, raw;
+        bool stripped;
+    };
+    std::vector<StripSeg> smap;
 };
 
 enum SrcKind { SRC_NONE, SRC_HOST, SRC_FILE, SRC_DEVICE, SRC_SYNTH_HOST, SRC_SYNTH_DEVICE, SRC_BGZF, SRC_BGZF_FILE };
@@ -280,6 +289,8 @@ struct Loaded {
     const char* base = nullptr;
     uint64_t c0 = 0, c1 = 0;
     hipEvent_t ev = nullptr; // upload done (slot only)
+    // the stripped part of the text (the strip crew): its lines and bytes, the densest the tiles will see
+    uint64_t lines = 0, lbytes = 0;
 };
 
 struct OutItem {
@@ -437,6 +448,17 @@ struct Dev {
         else
             tile_set((uint64_t)((double)n * sid_tile_unit(q2) / (double)std::max<uint64_t>(1, bytes) * 1.25) + 1, q2);
     }
+    // before a chunk with `lines` lines in `bytes` of stripped text (the strip crew: about 1.6 times the
+    // lines per byte of the text the slots were learned on) is parsed: the slots that density needs, a
+    // quarter on top as for a new shape, when they exceed the current ones -- or its shape, when that differs
+    void tile_ahead(uint64_t lines, uint64_t bytes)
+    {
+        if (!lines || !bytes || !tile_ok) return;
+        const bool q2 = bytes > 256 * lines;
+        const uint64_t per = (uint64_t)((double)lines * sid_tile_unit(q2) / (double)bytes * 1.25) + 1;
+        if (q2 != tile_quad) tile_set(per, q2);
+        else if (((per + 15) & ~15ull) > tile_cap) tile_set(std::max(per, tile_hi), q2);
+    }
     // a tile had more lines than slots (the chunk goes the two-pass way); the
     // tile parse stays off while no shape has room for them: judged in the
     // units of the shape tile_set chose (a quad tile's lines counted in lane
@@ -470,6 +492,12 @@ struct Dev {
         tile_hi = 0;
         tile_ok = true;
     }
+    // the strip crew's pinned staging (sid_engine_cfg.strip): a ring of chunk-sized buffers, made once
+    // and reused by every run, and per buffer the event of the last copies out of it
+    static constexpr int STRIP_RING = 3;
+    char* sbuf[STRIP_RING] = {nullptr, nullptr, nullptr};
+    hipEvent_t sev[STRIP_RING] = {nullptr, nullptr, nullptr};
+    uint64_t scap = 0;
     uint64_t hold_budget = 0, retain_budget = 0;
     std::atomic<uint64_t> hold_used{0}, retain_used{0};
     std::atomic<bool> hold_full{false};
@@ -711,6 +739,39 @@ class Crew {
     bool stop_ = false;
 };
 
+// One device's strip crew for one ingest (sid_engine_cfg.strip).  Job k is the k-th chunk
+// of the device's uploader.  Crew thread t strips region t -- a line-aligned T-th -- of job k into its
+// part of staging buffer k % STRIP_RING, publishing after every STRIP_STEP input bytes how far it is
+// (whole lines, their bytes visible); the uploader, when it holds a device buffer for the chunk, takes
+// every region as far as it got -- the stripped bytes from the staging, the rest of the region from the
+// source -- and the crew goes on to job k + 1.  A buffer is written again once the copies out of it
+// are done (the leader, thread 0, waits for their event).
+constexpr uint64_t STRIP_STEP = 128u << 10;
+struct StripProg {
+    std::mutex m;
+    uint64_t in_done = 0, out_done = 0, lines = 0;
+    bool taken = false;   // the uploader has read it: the thread stops
+};
+struct StripJob {
+    std::unique_ptr<StripProg[]> P;   // per crew thread
+    std::vector<uint64_t> cut;        // the regions' bounds in the chunk, T + 1 of them
+};
+struct StripRun {
+    int T = 0;
+    int mode = 0;   // sid_engine_cfg.strip: 0 what is ready in time, 1 every chunk whole, 2 every other one
+    std::vector<StripJob> jobs;
+    std::mutex m;
+    std::condition_variable cv;
+    std::vector<int> fin;   // per job: the threads that have left it
+    uint64_t decided = 0;   // jobs [0, decided) were taken by the uploader
+    uint64_t ready = 0;     // jobs [0, ready) have their staging buffer free (the leader)
+    bool stop = false;      // the uploader is done
+    bool sev_used[Dev::STRIP_RING] = {false, false, false};   // the buffer's event was recorded in this run
+    bool wanted(uint64_t k) const { return mode != 2 || !(k & 1); }
+    // region t's place in a staging buffer: 64-B aligned, behind region t - 1's bytes
+    uint64_t place(const StripJob& J, int t) const { return (J.cut[t] + 64 * (uint64_t)t + 63) & ~(uint64_t)63; }
+};
+
 }  // namespace
 
 struct sid_engine {
@@ -746,6 +807,15 @@ struct sid_engine {
     std::atomic<uint64_t> t_comp_sync{0}, t_write_wait{0};
     std::atomic<uint64_t> reg_chunks{0};   // chunks uploaded from registered pages (upload_register)
     std::atomic<uint64_t> t_register{0};   // ns in hipHostRegister / hipHostUnregister (the uploaders)
+    // the strip crews (sid_engine_cfg.strip): threads per device (0: off), whether the source is host
+    // memory pinned already, this run's crews, its chunks uploaded with stripped bytes, the input bytes
+    // not uploaded, and the crews' busy time (ns in sid_strip_stream, summed over the threads)
+    int strip_T = 0;
+    bool src_pinned = false;
+    std::vector<std::unique_ptr<StripRun>> strip_runs;
+    std::atomic<uint64_t> strip_chunks{0}, strip_bytes{0}, t_strip{0};
+    std::atomic<uint64_t> t_strip_min{UINT64_MAX}, t_strip_max{0};   // ... and the least and most busy thread's
+    uint64_t last_h2d_bytes = 0;   // the last ingest's sid_run_stats.h2d_bytes (SID_ENGINE_TIMING)
     // host-generated input: pinned buffers
     std::vector<char*> gen_buf;
     std::vector<uint64_t> gen_cap;
@@ -915,6 +985,33 @@ uint64_t synth_host(const std::vector<uint64_t>& cdf, uint64_t seed, uint64_t fi
     return (uint64_t)(o - dst);
 }
 
+// The strip crew's threads per pipeline (sid_engine_cfg.strip; 0: no crew): host_threads when set, else
+// the CPUs the process may use -- the smaller of its affinity mask and its cgroup's cpu.max, shared among
+// LOCAL_WORLD_SIZE ranks and this engine's pipelines -- less two (the uploader, the compute thread), at
+// most 14.  Fewer than two: off.  SID_STRIP=0: off.
+int strip_threads(const sid_engine_cfg& cfg, int pipelines)
+{
+    if (cfg.strip < 0) return 0;
+    if (const char* v = std::getenv("SID_STRIP"))
+        if (std::atoi(v) == 0) return 0;
+    int T = cfg.host_threads;
+    if (T <= 0) {
+        cpu_set_t allowed;
+        long n = sched_getaffinity(0, sizeof allowed, &allowed) == 0 ? CPU_COUNT(&allowed) : 1;
+        if (FILE* f = std::fopen("/sys/fs/cgroup/cpu.max", "r")) {
+            long long quota = 0, period = 0;
+            if (std::fscanf(f, "%lld %lld", &quota, &period) == 2 && quota > 0 && period > 0)
+                n = std::min<long>(n, (long)std::max<long long>(1, quota / period));
+            std::fclose(f);
+        }
+        if (const char* w = std::getenv("LOCAL_WORLD_SIZE"))
+            if (std::atoi(w) > 1) n /= std::atoi(w);
+        n /= std::max(1, pipelines);
+        T = (int)std::min<long>(14, n - 2);
+    }
+    return T >= 2 ? std::min(T, 64) : 0;
+}
+
 }  // namespace
 
 // ================================================================= C ABI ==
@@ -997,6 +1094,7 @@ extern "C" int sid_engine_create(const sid_opts* opts, const sid_engine_cfg* cfg
         }
     e->cx_n = e->devs[0]->ctx->cx_n;
     e->cx_on = e->devs[0]->ctx->cx_on;
+    e->strip_T = strip_threads(e->cfg, D);
     *out = e;
     return SID_OK;
 }
@@ -1023,6 +1121,7 @@ static void drop_source(sid_engine* e)
     sid_bgzf_free(e->zidx);
     e->zidx = nullptr;
     e->src = SRC_NONE;
+    e->src_pinned = false;
     e->text = nullptr;
     e->text_len = 0;
     e->ingested = e->estimated = false;
@@ -1041,6 +1140,10 @@ extern "C" int sid_engine_destroy(sid_engine* e)
             if (s.ev_free) (void)hipEventDestroy(s.ev_free);
         }
         for (char* p : d->pinned) (void)hipHostFree(p);
+        for (char* p : d->sbuf)
+            if (p) (void)hipHostFree(p);
+        for (hipEvent_t ev : d->sev)
+            if (ev) (void)hipEventDestroy(ev);
         d->hh_free();
         for (hipEvent_t ev : d->pinned_ev) (void)hipEventDestroy(ev);
         for (hipEvent_t ev : d->ev_cache) (void)hipEventDestroy(ev);
@@ -1171,7 +1274,8 @@ extern "C" int sid_engine_source_text(sid_engine* e, const char* text, uint64_t 
     e->src = SRC_HOST;
     e->text = text;
     e->text_len = len;
-    e->reg_upload = upload_register() && len && !host_pinned(text);
+    e->src_pinned = len && host_pinned(text);
+    e->reg_upload = upload_register() && len && !e->src_pinned;
     split_host_text(e, text, len);
     assign_devices(e);
     return SID_OK;
@@ -1515,10 +1619,94 @@ struct UploadReg {
     }
 };
 
-// the uploader of device d: the chunks of `list` into device buffers, in order
-void uploader(sid_engine* e, Dev& d, const std::vector<uint64_t>& list, int pass)
+// The uploads of this run may be stripped (sid_engine_cfg.strip): host text that is pinned already, and
+// an option set that reads nothing behind a line's read bases (-m quality reads both quality columns)
+bool strip_eligible(const sid_engine* e)
+{
+    return e->strip_T >= 2 && e->src == SRC_HOST && e->src_pinned && !e->reg_upload &&
+           e->opts.method != SID_METHOD_QUALITY;
+}
+
+// thread t of device d's strip crew (StripRun): its region of every job, in the uploader's order
+void strip_worker(sid_engine* e, Dev& d, StripRun& S, const std::vector<uint64_t>& list, int t)
 {
     bind_thread(d);
+    if (t == 0) (void)hipSetDevice(d.device);   // (the leader waits for the staging buffers' events)
+    double busy = 0;
+    for (uint64_t k = 0; k < S.jobs.size(); ++k) {
+        if (!S.wanted(k)) continue;
+        const int b = (int)(k % Dev::STRIP_RING);
+        {
+            std::unique_lock<std::mutex> l(S.m);
+            if (t == 0) {
+                // the buffer's last job: taken by the uploader, and left by every thread -- one that was
+                // taken goes on writing into its region until its next tick
+                uint64_t last = k;
+                while (last >= (uint64_t)Dev::STRIP_RING && !S.wanted(last -= Dev::STRIP_RING)) {
+                }
+                if (last != k && S.wanted(last))
+                    S.cv.wait(l, [&] { return S.stop || (S.decided > last && S.fin[last] == S.T); });
+                if (S.stop) break;
+                if (S.sev_used[b]) {
+                    l.unlock();
+                    (void)hipEventSynchronize(d.sev[b]);
+                    l.lock();
+                }
+                S.ready = k + 1;
+                S.cv.notify_all();
+            } else {
+                S.cv.wait(l, [&] { return S.stop || S.ready > k; });
+            }
+            if (S.stop) break;
+        }
+        StripJob& J = S.jobs[k];
+        StripProg& P = J.P[t];
+        bool go;
+        {
+            std::lock_guard<std::mutex> l(P.m);
+            go = !P.taken;
+        }
+        if (go) {
+            const double t0 = wall();
+            (void)sid_strip_stream(e->text + e->recs[list[k]].off + J.cut[t], J.cut[t + 1] - J.cut[t],
+                                   d.sbuf[b] + S.place(J, t), STRIP_STEP,
+                                   [](void* u, uint64_t in_done, uint64_t out_done, uint64_t lines) {
+                                       StripProg& Q = *(StripProg*)u;
+                                       std::lock_guard<std::mutex> l(Q.m);
+                                       if (Q.taken) return false;
+                                       Q.in_done = in_done, Q.out_done = out_done, Q.lines = lines;
+                                       return true;
+                                   },
+                                   &P);
+            busy += wall() - t0;
+        }
+        std::lock_guard<std::mutex> l(S.m);
+        if (++S.fin[k] == S.T) S.cv.notify_all();
+    }
+    const uint64_t ns = (uint64_t)(busy * 1e9);
+    e->t_strip += ns;
+    for (uint64_t c = e->t_strip_min.load(); ns < c && !e->t_strip_min.compare_exchange_weak(c, ns);) {
+    }
+    for (uint64_t c = e->t_strip_max.load(); ns > c && !e->t_strip_max.compare_exchange_weak(c, ns);) {
+    }
+}
+
+// the uploader of device d: the chunks of `list` into device buffers, in order
+// (S: the device's strip crew in this pass, or null)
+void uploader(sid_engine* e, Dev& d, const std::vector<uint64_t>& list, int pass, StripRun* S = nullptr)
+{
+    bind_thread(d);
+    // (however this thread leaves: the crew stops waiting for it)
+    struct CrewStop {
+        StripRun* S;
+        ~CrewStop()
+        {
+            if (!S) return;
+            std::lock_guard<std::mutex> l(S->m);
+            S->stop = true;
+            S->cv.notify_all();
+        }
+    } crew_stop{S};
     if (hipSetDevice(d.device) != hipSuccess) return (void)fail(e, SID_EHIP);
     UploadReg reg(e, pass);
     // the ingest's uploads timed as one span on the upload stream, from the
@@ -1552,7 +1740,112 @@ void uploader(sid_engine* e, Dev& d, const std::vector<uint64_t>& list, int pass
         }
         return UINT64_MAX;
     };
+    // Chunk j = job k of the crew, into dst: every region as far as its thread got -- those bytes from
+    // the staging buffer, the region's rest from the source (neighbouring rests in one copy).  Without
+    // cfg.strip 1 / 2 the link does not wait for the crew: the chunk is taken once the crew has left it,
+    // or the copies before it on the stream are done (prev_up), whichever comes first.
+    hipEvent_t prev_up = nullptr;   // the chunk before's upload done (null: it was waited for)
+    auto strip_copy = [&](uint64_t k, ChunkRec& r, char* dst, Loaded& L, uint64_t* moved) -> hipError_t {
+        StripJob& J = S->jobs[k];
+        const int T = S->T, b = (int)(k % Dev::STRIP_RING);
+        const char* src = e->text + r.off;
+        if (S->wanted(k)) {
+            std::unique_lock<std::mutex> l(S->m);
+            while (S->fin[k] < T && e->rc.load() == SID_OK) {
+                if (S->mode == 0) {
+                    l.unlock();
+                    const bool idle = !prev_up || hipEventQuery(prev_up) == hipSuccess;
+                    (void)hipGetLastError();   // (hipErrorNotReady)
+                    l.lock();
+                    if (idle) break;
+                }
+                S->cv.wait_for(l, std::chrono::microseconds(S->mode == 0 ? 50 : 1000));
+            }
+        }
+        hipError_t x = hipSuccess;
+        uint64_t o = 0, raw0 = 0, rawn = 0;   // the device offset; the source bytes waiting for their copy
+        bool staged = false;
+        r.smap.clear();
+        auto flush_raw = [&] {
+            if (!rawn) return;
+            if (x == hipSuccess) x = hipMemcpyAsync(dst + o, src + raw0, rawn, hipMemcpyHostToDevice, d.s_up);
+            r.smap.push_back({rawn, rawn, false});
+            o += rawn;
+            rawn = 0;
+        };
+        for (int t = 0; t < T; ++t) {
+            uint64_t in_done, out_done, lines;
+            {
+                std::lock_guard<std::mutex> l(J.P[t].m);
+                J.P[t].taken = true;
+                in_done = J.P[t].in_done, out_done = J.P[t].out_done, lines = J.P[t].lines;
+            }
+            const uint64_t a = J.cut[t], n = J.cut[t + 1] - a;
+            if (in_done) {
+                flush_raw();
+                if (x == hipSuccess)
+                    x = hipMemcpyAsync(dst + o, d.sbuf[b] + S->place(J, t), out_done, hipMemcpyHostToDevice, d.s_up);
+                r.smap.push_back({out_done, in_done, true});
+                o += out_done;
+                staged = true;
+                L.lines += lines;
+                L.lbytes += out_done;
+            }
+            if (in_done < n) {
+                if (!rawn) raw0 = a + in_done;
+                rawn += n - in_done;
+            }
+        }
+        flush_raw();
+        if (staged && x == hipSuccess) x = hipEventRecord(d.sev[b], d.s_up);
+        {
+            std::lock_guard<std::mutex> l(S->m);
+            S->sev_used[b] |= staged;
+            S->decided = k + 1;
+            S->cv.notify_all();
+        }
+        if (o < r.len) {
+            e->strip_chunks++;
+            e->strip_bytes += r.len - o;
+        } else {
+            r.smap.clear();   // (nothing dropped: the bytes are the input's)
+        }
+        *moved = o;
+        return x;
+    };
+    // Pass 2 reads a chunk again whose upload in pass 1 was stripped: the same bytes again, piece by piece
+    // (ChunkRec::smap; a piece's stripped form depends on its bytes alone) -- the parse kept since pass 1
+    // (ChunkRec::pre) holds line offsets into them.  Stripped by this thread into the first staging
+    // buffer, which no crew uses in pass 2, and waited for.
+    auto strip_again = [&](ChunkRec& r, char* dst, uint64_t* moved) -> hipError_t {
+        const char* src = e->text + r.off;
+        hipError_t x = hipSuccess;
+        uint64_t o = 0, raw = 0, so = 0;
+        for (const auto& g : r.smap) {
+            if (x != hipSuccess) break;
+            if (!g.stripped) {
+                x = hipMemcpyAsync(dst + o, src + raw, g.raw, hipMemcpyHostToDevice, d.s_up);
+            } else {
+                if (so + g.raw > d.scap) {   // (the buffer's earlier pieces copied first)
+                    x = hipStreamSynchronize(d.s_up);
+                    so = 0;
+                }
+                if (x != hipSuccess || g.raw > d.scap) return x != hipSuccess ? x : hipErrorUnknown;
+                const size_t m = sid_strip_lines(src + raw, g.raw, d.sbuf[0] + so, g.raw, nullptr);
+                if (m != g.dev) return hipErrorUnknown;   // cannot happen: the bytes pass 1 stripped
+                x = hipMemcpyAsync(dst + o, d.sbuf[0] + so, m, hipMemcpyHostToDevice, d.s_up);
+                so += (m + 63) & ~(uint64_t)63;
+            }
+            o += g.dev;
+            raw += g.raw;
+        }
+        if (x == hipSuccess) x = hipStreamSynchronize(d.s_up);
+        *moved = o;
+        return x;
+    };
+    uint64_t jobs = 0;
     for (uint64_t j : list) {
+        const uint64_t k = jobs++;   // (pass 1 of host text: every chunk of the list gets here, the crew's job k)
         if (e->rc.load() != SID_OK) break;
         if (pass == 1 && j > e->first_err.load()) break;
         ChunkRec& r = e->recs[j];
@@ -1665,7 +1958,9 @@ void uploader(sid_engine* e, Dev& d, const std::vector<uint64_t>& list, int pass
         }
         if (src_host(e->src) || src_file(e->src)) {
             if (pass == 1 && len && !span.t0 && (span.t0 = d.h2d_event())) x = hipEventRecord(span.t0, d.s_up);
-            if (len && x == hipSuccess) x = reg.copy(cdst, j, d.s_up);
+            if (len && x == hipSuccess) x = S                                ? strip_copy(k, r, cdst, L, &len)
+                                            : pass == 2 && !r.smap.empty() ? strip_again(r, cdst, &len)
+                                                                           : reg.copy(cdst, j, d.s_up);
             if (pass == 1 && span.t0 && x == hipSuccess) span.bytes += len;
             // the next chunk's pages pinned while this copy runs; the ones
             // whose copies are done released
@@ -1782,6 +2077,7 @@ void uploader(sid_engine* e, Dev& d, const std::vector<uint64_t>& list, int pass
         L.c0 = 0;
         L.c1 = len;
         L.ev = ev;
+        prev_up = ev;
         if (pass == 2) e->reloaded++;
         if (!d.loaded.push(L)) break;
     }
@@ -1933,6 +2229,7 @@ void compute(sid_engine* e, Dev& d, int pass)
         int rc = SID_OK;
         hipError_t x = hipSuccess;
         if (L.ev && !pre_indexed && !pre_tiled) x = hipStreamWaitEvent(d.s_comp, L.ev, 0);
+        if (!pre_tiled) d.tile_ahead(L.lines, L.lbytes);   // (stripped text: slots for its lines per byte)
         const bool P = e->prof;
         if (P && pass == 1) d.prof_chunks++;   // chunks, not passes: a Lynch run formats each chunk again in pass 2
         if (!pre_tiled) {
@@ -2046,6 +2343,7 @@ void compute(sid_engine* e, Dev& d, int pass)
                     have_next = true;
                     const ChunkRec& r2 = e->recs[nextL.j];
                     if (nextL.kind == 0 && !(pass == 2 && r2.pre) && !(pass == 1 && nextL.j > e->first_err.load())) {
+                        d.tile_ahead(nextL.lines, nextL.lbytes);
                         const uint32_t lg2 = d.tile_cap;
                         const bool q2 = d.tile_quad;
                         if (nextL.ev) x = hipStreamWaitEvent(d.s_comp, nextL.ev, 0);
@@ -2637,9 +2935,14 @@ static void timing_report(sid_engine* e, const char* phase, double s)
     if (on)
         std::fprintf(stderr,
                      "{\"engine_phase\": \"%s\", \"s\": %.6f, \"compute_sync_s\": %.6f, \"writer_wait_s\": %.6f, "
-                     "\"chunks_registered\": %llu}\n",
+                     "\"chunks_registered\": %llu, \"strip_threads\": %d, \"strip_busy_s\": %.6f, "
+                     "\"strip_busy_min_s\": %.6f, \"strip_busy_max_s\": %.6f, "
+                     "\"chunks_stripped\": %llu, \"strip_bytes\": %llu, \"h2d_bytes\": %llu}\n",
                      phase, s, e->t_comp_sync.load() * 1e-9, e->t_write_wait.load() * 1e-9,
-                     (unsigned long long)e->reg_chunks.load());
+                     (unsigned long long)e->reg_chunks.load(), e->strip_T, e->t_strip.load() * 1e-9,
+                     e->t_strip_max.load() ? e->t_strip_min.load() * 1e-9 : 0.0, e->t_strip_max.load() * 1e-9,
+                     (unsigned long long)e->strip_chunks.load(), (unsigned long long)e->strip_bytes.load(),
+                     (unsigned long long)e->last_h2d_bytes);
     e->t_comp_sync = e->t_write_wait = 0;
     e->reg_chunks = 0;
     e->t_register = 0;
@@ -2666,6 +2969,7 @@ static void reset_run(sid_engine* e)
         r.sunk = false;
         r.err = ~0ull;
         r.zbad = ~0ull;
+        r.smap.clear();
         r.parsed = 0;
         r.cx = sid_cx_desc{};
         r.cx_total = 0;
@@ -2682,6 +2986,11 @@ static void reset_run(sid_engine* e)
     e->rs_ready = false;
     e->z_bytes = 0;
     e->z_blocks = 0;
+    e->strip_chunks = 0;
+    e->strip_bytes = 0;
+    e->t_strip = 0;
+    e->t_strip_min = UINT64_MAX;
+    e->t_strip_max = 0;
     for (auto& dp : e->devs) {
         Dev& d = *dp;
         d.hold_used = 0;
@@ -2785,6 +3094,66 @@ static int alloc_ring_here(Dev& d)
     return SID_OK;
 }
 
+// This run's strip crews (sid_engine_cfg.strip), one per pipeline, or none: the staging rings (made
+// once, grown when a run's chunks are larger; on the GPU's NUMA node) and every job's regions.  Without
+// the pinned memory for a ring the run goes without crews.
+static void setup_strip(sid_engine* e, const std::vector<std::vector<uint64_t>>& lists)
+{
+    e->strip_runs.clear();
+    if (!strip_eligible(e)) return;
+    const int T = e->strip_T;
+    for (size_t i = 0; i < e->devs.size(); ++i) {
+        Dev& d = *e->devs[i];
+        uint64_t need = 0;
+        for (uint64_t j : lists[i]) need = std::max(need, e->recs[j].len);
+        need += 64 * (uint64_t)(T + 2);
+        bool ok = true;
+        if (d.scap < need) on_node(d, [&] {
+            ok = hipSetDevice(d.device) == hipSuccess;
+            for (int b = 0; b < Dev::STRIP_RING && ok; ++b) {
+                if (d.sbuf[b]) (void)hipHostFree(d.sbuf[b]);
+                d.sbuf[b] = nullptr;
+                d.scap = 0;
+                ok = hipHostMalloc((void**)&d.sbuf[b], need, hipHostMallocDefault) == hipSuccess;
+                if (ok && !d.sev[b]) ok = hipEventCreateWithFlags(&d.sev[b], hipEventDisableTiming) == hipSuccess;
+            }
+            if (ok) d.scap = need;
+            else (void)hipGetLastError();
+        });
+        if (!ok) {
+            e->strip_runs.clear();
+            return;
+        }
+        auto S = std::make_unique<StripRun>();
+        S->T = T;
+        S->mode = e->cfg.strip;
+        S->jobs.resize(lists[i].size());
+        S->fin.assign(lists[i].size(), 0);
+        for (size_t k = 0; k < lists[i].size(); ++k) {
+            const ChunkRec& r = e->recs[lists[i][k]];
+            StripJob& J = S->jobs[k];
+            J.P.reset(new StripProg[T]);
+            J.cut.assign(T + 1, r.len);
+            J.cut[0] = 0;
+            for (int t = 1; t < T; ++t) J.cut[t] = next_line_start(e->text + r.off, r.len, r.len * t / T);
+        }
+        e->strip_runs.push_back(std::move(S));
+    }
+}
+
+// A parse error's offset in a chunk as the device saw it -> in the chunk's input bytes (ChunkRec::smap)
+static uint64_t strip_unmap(const sid_engine* e, const ChunkRec& r, uint64_t off)
+{
+    uint64_t dev = 0, raw = 0;
+    for (const auto& g : r.smap) {
+        if (off < dev + g.dev)
+            return raw + (g.stripped ? sid_strip_map(e->text + r.off + raw, g.raw, off - dev) : off - dev);
+        dev += g.dev;
+        raw += g.raw;
+    }
+    return raw + (off - dev);
+}
+
 extern "C" int sid_engine_ingest(sid_engine* e, sid_run_stats* st)
 {
     if (!e || e->src == SRC_NONE) return SID_EINVAL;
@@ -2814,11 +3183,14 @@ extern "C" int sid_engine_ingest(sid_engine* e, sid_run_stats* st)
     std::vector<std::vector<uint64_t>> lists(D);
     for (uint64_t j = 0; j < e->recs.size(); ++j) lists[e->recs[j].dev].push_back(j);
     std::vector<std::function<void()>> th;
+    setup_strip(e, lists);
     for (int i = 0; i < D; ++i) {
         Dev& d = *e->devs[i];
         const std::vector<uint64_t>& li = lists[i];
-        th.emplace_back([e, &d, &li] { uploader(e, d, li, 1); });
+        StripRun* S = e->strip_runs.empty() ? nullptr : e->strip_runs[i].get();
+        th.emplace_back([e, &d, &li, S] { uploader(e, d, li, 1, S); });
         th.emplace_back([e, &d] { compute(e, d, 1); });
+        for (int t = 0; S && t < S->T; ++t) th.emplace_back([e, &d, &li, S, t] { strip_worker(e, d, *S, li, t); });
     }
     // the emit's pinned ring, pinned on a thread of its own during the ingest
     // of a run that writes its records through it (no host arena, no device
@@ -2871,6 +3243,7 @@ extern "C" int sid_engine_ingest(sid_engine* e, sid_run_stats* st)
         tile_oq += dp->tile_over_queued;
         dp->tiled = dp->tile_overflows = dp->tile_over_queued = 0;
     }
+    e->last_h2d_bytes = h2d_bytes;
     uint64_t sites = 0, bytes = 0, held = 0, kept = 0;
     for (auto& r : e->recs) {
         sites += r.parsed;
@@ -2914,12 +3287,20 @@ extern "C" int sid_engine_ingest(sid_engine* e, sid_run_stats* st)
                                                                                              : SID_ENOBQ;
         if (st) {
             st->status_kind = prc;
-            st->err_offset = (src_bgzf(e->src) ? r.toff : r.off) + (r.err >> 3);
+            st->err_offset = (src_bgzf(e->src) ? r.toff : r.off) + strip_unmap(e, r, r.err >> 3);
         }
         return prc;
     }
     e->ingested = true;
     e->estimated = !e->lynch;
+    return SID_OK;
+}
+
+extern "C" int sid_engine_strip_stats(const sid_engine* e, uint64_t* chunks_stripped, uint64_t* strip_bytes)
+{
+    if (!e) return SID_EINVAL;
+    if (chunks_stripped) *chunks_stripped = e->strip_chunks.load();
+    if (strip_bytes) *strip_bytes = e->strip_bytes.load();
     return SID_OK;
 }
 
